@@ -2,12 +2,13 @@
 """bench.py -- frames/sec of the acoustic-likelihood hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gmm|full|recipe]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input:
   full   (BASELINE configs[2], the default `value` -- the metric's own "GMM log-lik + MFCC"
          workload): 1 h of 16 kHz int16 audio as 360 x 10 s utterances (449 280 frames), resident
          in HBM -> MFCC chain -> 50 000-Gaussian / 3 125-state x 16 diagonal HmmSet scoring ->
-         2-byte LNA codes.  The default run also reports the per-stage split, the HBM rooflines
+         2-byte LNA codes.  With --full the run also reports the per-stage split, the HBM rooflines
          of the feature chain and the LNA pass (roofline.stages), the fraction of LNA codes equal
          to the oracle's on a sampled utterance, the scoring stage under every arithmetic the engine
          has (config.precision_ladder: f16x2 / bf16x3 / f32) and under per-state precision routing
@@ -15,14 +16,28 @@ A "step" is one pass of the hot path over one batch of synthetic input:
          pass pyrectool runs (config.clustered), configs[1] (config.configs1), configs[4]
          (config.configs4) and configs[3] at full size -- the 10 000-utterance recipe, WAV files in,
          2-byte and 4-byte LNA files out (config.recipe_e2e; a 256-utterance miniature when /dev/shm
-         has no room) -- so one driver run carries all of them.
+         has no room) -- so one run carries all of them.
   gmm    (BASELINE configs[1]): 1 000 000 x 39 float32 frames, resident in HBM, against the same
          model -> [F x S] state log-likelihoods (k_gmm_diag_score_pl, two fp16 terms); no MFCC, no LNA.
+         With --full: configs[2] and the small recipe beside it.
   recipe (BASELINE configs[3]): a recipe of --utts (default 10 000) seeded utterances of
          U(2 s, 12 s) as WAV files, sliced over the ranks with Recipe::read's rule
          (aku/Recipe.cc:63-115), read -> features -> scoring -> 2-byte LNA files written; value =
          total frames / wall time of the slowest rank ("strong" scaling: the recipe is fixed),
          the device-only rate is reported beside it.
+
+A plain run sets up, warms up, times the --steps steps and prints the line: `roofline` and
+`cpu_baseline` are null there.  --full adds everything that takes runs of its own after the timed
+steps: the roofline block (the scoring kernel timed alone, clock and power, the matrix-pipe probe,
+committed PMC traffic), the secondary measurements named above (--secondary 0 leaves them out) and
+the CPU baseline (--cpu-frames 0 leaves it out).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed on rank 0 as
+DIR/<name>.npy (float32, 64 MB at most in all): a fixed, seeded sample of frames of its output --
+`full`: lna_codes (the 2-byte LNA codes as hi * 256 + lo) and state_loglik (the scores they were
+coded from), `gmm`: state_loglik, `recipe`: lna_codes of a seeded sample of the rank's utterances,
+read back from the last pass's LNA files.  The inputs are seeded, so two builds given the same
+arguments can be compared output for output.
 
 Multi-GPU: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) the rank takes its
 place; without it `--gpus N` (N > 1) starts the N ranks itself by re-executing this file under
@@ -94,9 +109,17 @@ def parse_args():
                     help="where the recipe workload keeps its WAV inputs and LNA outputs "
                          "(default: /dev/shm when it has room, else the system temp directory)")
     ap.add_argument("--secondary", type=int, default=int(os.environ.get("AASR_BENCH_SECONDARY", "1")),
-                    help="full / gmm workloads: also measure the other single-GPU config (configs[1] resp. configs[2]) "
-                         "and a small recipe run (1 = yes)")
-    return ap.parse_args()
+                    help="with --full, full / gmm workloads: also measure the other single-GPU config (configs[1] resp. "
+                         "configs[2]) and a small recipe run (1 = yes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline block, the secondary configs and the CPU "
+                         "baseline (a plain run reports the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write a seeded sample of what the last timed step computed to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # --------------------------------------------------------------------------- CPU baseline --
@@ -315,9 +338,11 @@ def run_recipe_e2e(args, capi, synth, shard, gmm, world, rank, sync_all, max_ove
         shutil.rmtree(workdir, ignore_errors=True)
 
 
-def run_recipe_workload(args, capi, synth, shard, gmm, world, rank, n_utts, steps, warmup, sync_all, workdir=None):
+def run_recipe_workload(args, capi, synth, shard, gmm, world, rank, n_utts, steps, warmup, sync_all, workdir=None,
+                        keep_outputs=False):
     """configs[3]: the rank's Recipe::read slice, files in, LNA files out.  Returns a dict
-    with the local figures; the caller aggregates over ranks."""
+    with the local figures; the caller aggregates over ranks.  keep_outputs: "outputs" holds
+    lna_codes of a seeded sample of the slice's utterances from the last pass's files."""
     feat = capi.Feat(synth.make_feature_config())
     lengths = recipe_lengths(n_utts)
     frames_all = np.array([feat.eof_frame(int(n)) for n in lengths], np.int64)
@@ -360,12 +385,66 @@ def run_recipe_workload(args, capi, synth, shard, gmm, world, rank, n_utts, step
         sync_all()
         wall = time.perf_counter() - t0
         assert st.frames == my_frames and st.utterances == count, (st.frames, my_frames, st.utterances, count)
-        return {"frames": my_frames, "utterances": count, "wall_s": wall, "device_s": dev_s, "copy_s": copy_s, "steps": steps,
-                "dir": os.path.dirname(workdir) if own else workdir, "lna_bytes_per_step": out_bytes,
-                "audio_bytes_per_step": in_bytes}
+        res = {"frames": my_frames, "utterances": count, "wall_s": wall, "device_s": dev_s, "copy_s": copy_s, "steps": steps,
+               "dir": os.path.dirname(workdir) if own else workdir, "lna_bytes_per_step": out_bytes,
+               "audio_bytes_per_step": in_bytes}
+        if keep_outputs:
+            last = os.path.join(workdir, "lna", "pass%d" % (passes[0] - 1))
+            res["outputs"] = {"lna_codes": _read_recipe_codes(last, frames_all, first, count, synth.SEED + 4003)}
+        return res
     finally:
         if own:
             shutil.rmtree(workdir, ignore_errors=True)
+
+
+# ------------------------------------------------------------------------ --dump-outputs --
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ROWS = 4096        # frames sampled per dump: [4096 x 3125] float32 = 51 MB; `full` takes half of it for each of its two arrays
+
+
+def _sample_rows(n, k, seed):
+    """A fixed, seeded, sorted sample of k of n row indices (all of them when n <= k)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False)).astype(np.int64)
+
+
+def _codes(byte_rows, S):
+    """2-byte LNA codes [rows x 2S] uint8 -> [rows x S] float32 values hi * 256 + lo."""
+    b = np.asarray(byte_rows).reshape(len(byte_rows), S, 2).astype(np.float32)
+    return b[..., 0] * 256.0 + b[..., 1]
+
+
+def _read_recipe_codes(lna_dir, frames_all, first, count, seed):
+    """lna_codes of the utterances of a seeded permutation of the slice [first, first + count), taken while they fit
+    in DUMP_ROWS frames (at least one), read from the 2-byte LNA files of `lna_dir` in utterance order."""
+    import struct
+    order = first + np.random.default_rng(seed).permutation(count)
+    pick, rows = [], 0
+    for i in order:
+        if pick and rows + int(frames_all[i]) > DUMP_ROWS:
+            break
+        pick.append(int(i))
+        rows += int(frames_all[i])
+    out = []
+    for i in sorted(pick):
+        data = open(os.path.join(lna_dir, "u%05d.lna" % i), "rb").read()
+        n_states, nbytes = struct.unpack(">IB", data[:5])
+        assert nbytes == 2, nbytes
+        out.append(_codes(np.frombuffer(data[5:], np.uint8).reshape(-1, n_states * 2), n_states))
+    return np.concatenate(out)
+
+
+def write_outputs(outdir, arrays):
+    """arrays: name -> float32 / float64 array, written as outdir/<name>.npy."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_MAX_BYTES))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 # -------------------------------------------------------------------------------- main --
@@ -470,7 +549,8 @@ def main():
     if args.workload == "recipe":
         # ---- configs[3]: wall clock over files in -> LNA files out; strong scaling
         n_utts = args.utts or 10000
-        res = run_recipe_workload(args, capi, synth, shard, gmm, world, rank, n_utts, args.steps, args.warmup, sync_all)
+        res = run_recipe_workload(args, capi, synth, shard, gmm, world, rank, n_utts, args.steps, args.warmup, sync_all,
+                                  keep_outputs=bool(args.dump_outputs) and rank == 0)
         elapsed = max_over_ranks(res["wall_s"])
         total_frames = sum_over_ranks(float(res["frames"]))
         dev_max = max_over_ranks(res["device_s"])
@@ -534,10 +614,28 @@ def main():
         ms_per_step = 1e3 * elapsed / args.steps
         value = world * F * args.steps / elapsed
 
-    # ---- dominant-kernel time: HIP events on the launch stream, scoring only
-    roofline = None
+    # ---- what the last timed step computed, before anything else touches the buffers (rank 0's share)
+    if args.dump_outputs and rank == 0:
+        if args.workload == "recipe":
+            outputs = res["outputs"]
+        elif args.workload == "gmm":
+            pick = torch.from_numpy(_sample_rows(F, DUMP_ROWS, synth.SEED + 4100)).to(dev)
+            outputs = {"state_loglik": d_out.index_select(0, pick)[:, :S].cpu().numpy()}
+        else:
+            pick = torch.from_numpy(_sample_rows(F, DUMP_ROWS // 2, synth.SEED + 4100)).to(dev)
+            outputs = {"lna_codes": _codes(runner.d_bytes.index_select(0, pick).cpu().numpy(), S),
+                       "state_loglik": runner.d_ll.index_select(0, pick)[:, :S].cpu().numpy()}
+        write_outputs(args.dump_outputs, outputs)
+
     dtype = "f32"
     if args.workload != "recipe":
+        dtype = {"f32": "f32",
+                 "bf16x3": "f32 (3-term bf16 split on the matrix cores, f32 accumulate)",
+                 "f16x2": "f32 (2-term fp16 split on the matrix cores, f32 accumulate)"}[args.precision]
+
+    # ---- dominant-kernel time: HIP events on the launch stream, scoring only
+    roofline = None
+    if args.workload != "recipe" and args.full:
         ev0 = torch.cuda.Event(enable_timing=True)
         ev1 = torch.cuda.Event(enable_timing=True)
         kreps = max(1, args.steps)
@@ -560,7 +658,7 @@ def main():
         algo_flop = 4.0 * DIM * float(F) * float(rows)
         achieved = algo_flop / (k_ms * 1e-3) / 1e12
         if args.precision == "f32":
-            kernel, peak, dtype = "k_gmm_diag_score_tracks<40,true>", FP32_MATRIX_PEAK_TFLOPS, "f32"
+            kernel, peak = "k_gmm_diag_score_tracks<40,true>", FP32_MATRIX_PEAK_TFLOPS
             peak_note = "dense FP32 matrix peak (v_mfma_f32_32x32x2_f32), MI355X_MICROARCH.md"
             products = 1.0
         elif args.precision == "bf16x3":
@@ -568,8 +666,7 @@ def main():
             # bits), six bf16 matrix-core products per f32 product (terms below 2^-16 dropped), f32
             # accumulation; it meets the same 1e-4 parity bar as the plain f32 kernel (--precision f32).
             # The ceiling for ALGORITHMIC flops on the bf16 pipe is therefore the dense bf16 peak / 6.
-            kernel, peak, dtype = ("k_gmm_diag_score_bf16x3<5,true,false,true,3>", BF16_MATRIX_PEAK_TFLOPS / 6.0,
-                                   "f32 (3-term bf16 split on the matrix cores, f32 accumulate)")
+            kernel, peak = "k_gmm_diag_score_bf16x3<5,true,false,true,3>", BF16_MATRIX_PEAK_TFLOPS / 6.0
             peak_note = ("dense BF16 matrix peak 2500 TFLOP/s / 6 bf16 products per f32-accurate product; "
                          "executed matrix flops = 6 * 160/156 * achieved")
             products = 6.0
@@ -578,8 +675,7 @@ def main():
             # (lo*lo dropped), f32 accumulation: same 1e-4 parity bar (state-level worst 3.4e-5 on 10^7 states,
             # tools/exp_fp16_split.py), chosen per model by its conditioning.  Ceiling for ALGORITHMIC flops:
             # the dense fp16 peak / 3.
-            kernel, peak, dtype = ("k_gmm_diag_score_pl<5,true,false,true,2>", BF16_MATRIX_PEAK_TFLOPS / 3.0,
-                                   "f32 (2-term fp16 split on the matrix cores, f32 accumulate)")
+            kernel, peak = "k_gmm_diag_score_pl<5,true,false,true,2>", BF16_MATRIX_PEAK_TFLOPS / 3.0
             peak_note = ("dense FP16 matrix peak 2500 TFLOP/s / 3 fp16 products per product; "
                          "executed matrix flops = 3 * 160/156 * achieved")
             products = 3.0
@@ -618,8 +714,9 @@ def main():
             roofline["traffic"] = td["bytes"]
             roofline["traffic_detail"] = td
 
-    # ---- secondary measurements of the default run (every rank takes part: they hold barriers)
-    if args.workload == "full" and args.secondary:
+    # ---- secondary measurements of a --full run (every rank takes part: they hold barriers)
+    secondary = args.full and args.secondary
+    if args.workload == "full" and secondary:
         # the per-stage split of the timed workload and its HBM-bound stages priced against 8 TB/s
         try:
             split = runner.stage_split(max(3, min(args.steps, 10)))
@@ -660,7 +757,7 @@ def main():
                 extra_cfg["configs4"] = _measure_configs4(torch, capi, synth, dev, stream)
             except Exception as e:
                 extra_cfg["configs4"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if args.workload == "gmm" and args.secondary:
+    if args.workload == "gmm" and secondary:
         try:
             del d_out
             torch.cuda.empty_cache()
@@ -669,7 +766,7 @@ def main():
                                                       PREC)
         except Exception as e:  # the headline must survive a failure of the extras
             extra_cfg["configs2"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if args.workload in ("gmm", "full") and args.secondary:
+    if args.workload in ("gmm", "full") and secondary:
         try:
             torch.cuda.empty_cache()
             extra_cfg["recipe_e2e"] = run_recipe_e2e(args, capi, synth, shard, gmm, world, rank, sync_all, max_over_ranks,
@@ -677,9 +774,9 @@ def main():
         except Exception as e:
             extra_cfg["recipe_e2e"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    # ---- CPU baseline (rank 0, N=1 only): oracle's reference-shaped loop
+    # ---- CPU baseline (--full, rank 0, N=1 only): oracle's reference-shaped loop
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         cpu = cpu_baseline(args, (mean, var, off, idx, w))
 
     if rank == 0:
@@ -694,7 +791,7 @@ def main():
         line = {
             "metric": METRIC,
             "metric_note": "value is the workload named in config.workload (default: configs[2], the metric's MFCC-inclusive chain); "
-                           "the GMM-only rate of configs[1] is config.configs1.frames_per_s",
+                           "the GMM-only rate of configs[1] is config.configs1.frames_per_s (--full runs)",
             "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": scaling, "vs_baseline": None, "dtype": dtype, "data": "synthetic",

@@ -42,12 +42,12 @@ def _have_device():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("args,key", [(["--utts", "24", "--frames", "40000", "--steps", "2", "--warmup", "1", "--cpu-frames", "200", "--cpu-procs", "2"], "default"),
-                                      (["--workload", "gmm", "--frames", "40000", "--steps", "2", "--warmup", "1", "--cpu-frames", "0"], "gmm"),
+@pytest.mark.parametrize("args,key", [(["--full", "--utts", "24", "--frames", "40000", "--steps", "2", "--warmup", "1", "--cpu-frames", "200", "--cpu-procs", "2"], "default"),
+                                      (["--full", "--workload", "gmm", "--frames", "40000", "--steps", "2", "--warmup", "1", "--cpu-frames", "0"], "gmm"),
                                       (["--workload", "recipe", "--utts", "40", "--steps", "1", "--warmup", "1", "--cpu-frames", "0"], "recipe")])
 def test_bench_line_on_a_gpu(args, key):
-    """One JSON line on stdout with the contract's keys, for each workload (small sizes).  The default
-    workload is BASELINE configs[2] -- the metric's own "GMM log-lik + MFCC" chain."""
+    """One JSON line on stdout with the contract's keys, for each workload (small sizes; the figures beyond the
+    headline under --full).  The default workload is BASELINE configs[2] -- the metric's own "GMM log-lik + MFCC" chain."""
     if not _have_device():
         pytest.skip("no HIP device on this host (bench.py has no CPU fallback)")
     r = _run(args)
@@ -91,7 +91,8 @@ def test_two_ranks_go_through_the_whole_default_run():
     """What a one-GPU box can check of `--gpus N`: the file under torch.distributed.run with two ranks -- both on
     device 0 and the collectives over gloo (AASR_BENCH_SHARE_GPU / AASR_BENCH_BACKEND: RCCL refuses two ranks on one
     device) -- reaches the end of the default run, secondary measurements included, with every barrier matched, and
-    rank 0 prints the one line with n_gpus = 2.  The line says that it is a rehearsal."""
+    rank 0 prints the one line with n_gpus = 2.  The line says that it is a rehearsal.  (--full: the secondary
+    measurements hold barriers of their own.)"""
     if not _have_device():
         pytest.skip("no HIP device on this host")
     e = dict(os.environ)
@@ -104,7 +105,7 @@ def test_two_ranks_go_through_the_whole_default_run():
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--utts", "24", "--frames", "40000",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--utts", "24", "--frames", "40000",
            "--steps", "2", "--warmup", "1", "--cpu-frames", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=e, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -115,3 +116,62 @@ def test_two_ranks_go_through_the_whole_default_run():
     assert "NOT a multi-GPU measurement" in d["config"]["rehearsal"]
     assert "error" not in d["config"]["configs1"] and "error" not in d["config"]["recipe_e2e"]
     assert d["config"]["recipe_e2e"]["what"].startswith("configs[3] in small: 512 utterances")
+
+
+def test_dump_helpers_read_lna_files_and_keep_the_cap(tmp_path):
+    """--dump-outputs on the host side: 2-byte LNA files read back as hi * 256 + lo codes, a seeded choice of
+    utterances that fits the frame budget, and a refusal to write more than the 64 MB cap."""
+    import numpy as np
+    import bench
+    S, frames = 7, np.array([3, 5, 2, 4], np.int64)
+    codes = {}
+    for i, n in enumerate(frames):
+        by = np.random.default_rng(i).integers(0, 256, (int(n), 2 * S), dtype=np.uint8)
+        with open(tmp_path / ("u%05d.lna" % i), "wb") as f:
+            f.write(S.to_bytes(4, "big") + bytes([2]) + by.tobytes())
+        codes[i] = by[:, 0::2].astype(np.float32) * 256 + by[:, 1::2]
+    got = bench._read_recipe_codes(str(tmp_path), frames, 1, 3, seed=5)
+    again = bench._read_recipe_codes(str(tmp_path), frames, 1, 3, seed=5)
+    assert got.dtype == np.float32 and got.shape == (11, S) and np.array_equal(got, again)
+    assert np.array_equal(got, np.concatenate([codes[1], codes[2], codes[3]]))
+    rows = bench._sample_rows(10 ** 6, 100, seed=1)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and np.array_equal(rows, bench._sample_rows(10 ** 6, 100, seed=1))
+    bench.write_outputs(str(tmp_path / "out"), {"a": np.zeros(4, np.float32)})
+    assert np.load(tmp_path / "out" / "a.npy").dtype == np.float32
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "big"), {"a": np.zeros((64 << 20) // 8 + 1, np.float64)})
+    assert not os.path.exists(tmp_path / "big")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("args,names", [(["--utts", "24"], ["lna_codes", "state_loglik"]),
+                                        (["--workload", "gmm", "--frames", "40000"], ["state_loglik"]),
+                                        (["--workload", "recipe", "--utts", "40"], ["lna_codes"])])
+def test_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(args, names, tmp_path):
+    """A plain run: the headline only (no roofline, no CPU baseline, no secondary configs), --steps timed steps,
+    and --dump-outputs writes float32 samples of the last step's output that two runs reproduce exactly."""
+    if not _have_device():
+        pytest.skip("no HIP device on this host")
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = _run(args + ["--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["roofline"] is None and d["cpu_baseline"] is None
+        assert not {"configs1", "configs2", "configs4", "recipe_e2e", "precision_ladder", "lna_check"} & set(d["config"])
+        assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in names)
+        arrays = {n: np.load(out / (n + ".npy")) for n in names}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        for n, a in arrays.items():
+            assert a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 3125 and a.shape[0] > 0, (n, a.shape)
+            assert np.isfinite(a).all()
+            if n == "lna_codes":
+                assert a.min() >= 0 and a.max() <= 65535 and np.array_equal(a, np.round(a))
+        dumps.append(arrays)
+    for n in names:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

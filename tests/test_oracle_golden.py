@@ -1,13 +1,33 @@
 """CPU tests that PIN THE ORACLE: against the reference's own golden files
 (aku/tests/*.ref with short.wav and the .feaconf files, copied as data under
 tests/golden/), against the real KissFFT / util.hh / ModuleConfig where
-oracle/_ref was built, and against hand-derived expectations of the text
-formats.  No GPU, no product code."""
+oracle/_ref was built (KissFFT, util.hh and the LNA reader elsewhere against
+their outputs recorded in tests/golden/reference_outputs.npz), and against
+hand-derived expectations of the text formats.  No GPU, no product code."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
+
+
+def _make_golden():
+    import importlib.util
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "make_golden.py")
+    spec = importlib.util.spec_from_file_location("make_golden", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+make_golden = _make_golden()     # the pins' inputs, shared with the tool that records the reference's outputs
+
+
+@pytest.fixture(scope="module")
+def recorded(golden_dir):
+    """What the reference's own code returned on the pins' inputs (tools/make_golden.py --reference): the pins
+    below compare with it where oracle/_ref was not built."""
+    return np.load(os.path.join(golden_dir, "reference_outputs.npz"))
 
 
 def _load(oracle, golden_dir, name):
@@ -52,37 +72,39 @@ def test_random_access_is_deterministic(oracle, golden_dir):
         assert np.abs(one[0] - seq[f + 10]).max() < 1e-12
 
 
-def test_fft_bit_exact_vs_reference_kissfft(oracle):
+def test_fft_bit_exact_vs_reference_kissfft(oracle, recorded):
+    """The oracle's real FFT against KissFFT's kiss_fftr, bit for bit: live where oracle/_ref holds the reference's
+    build, else against the SHA-256 of every output the reference produced on the same inputs."""
     K = oracle.ref_kissfft()
-    if K is None:
-        pytest.skip("oracle/_ref/libkissfft_ref.so not built (no reference tree)")
     L = oracle.lib()
-    rng = np.random.default_rng(2)
     pf = C.POINTER(C.c_float)
-    # the last six need the generic butterfly (prime factors 7, 11, 13, 17, 23 of the half length)
-    for n in (8, 32, 128, 256, 512, 1024, 6, 18, 200, 320, 400, 480, 600, 750, 1000, 14, 56, 220, 364, 442, 552):
-        cfg = K.kiss_fftr_alloc(n, 0, None, None)
-        for _ in range(20):
-            x = (rng.standard_normal(n) * 10 ** rng.uniform(-3, 4)).astype(np.float32)
-            out = np.zeros((n // 2 + 1) * 2, np.float32)
-            K.kiss_fftr(cfg, x.ctypes.data_as(pf), out.ctypes.data_as(pf))
-            re = np.zeros(n // 2 + 1, np.float32)
-            im = np.zeros(n // 2 + 1, np.float32)
-            assert L.orc_rfft(n, x.ctypes.data_as(pf), re.ctypes.data_as(pf), im.ctypes.data_as(pf)) == 0
-            assert np.array_equal(out[0::2].view(np.uint32), re.view(np.uint32))
-            assert np.array_equal(out[1::2].view(np.uint32), im.view(np.uint32))
+    # the last six sizes need the generic butterfly (prime factors 7, 11, 13, 17, 23 of the half length)
+    cfgs = {}
+    sha = recorded["kissfft_sha256"].reshape(-1, 32)
+    for i, (n, x) in enumerate(make_golden.fft_inputs()):
+        re = np.zeros(n // 2 + 1, np.float32)
+        im = np.zeros(n // 2 + 1, np.float32)
+        assert L.orc_rfft(n, x.ctypes.data_as(pf), re.ctypes.data_as(pf), im.ctypes.data_as(pf)) == 0
+        if K is None:
+            mine = np.empty((n // 2 + 1) * 2, np.float32)
+            mine[0::2], mine[1::2] = re, im
+            assert np.array_equal(make_golden.digest(mine), sha[i]), (n, i % make_golden.FFT_REPS)
+            continue
+        cfg = cfgs.setdefault(n, K.kiss_fftr_alloc(n, 0, None, None))
+        out = np.zeros((n // 2 + 1) * 2, np.float32)
+        K.kiss_fftr(cfg, x.ctypes.data_as(pf), out.ctypes.data_as(pf))
+        assert np.array_equal(out[0::2].view(np.uint32), re.view(np.uint32))
+        assert np.array_equal(out[1::2].view(np.uint32), im.view(np.uint32))
 
 
-def test_safe_log_and_str2float_vs_reference(oracle):
+def test_safe_log_and_str2float_vs_reference(oracle, recorded):
     A = oracle.ref_aku()
-    if A is None:
-        pytest.skip("oracle/_ref/libaku_ref.so not built (no reference tree)")
     L = oracle.lib()
-    for x in [0.0, 1e-60, 1e-50, 9.99e-51, 1.0000001e-50, 1.0, 3.3e-7, 1e300]:
-        assert A.ref_safe_log(x) == L.orc_safe_log(x)
     ok = C.c_int()
-    for s in ["0.97", "1e-3", "5.5112", "-6.36855e-05", "16777217", "0.1", "3.4e38"]:
-        assert np.float32(A.ref_str2float(s.encode(), C.byref(ok))) == oracle.str2float(s)
+    for x, want in zip(make_golden.SAFE_LOG_ARGS, recorded["safe_log"]):
+        assert (A.ref_safe_log(x) if A is not None else want) == L.orc_safe_log(x)
+    for s, want in zip(make_golden.STR2FLOAT_ARGS, recorded["str2float"]):
+        assert np.float32(A.ref_str2float(s.encode(), C.byref(ok)) if A is not None else want) == oracle.str2float(s)
 
 
 def test_module_config_parser_vs_reference(oracle, golden_dir):
@@ -324,26 +346,21 @@ def test_pre_module_golden(oracle, golden_dir):
 
 
 @pytest.mark.parametrize("nbytes", [2, 4])
-def test_lna_files_read_by_the_reference_decoder_reader(oracle, tmp_path, nbytes):
+def test_lna_files_read_by_the_reference_decoder_reader(oracle, recorded, tmp_path, nbytes):
     """The consumer side of the LNA format, pinned on the real reference code: a file written
     by the oracle's phone_probs restatement (aku/phone_probs.cc:213-262) is opened with the
     recogniser's own LnaReaderCircular (decoder/src/LnaReaderCircular.cc, compiled in place) and
     its log_prob() view is (a) what the oracle's lna_decode says and (b) within the format's
-    resolution of the log-probabilities phone_probs computed."""
-    if oracle.ref_lna() is None:
-        pytest.skip("oracle/_ref/liblna_ref.so not built (no reference tree)")
-    rng = np.random.default_rng(11)
-    F, S = 57, 43
-    lik = np.exp(rng.uniform(-60, 3, (F, S)))
-    lik[3, :] = 0.0                       # Z == 0 row
-    lik[5, 7] = 1e-300                    # far below the 2-byte range
-    lp, by = oracle.lna_encode(lik, True, nbytes)
+    resolution of the log-probabilities phone_probs computed.  Where oracle/_ref was not built, the reader's
+    output on the same file as recorded by tools/make_golden.py --reference."""
     path = str(tmp_path / "x.lna")
-    with open(path, "wb") as f:
-        f.write(oracle.lna_header(S, nbytes))
-        f.write(by.tobytes())
-    for order, buf in ((0, 1), (0, 8), (1, 8), (1, 57)):
-        got = oracle.ref_lna_read(path, F + 5, S, buf_size=buf, order=order)
+    F, S, lp = make_golden.lna_pin_file(path, nbytes)
+    live = oracle.ref_lna() is not None
+    if not live:
+        assert np.array_equal(make_golden.digest(np.frombuffer(open(path, "rb").read(), np.uint8)),
+                              recorded["lna%d_file_sha256" % nbytes]), "the oracle writes another file than the one recorded"
+    for k, (order, buf) in enumerate(make_golden.LNA_READS):
+        got = oracle.ref_lna_read(path, F + 5, S, buf_size=buf, order=order) if live else recorded["lna%d_reads" % nbytes][k]
         assert got.shape == (F, S)       # go_to() reports EOF exactly after the last frame
         want = oracle.lna_decode(open(path, "rb").read())
         assert np.array_equal(got, want.astype(np.float32))
