@@ -92,6 +92,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     bindir = os.path.join(LIBDIR, "bin")
     os.makedirs(bindir, exist_ok=True)
     for name, src in (("phone_probs", "aku/main_phone_probs.cc"),
+                      ("align", "aku/main_align.cc"),
                       ("aku_adapter_check", "aku/main_adapter_check.cc"),
                       ("feacat", "aku/main_feacat.cc"),
                       ("plugin_check", "aku/main_plugin_check.cc"),
@@ -101,6 +102,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if force or not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(srcp), os.path.getmtime(LIB)):
             cmd = [HIPCC, "-O2", "-std=c++17", srcp, "-o", exe, "-L", LIBDIR, "-laasr",
                    "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib"]
+            if name == "align":   # train.pl copies its align binary into a work directory before it runs it
+                cmd.append("-Wl,-rpath," + os.path.abspath(LIBDIR))
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError("building %s failed:\n%s\n%s" % (name, r.stdout, r.stderr))

@@ -93,6 +93,36 @@ def _declare(L: C.CDLL) -> None:
     i32, i64, f, d, vp, cp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p, C.c_char_p
     pvp = C.POINTER(vp)
     L.aasr_last_error.restype = cp
+    # forced alignment
+    L.aasr_topo_create_from_ph.argtypes = [cp, pvp]
+    L.aasr_topo_destroy.argtypes = [vp]
+    L.aasr_topo_destroy.restype = None
+    L.aasr_topo_num_hmms.argtypes = [vp]
+    L.aasr_topo_hmm_index.argtypes = [vp, cp]
+    L.aasr_topo_hmm_label.argtypes = [vp, i32]
+    L.aasr_topo_hmm_label.restype = cp
+    L.aasr_topo_hmm_num_states.argtypes = [vp, i32]
+    L.aasr_topo_hmm_states.argtypes = [vp, i32, vp]
+    L.aasr_topo_num_states.argtypes = [vp]
+    L.aasr_topo_state_num_transitions.argtypes = [vp, i32]
+    L.aasr_topo_state_transitions.argtypes = [vp, i32, vp, vp]
+    L.aasr_topo_max_offset.argtypes = [vp]
+    L.aasr_topo_validate.argtypes = [vp, vp]
+    L.aasr_topo_check_states.argtypes = [vp, i32]
+    L.aasr_align_default_options.argtypes = [vp]
+    L.aasr_align_default_options.restype = None
+    L.aasr_align_read_transcript.argtypes = [vp, cp, f, i32, i32, C.POINTER(C.POINTER(i32)), C.POINTER(i32)]
+    L.aasr_align_format_line.argtypes = [f, i32, i32, cp, cp, cp, i32]
+    L.aasr_align_batch_create.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, pvp]
+    L.aasr_align_batch_destroy.argtypes = [vp]
+    L.aasr_align_batch_destroy.restype = None
+    L.aasr_align_batch_rows.argtypes = [vp, i32]
+    L.aasr_align_batch_device_bytes.argtypes = [vp]
+    L.aasr_align_batch_device_bytes.restype = i64
+    L.aasr_align_batch_dev.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp]
+    L.aasr_align_batch_sync.argtypes = [vp, vp, C.POINTER(i32)]
+    L.aasr_align_batch_result.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(d), C.POINTER(i32), C.POINTER(i32)]
+    L.aasr_run_align_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
     L.aasr_set_device.argtypes = [C.c_int]
@@ -794,3 +824,146 @@ def recipe_last_timing(gmm: Gmm) -> dict:
 
 def set_host_share(processes: int) -> None:
     check(lib().aasr_set_host_share(int(processes)))
+
+
+# ---- forced alignment ---------------------------------------------------------------------------
+
+class AlignOptions(C.Structure):
+    """aasr_align_options: align's options (aku/align.cc:180-198) with the same defaults."""
+    _fields_ = [("swins", C.c_int32), ("beam", C.c_double), ("sbeam", C.c_int32), ("maxbeam", C.c_double),
+                ("overlap", C.c_float), ("no_force_end", C.c_int32), ("phoseg", C.c_int32), ("info", C.c_int32),
+                ("num_batches", C.c_int32), ("batch_index", C.c_int32), ("speakers", C.c_void_p)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "AlignOptions":
+        o = cls()
+        lib().aasr_align_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+ALIGN_ACTIVE, ALIGN_OK, ALIGN_GAVE_UP, ALIGN_ERROR = 0, 1, 2, 3
+
+
+class Topology:
+    """Owner of an aasr_topo handle: the HMMs of a .ph file with their transitions."""
+
+    def __init__(self, ph_path: str):
+        h = C.c_void_p()
+        check(lib().aasr_topo_create_from_ph(ph_path.encode(), C.byref(h)))
+        self._h = h.value
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_topo_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self) -> int:
+        return self._h
+
+    def num_hmms(self) -> int:
+        return lib().aasr_topo_num_hmms(self._h)
+
+    def hmm_index(self, label: str) -> int:
+        return lib().aasr_topo_hmm_index(self._h, label.encode())
+
+    def hmm_label(self, hmm: int) -> str:
+        return lib().aasr_topo_hmm_label(self._h, hmm).decode()
+
+    def hmm_states(self, hmm: int) -> list:
+        n = lib().aasr_topo_hmm_num_states(self._h, hmm)
+        out = np.zeros(max(n, 1), np.int32)
+        check(lib().aasr_topo_hmm_states(self._h, hmm, _ptr(out)))
+        return [int(x) for x in out[:n]]
+
+    def num_states(self) -> int:
+        return lib().aasr_topo_num_states(self._h)
+
+    def transitions(self, state: int) -> list:
+        """[(target_offset, prob)] of a state, in file order."""
+        n = lib().aasr_topo_state_num_transitions(self._h, state)
+        off = np.zeros(max(n, 1), np.int32)
+        prob = np.zeros(max(n, 1), np.float64)
+        check(lib().aasr_topo_state_transitions(self._h, state, _ptr(off), _ptr(prob)))
+        return [(int(off[k]), float(prob[k])) for k in range(n)]
+
+    def max_offset(self) -> int:
+        return lib().aasr_topo_max_offset(self._h)
+
+    def validate(self, gmm: "Gmm") -> None:
+        check(lib().aasr_topo_validate(self._h, gmm._h))
+
+    def check_states(self, num_states: int) -> None:
+        check(lib().aasr_topo_check_states(self._h, num_states))
+
+    def read_transcript(self, path: str, frame_rate: float = 125.0, first_frame: int = 0, last_frame: int = 0) -> list:
+        """HMM index per transcript line (-1: a line that adds none)."""
+        p = C.POINTER(C.c_int32)()
+        n = C.c_int32()
+        check(lib().aasr_align_read_transcript(self._h, path.encode(), frame_rate, first_frame, last_frame,
+                                               C.byref(p), C.byref(n)))
+        try:
+            return [int(p[k]) for k in range(n.value)]
+        finally:
+            lib().aasr_free(p)
+
+
+def align_format_line(frame_rate: float, start: int, end: int, label: str, comment: str) -> str:
+    buf = C.create_string_buffer(4096)
+    n = lib().aasr_align_format_line(frame_rate, start, end, label.encode(), comment.encode(), buf, len(buf))
+    if n < 0:
+        raise AasrError(AASR_ERR_INVALID, "line too long")
+    return buf.raw[:n].decode()
+
+
+def align_batch(gmm: "Gmm", topo: Topology, transcripts: list, scores, row0: list, start_frames: list,
+                end_frames: list, eof_frames: list, opts: Optional[AlignOptions] = None, windows: int = 1 << 20,
+                stream: int = 0) -> list:
+    """Batched forced alignment on the device.  transcripts[u]: HMM index per line; scores: a device
+    tensor of state log-likelihood rows (float32, or float64 for AASR_PREC_F64 rows), row0[u] the row of
+    utterance u's first frame.  Enqueues `windows` window steps per call until every utterance is done.
+    Returns per utterance a dict: positions (committed absolute transcription position per frame),
+    loglik, status, n_fail."""
+    L = lib()
+    opts = opts or AlignOptions.defaults()
+    n = len(transcripts)
+    line_off = np.zeros(n + 1, np.int32)
+    for u, t in enumerate(transcripts):
+        line_off[u + 1] = line_off[u] + len(t)
+    lines = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32) for t in transcripts] + [np.zeros(1, np.int32)]))
+    sf = np.ascontiguousarray(start_frames, np.int32)
+    ef = np.ascontiguousarray(end_frames, np.int32)
+    of = np.ascontiguousarray(eof_frames, np.int32)
+    r0 = np.ascontiguousarray(row0, np.int64)
+    b = C.c_void_p()
+    check(L.aasr_align_batch_create(topo.handle, C.byref(opts), n, _ptr(line_off), _ptr(lines), _ptr(sf), _ptr(ef),
+                                    _ptr(of), C.byref(b)))
+    try:
+        f64 = 1 if str(scores.dtype) == "torch.float64" else 0
+        pitch = scores.shape[1]
+        active = C.c_int32(n)
+        steps = 0
+        while active.value > 0:
+            check(L.aasr_align_batch_dev(gmm._h, b, _ptr(scores), pitch, f64, _ptr(r0), windows, stream))
+            check(L.aasr_align_batch_sync(b, stream, C.byref(active)))
+            steps += 1
+        out = []
+        for u in range(n):
+            rows = L.aasr_align_batch_rows(b, u)
+            pos = np.zeros(max(rows, 1), np.int32)
+            nc, st, nf = C.c_int32(), C.c_int32(), C.c_int32()
+            ll = C.c_double()
+            check(L.aasr_align_batch_result(b, u, _ptr(pos), C.byref(nc), C.byref(ll), C.byref(st), C.byref(nf)))
+            out.append({"positions": pos[:nc.value].copy(), "loglik": ll.value, "status": st.value,
+                        "n_fail": nf.value, "calls": steps})
+        return out
+    finally:
+        L.aasr_align_batch_destroy(b)

@@ -1,6 +1,7 @@
 // HmmSet.cc -- see HmmSet.hh.
 #include "HmmSet.hh"
 #include "str.hh"
+#include "../ph_parse.h"
 
 #include <cmath>
 #include <cstdio>
@@ -67,75 +68,18 @@ bool HmmSet::read_ph(const std::string &filename) {
   return true;  // legacy PHONE format is the only one the reference reads too
 }
 
-// aku/HmmSet.cc:208-329.  Per phone: "index states label", the two dummy states' numbers, one pdf
-// index per real state, then per source (dummies included) "source n" and n "target prob" pairs.
-// States are tied by their pdf: the first phone that mentions a pdf defines that state's
-// transitions (target 1 = the sink, stored as the offset that leaves the HMM), later mentions are
-// only checked.  States are then created in pdf order, transitions numbered state by state.
+// aku/HmmSet.cc:208-329 through the shared reader (csrc/ph_parse.h).  States are then created in
+// pdf order, transitions numbered state by state.
 void HmmSet::read_legacy_ph(std::ifstream &in) {
-  std::string label;
-  int phonemes = 0;
-  std::vector<std::vector<HmmTransition>> state_info;
-  in >> phonemes;
-  m_hmms.reserve(phonemes > 0 ? phonemes : 0);
-  for (int h = 0; h < phonemes; h++) {
-    int index = 0, states = 0;
-    in >> index >> states >> label;
-    if (!in) throw ReadError();
-    states -= 2;  // the dummy entry / exit states
-    Hmm &hmm = add_hmm(label, states);
-    int dummy, pdf;
-    std::vector<bool> load_transitions;
-    in >> dummy >> dummy;
-    for (int s = 0; s < states; s++) {
-      in >> pdf;
-      // (the reference indexes with whatever it read: a negative or garbage index is a ReadError here)
-      if (!in || pdf < 0 || pdf > (1 << 24)) throw ReadError();
-      if (pdf >= (int)state_info.size()) state_info.resize((size_t)pdf + 1);
-      hmm.state(s) = pdf;
-      load_transitions.push_back(state_info[(size_t)pdf].empty());
-    }
-    for (int s = -2; s < states; s++) {
-      int transitions = 0, source = 0;
-      in >> source >> transitions;
-      source -= 2;
-      if (source >= states)
-        throw str::fmt(128, "HmmSet::read_legacy_ph: Invalid source state number %i (only %i states)", source,
-                       states);
-      for (int t = 0; t < transitions; t++) {
-        int target;
-        double prob;
-        in >> target >> prob;
-        if (prob <= 0)
-          throw str::fmt(128,
-                         "HmmSet::read_legacy_ph: Phone %i (%s) transition from %i to %i has nonpositive "
-                         "probability %f.",
-                         index, label.c_str(), source, target, prob);
-        if (source >= 0 && load_transitions[(size_t)source]) {
-          if (target == 1) {
-            target = states - source;  // the sink
-          } else {
-            target -= 2;
-            if (target > states)
-              throw str::fmt(128, "HmmSet::read_legacy_ph: Invalid target state number %i (only %i states)",
-                             source, states);
-            target -= source;  // relative
-          }
-          state_info[(size_t)hmm.state(source)].push_back(HmmTransition(hmm.state(source), target, prob));
-        }
-      }
-      if (source >= 0 && !load_transitions[(size_t)source])
-        for (const HmmTransition &tr : state_info[(size_t)hmm.state(source)])
-          if (source + tr.target_offset > states)
-            throw str::fmt(128,
-                           "HmmSet::read_legacy_ph: Invalid target state number %i on existing state %i (only "
-                           "%i states)",
-                           source, hmm.state(source), states);
-    }
-  }
+  std::vector<std::vector<aasr::PhTransition>> state_info;
+  Hmm *hmm = nullptr;
+  aasr::parse_legacy_ph(
+      in,
+      [&](const std::string &label, int states) { hmm = &add_hmm(label, states); },
+      [&](int s, int pdf) { hmm->state(s) = pdf; }, [] { throw ReadError(); }, state_info);
   for (int s = 0; s < (int)state_info.size(); s++) {
     add_state(s);
-    for (const HmmTransition &tr : state_info[(size_t)s]) add_transition(s, tr.target_offset, tr.prob);
+    for (const aasr::PhTransition &tr : state_info[(size_t)s]) add_transition(s, tr.target_offset, tr.prob);
   }
 }
 

@@ -566,6 +566,105 @@ aasr_status aasr_audio_read(const aasr_feat *feat, const char *path, int16_t **p
 aasr_status aasr_audio_decode(const aasr_feat *feat, const void *data, int64_t n_bytes, int16_t **pcm,
                               int64_t *n_samples, int32_t *sample_rate);
 
+/* ---------------------------------------------------------------------------
+ * Forced alignment: aku/align.cc with aku/Viterbi.cc and aku/Lattice.cc, the Viterbi search on the
+ * device (csrc/align_viterbi.hip, one wave per utterance, many utterances per launch).
+ *
+ * Topology: the HMMs of a legacy PHONE .ph file with their transitions (aku/HmmSet.cc:183-329; the
+ * same reader as the aku::HmmSet adapter).  States are tied by pdf index; a transition to the
+ * dummy final state is stored as the offset that leaves the HMM (+1 past its last state).  The
+ * handle is separate from aasr_gmm: scoring and the model cache do not see it. */
+typedef struct aasr_topo aasr_topo;
+aasr_status aasr_topo_create_from_ph(const char *ph_path, aasr_topo **out);
+void aasr_topo_destroy(aasr_topo *h);
+int32_t aasr_topo_num_hmms(const aasr_topo *h);
+/* HmmSet::hmm_index: -1 for an unknown label */
+int32_t aasr_topo_hmm_index(const aasr_topo *h, const char *label);
+const char *aasr_topo_hmm_label(const aasr_topo *h, int32_t hmm);
+int32_t aasr_topo_hmm_num_states(const aasr_topo *h, int32_t hmm);
+/* the HMM's state (= pdf) indices, hmm_num_states entries */
+aasr_status aasr_topo_hmm_states(const aasr_topo *h, int32_t hmm, int32_t *states);
+/* number of states the file mentions (largest pdf index + 1) */
+int32_t aasr_topo_num_states(const aasr_topo *h);
+int32_t aasr_topo_state_num_transitions(const aasr_topo *h, int32_t state);
+/* the state's transitions in file order: target offset (relative position) and probability */
+aasr_status aasr_topo_state_transitions(const aasr_topo *h, int32_t state, int32_t *target_offset, double *prob);
+int32_t aasr_topo_max_offset(const aasr_topo *h);
+/* every state index below aasr_gmm_num_states and every target offset <= 255 (the search's
+ * back-pointer encoding); AASR_ERR_INVALID naming the HMM otherwise */
+aasr_status aasr_topo_validate(const aasr_topo *h, const aasr_gmm *gmm);
+/* the same checks against a state count (host only: what aasr_topo_validate runs with
+ * aasr_gmm_num_states(gmm)) */
+aasr_status aasr_topo_check_states(const aasr_topo *h, int32_t num_states);
+
+typedef struct aasr_align_options {
+  int32_t swins;         /* --swins: window size in frames and positions (1000)        */
+  double beam;           /* --beam: log-probability beam (100)                         */
+  int32_t sbeam;         /* --sbeam: state beam (100)                                  */
+  double maxbeam;        /* --maxbeam: retries double the beams up to this (1600)      */
+  float overlap;         /* --overlap: window overlap (0.4)                            */
+  int32_t no_force_end;  /* --no-force-end                                             */
+  int32_t phoseg;        /* --phoseg: phone segmentation instead of states             */
+  int32_t info;          /* -i                                                         */
+  int32_t num_batches;   /* -B                                                         */
+  int32_t batch_index;   /* -I                                                         */
+  struct aasr_spkc *speakers; /* -S: speaker configuration or NULL                     */
+} aasr_align_options;
+void aasr_align_default_options(aasr_align_options *opt);
+
+/* A transcript as aku/PhnReader.cc:294-400 reads it for align: "label [comment]" lines or
+ * "start end label[.state] [comment]" lines (sample numbers at 16 kHz), empty lines skipped, the
+ * frame limits of a recipe line applied (first_frame / last_frame as PhnReader::set_frame_limits,
+ * both 0: none).  Per line, *line_hmms receives the HMM index the line adds, or -1 for a line whose
+ * state field is > 0 (it adds none).  An unknown label is AASR_ERR_INVALID naming label and file.
+ * *line_hmms is malloc'ed (aasr_free). */
+aasr_status aasr_align_read_transcript(const aasr_topo *topo, const char *path, float frame_rate,
+                                       int32_t first_frame, int32_t last_frame, int32_t **line_hmms,
+                                       int32_t *n_lines);
+/* One line of an alignment file (align.cc:print_line): "start*m end*m label comment\n" with
+ * m = (int)(16000 / frame_rate); nothing for start < 0.  Returns the length written (< cap). */
+int32_t aasr_align_format_line(float frame_rate, int32_t start, int32_t end, const char *label,
+                               const char *comment, char *buf, int32_t cap);
+
+/* Batched search.  A batch holds n_utt utterances: their transcripts (lines [line_off[u],
+ * line_off[u+1]) of line_hmms), first frame, end frame ((int)(end_time * frame_rate), 0: to the end of the
+ * audio) and eof frame (aasr_feat_eof_frame).  It carries each utterance's lattice on the device
+ * between calls. */
+typedef struct aasr_align_batch aasr_align_batch;
+aasr_status aasr_align_batch_create(const aasr_topo *topo, const aasr_align_options *opt, int32_t n_utt,
+                                    const int32_t *line_off, const int32_t *line_hmms,
+                                    const int32_t *start_frame, const int32_t *end_frame,
+                                    const int32_t *eof_frame, aasr_align_batch **out);
+void aasr_align_batch_destroy(aasr_align_batch *b);
+/* score rows each utterance reads: frames start_frame .. min(eof, end) - 1, at least one */
+int32_t aasr_align_batch_rows(const aasr_align_batch *b, int32_t u);
+/* device bytes the batch holds (lattice rings, transcripts, outputs) */
+int64_t aasr_align_batch_device_bytes(const aasr_align_batch *b);
+/* Enqueues `windows` window steps (>= 1) of every active utterance on `stream`, no host wait.
+ * d_state_loglik: state log-likelihood rows on the device (float, or double when f64 -- the
+ * AASR_PREC_F64 rows), `pitch` elements apart; row0[u] (host) is the row of utterance u's first
+ * frame.  gmm is the model the rows were scored with (its state count bounds the topology). */
+aasr_status aasr_align_batch_dev(const aasr_gmm *gmm, aasr_align_batch *b, const void *d_state_loglik,
+                                 int64_t pitch, int32_t f64, const int64_t *row0, int32_t windows,
+                                 void *stream);
+/* Waits for `stream` and fetches the per-utterance results; *n_active: utterances still running. */
+aasr_status aasr_align_batch_sync(aasr_align_batch *b, void *stream, int32_t *n_active);
+enum { AASR_ALIGN_ACTIVE = 0, AASR_ALIGN_OK = 1, AASR_ALIGN_GAVE_UP = 2, AASR_ALIGN_ERROR = 3 };
+/* Results after a sync: the committed absolute transcription position of each frame from the first
+ * (n_committed of them; positions may be NULL), the log-likelihood (Viterbi::best_path_log_prob),
+ * the status, how many times the forced end was missed (each miss doubled beam and state beam;
+ * status OK with n_fail > 0: retried, GAVE_UP: beyond maxbeam). */
+aasr_status aasr_align_batch_result(const aasr_align_batch *b, int32_t u, int32_t *positions,
+                                    int32_t *n_committed, double *loglik, int32_t *status,
+                                    int32_t *n_fail);
+
+/* align main loop (aku/align.cc:171-346) over one recipe slice: audio, transcripts, features and
+ * scores per utterance (speaker configuration applied per utterance), the search for many
+ * utterances at once on the device, .phn files and the -i diagnostics on stderr. */
+aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
+                                  const char *recipe_path, const aasr_align_options *opt,
+                                  aasr_run_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
