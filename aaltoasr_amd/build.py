@@ -93,6 +93,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(bindir, exist_ok=True)
     for name, src in (("phone_probs", "aku/main_phone_probs.cc"),
                       ("align", "aku/main_align.cc"),
+                      ("stats", "aku/main_stats.cc"),
                       ("aku_adapter_check", "aku/main_adapter_check.cc"),
                       ("feacat", "aku/main_feacat.cc"),
                       ("plugin_check", "aku/main_plugin_check.cc"),
@@ -102,7 +103,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if force or not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(srcp), os.path.getmtime(LIB)):
             cmd = [HIPCC, "-O2", "-std=c++17", srcp, "-o", exe, "-L", LIBDIR, "-laasr",
                    "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib"]
-            if name == "align":   # train.pl copies its align binary into a work directory before it runs it
+            if name in ("align", "stats"):   # train.pl copies its align and stats binaries into a work directory before it runs it
                 cmd.append("-Wl,-rpath," + os.path.abspath(LIBDIR))
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:

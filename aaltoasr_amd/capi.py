@@ -123,6 +123,28 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_align_batch_sync.argtypes = [vp, vp, C.POINTER(i32)]
     L.aasr_align_batch_result.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(d), C.POINTER(i32), C.POINTER(i32)]
     L.aasr_run_align_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
+    # ML statistics
+    L.aasr_feat_run_f64_dev.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+    L.aasr_stats_read_segmentation.argtypes = [vp, cp, f, i32, i32, i32, i32, C.POINTER(i32),
+                                               C.POINTER(C.POINTER(i32)), C.POINTER(C.POINTER(i32)), C.POINTER(i32)]
+    L.aasr_stats_write_gks.argtypes = [cp, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.aasr_stats_write_mcs.argtypes = [cp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.aasr_stats_write_phs.argtypes = [cp, i32, vp, vp, vp]
+    L.aasr_stats_write_lls.argtypes = [cp, d, i64]
+    L.aasr_stats_create.argtypes = [vp, vp, pvp]
+    L.aasr_stats_destroy.argtypes = [vp]
+    L.aasr_stats_destroy.restype = None
+    L.aasr_stats_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.aasr_stats_add_transitions.argtypes = [vp, vp, i64]
+    L.aasr_stats_fetch.argtypes = [vp, vp]
+    L.aasr_stats_gaussians.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.aasr_stats_mixtures.argtypes = [vp, vp, vp, vp]
+    L.aasr_stats_num_transitions.argtypes = [vp]
+    L.aasr_stats_transitions.argtypes = [vp, vp, vp, vp]
+    L.aasr_stats_write.argtypes = [vp, cp]
+    L.aasr_stats_default_options.argtypes = [vp]
+    L.aasr_stats_default_options.restype = None
+    L.aasr_run_stats_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
     L.aasr_set_device.argtypes = [C.c_int]
@@ -967,3 +989,132 @@ def align_batch(gmm: "Gmm", topo: Topology, transcripts: list, scores, row0: lis
         return out
     finally:
         L.aasr_align_batch_destroy(b)
+
+
+# ---- ML statistics ------------------------------------------------------------------------------
+
+class StatsOptions(C.Structure):
+    """aasr_stats_options: stats' options (aku/stats.cc:321-356) for --ml over .phn files."""
+    _fields_ = [("transitions", C.c_int32), ("ophn", C.c_int32), ("no_train", C.c_int32), ("uttadap", C.c_int32),
+                ("info", C.c_int32), ("num_batches", C.c_int32), ("batch_index", C.c_int32),
+                ("speakers", C.c_void_p), ("out", C.c_char_p)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "StatsOptions":
+        o = cls()
+        lib().aasr_stats_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def stats_read_segmentation(topo: Topology, path: str, frame_rate: float = 125.0, first_frame: int = 0,
+                            last_frame: int = 0, eof_frame: int = -1, transitions: bool = True):
+    """PhnReader::next_frame as stats drives it (host only).  Returns (start_frame, pdf per frame, global
+    transition index per frame or -1), or None for a file without lines."""
+    L = lib()
+    sf, n = C.c_int32(), C.c_int32()
+    pp, tp = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+    check(L.aasr_stats_read_segmentation(topo.handle, path.encode(), frame_rate, first_frame, last_frame, eof_frame,
+                                         1 if transitions else 0, C.byref(sf), C.byref(pp), C.byref(tp), C.byref(n)))
+    try:
+        if n.value < 0:
+            return None
+        pdf = np.array([pp[k] for k in range(n.value)], np.int32)
+        tr = np.array([tp[k] for k in range(n.value)], np.int32)
+        return sf.value, pdf, tr
+    finally:
+        L.aasr_free(pp)
+        L.aasr_free(tp)
+
+
+def stats_write_gks(path: str, feacount, gamma, aux_gamma, sum_x, sum_xx, mode: int = 1) -> None:
+    fc = np.ascontiguousarray(feacount, np.int64)
+    g, a = np.ascontiguousarray(gamma, np.float64), np.ascontiguousarray(aux_gamma, np.float64)
+    sx, sxx = np.ascontiguousarray(sum_x, np.float64), np.ascontiguousarray(sum_xx, np.float64)
+    G, D = sx.shape
+    check(lib().aasr_stats_write_gks(path.encode(), G, D, mode, _ptr(fc), _ptr(g), _ptr(a), _ptr(sx), _ptr(sxx)))
+
+
+def stats_write_mcs(path: str, mix_off, mix_idx, count, gamma, aux_gamma, mixture_ll, mode: int = 1) -> None:
+    off, idx = np.ascontiguousarray(mix_off, np.int32), np.ascontiguousarray(mix_idx, np.int32)
+    cnt, g = np.ascontiguousarray(count, np.int64), np.ascontiguousarray(gamma, np.float64)
+    a, mll = np.ascontiguousarray(aux_gamma, np.float64), np.ascontiguousarray(mixture_ll, np.float64)
+    check(lib().aasr_stats_write_mcs(path.encode(), len(off) - 1, mode, _ptr(off), _ptr(idx), _ptr(cnt), _ptr(g),
+                                     _ptr(a), _ptr(mll)))
+
+
+def stats_write_phs(path: str, source, target_offset, count) -> None:
+    src, off = np.ascontiguousarray(source, np.int32), np.ascontiguousarray(target_offset, np.int32)
+    cnt = np.ascontiguousarray(count, np.float64)
+    check(lib().aasr_stats_write_phs(path.encode(), len(src), _ptr(src), _ptr(off), _ptr(cnt)))
+
+
+def stats_write_lls(path: str, loglik: float, frames: int) -> None:
+    check(lib().aasr_stats_write_lls(path.encode(), loglik, frames))
+
+
+class Stats:
+    """Owner of an aasr_stats handle: ML statistics of one model and topology, accumulated on the device."""
+
+    def __init__(self, gmm: "Gmm", topo: Topology, n_components: int = 0):
+        """n_components: the model's mixture components in all (for the per-component gammas of fetch)"""
+        h = C.c_void_p()
+        check(lib().aasr_stats_create(gmm._h, topo.handle, C.byref(h)))
+        self._h = h.value
+        self.G, self.D, self.S, self.K = gmm.num_gaussians, gmm.dim, gmm.num_states, n_components
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_stats_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def accumulate_dev(self, d_frames, pdf, d_frame_ll=None, stream=None) -> None:
+        """d_frames: a float64 device tensor [n x dim]; pdf: host int32 per frame (-1: skip)."""
+        p = np.ascontiguousarray(pdf, np.int32)
+        check(lib().aasr_stats_accumulate_dev(self._h, _ptr(d_frames), len(p), _ptr(p), _ptr(d_frame_ll),
+                                              _stream_handle(stream)))
+
+    def add_transitions(self, transition) -> None:
+        t = np.ascontiguousarray(transition, np.int32)
+        check(lib().aasr_stats_add_transitions(self._h, _ptr(t), len(t)))
+
+    def fetch(self, stream=None) -> dict:
+        """Waits for the device and returns every sum: per pool Gaussian feacount, gamma, aux_gamma,
+        sum_x, sum_xx; per pdf count and mixture_ll; per mixture component (record order) mix_gamma."""
+        L = lib()
+        check(L.aasr_stats_fetch(self._h, _stream_handle(stream)))
+        G, D, S = self.G, self.D, self.S
+        fc = np.zeros(G, np.int64)
+        g, a = np.zeros(G), np.zeros(G)
+        sx, sxx = np.zeros((G, D)), np.zeros((G, D))
+        check(L.aasr_stats_gaussians(self._h, _ptr(fc), _ptr(g), _ptr(a), _ptr(sx), _ptr(sxx)))
+        cnt, mll, mg = np.zeros(S, np.int64), np.zeros(S), np.zeros(max(1, self.K))
+        check(L.aasr_stats_mixtures(self._h, _ptr(cnt), _ptr(mg), _ptr(mll)))
+        return {"feacount": fc, "gamma": g, "aux_gamma": a, "sum_x": sx, "sum_xx": sxx, "count": cnt,
+                "mixture_ll": mll, "mix_gamma": mg[:self.K]}
+
+    def transitions(self):
+        n = lib().aasr_stats_num_transitions(self._h)
+        src, off, cnt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1))
+        check(lib().aasr_stats_transitions(self._h, _ptr(src), _ptr(off), _ptr(cnt)))
+        return src[:n], off[:n], cnt[:n]
+
+    def write(self, base: str) -> None:
+        check(lib().aasr_stats_write(self._h, base.encode()))
+
+
+def run_stats_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str, out: str,
+                     opts: Optional[StatsOptions] = None) -> dict:
+    opts = opts or StatsOptions.defaults()
+    ob = out.encode()
+    opts.out = ob
+    st = RunStats()
+    check(lib().aasr_run_stats_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}

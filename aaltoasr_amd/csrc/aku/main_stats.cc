@@ -1,0 +1,202 @@
+// stats -- maximum-likelihood statistics with the reference tool's options (aku/stats.cc:321-356) on
+// the engine: features per utterance on the device, .phn segmentations on the host, the accumulation
+// for many utterances per launch (aasr_run_stats_recipe), dumps as HmmSet::dump_statistics writes them.
+//
+//   stats (-b BASE | -g GK -m MC -p PH) -c CFG -r RECIPE -o OUT --ml [-t] [-O] [-S SPKC [-U]] [-n]
+//         [-B n -I k] [-i level] [-F f -W f -A f]
+//
+// Only --ml over .phn files is built: -H (hmmnets), --mmi / --mpe / --grad, --mllt, -P, --savelat,
+// -a and --nseggk / --nsegmc are refused before the device is opened, and so are full-covariance or
+// subspace pools and speaker files with model transforms.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../../include/aasr.h"
+#include "conf.hh"
+
+static void die(const std::string &msg) {
+  fprintf(stderr, "exception: %s\n", msg.c_str());
+  exit(1);
+}
+
+// PDFPool::read_gk's header and per-Gaussian tags, without the values: diagonal pools only
+static void check_pool(const std::string &gk) {
+  std::ifstream in(gk);
+  if (!in) die("could not open " + gk);
+  int size = 0, dim = 0;
+  std::string kind;
+  in >> size >> dim >> kind;
+  if (!in) die("could not read the header of " + gk);
+  if (kind == "diagonal_cov") return;
+  if (kind != "variable") die("stats: only diagonal Gaussians are supported (" + gk + " is a " + kind + " pool)");
+  std::string tag, value;
+  for (int g = 0; g < size; g++) {
+    if (!(in >> tag)) die("could not read " + gk);
+    if (tag != "diag")
+      die("stats: only diagonal Gaussians are supported (" + gk + " holds '" + tag + "' Gaussians)");
+    for (int i = 0; i < 2 * dim; i++) in >> value;
+  }
+}
+
+// a speaker file's "model <module>" entries set model-side transforms (ModelTransformer)
+static void check_speakers(const std::string &path) {
+  std::ifstream in(path);
+  if (!in) die("could not open " + path);
+  std::string line;
+  while (std::getline(in, line)) {
+    std::istringstream ls(line);
+    std::string first;
+    if (ls >> first && first == "model")
+      die("stats: speaker files with model transforms (" + line + ") are not supported");
+  }
+}
+
+// recipe lines with start-line / end-line, refused as align refuses them
+static void check_recipe(const std::string &path, int num_batches, int batch_index) {
+  std::ifstream in(path);
+  if (!in) die("could not open " + path);
+  std::stringstream ss;
+  ss << in.rdbuf();
+  char *table = nullptr;
+  int64_t len = 0;
+  if (aasr_recipe_read_all(ss.str().c_str(), num_batches, batch_index, 0, &table, &len) != AASR_OK)
+    die(aasr_last_error());
+  const std::string t(table, (size_t)len);
+  aasr_free(table);
+  std::istringstream lines(t);
+  std::string line;
+  while (std::getline(lines, line)) {
+    std::vector<std::string> fl;
+    size_t a = 0;
+    for (;;) {
+      const size_t b = line.find('\x1f', a);
+      fl.push_back(line.substr(a, b == std::string::npos ? std::string::npos : b - a));
+      if (b == std::string::npos) break;
+      a = b + 1;
+    }
+    if (fl.size() == 13 && (atoi(fl[9].c_str()) > 0 || atoi(fl[10].c_str()) > 0))
+      die("stats: recipe line limits (start-line / end-line) are not supported");
+  }
+}
+
+int main(int argc, char *argv[]) {
+  aku::conf::Config config;
+  config("usage: stats [OPTION...]\n")
+    ('h', "help", "", "", "display help")
+    ('b', "base=BASENAME", "arg", "", "base filename for model files")
+    ('g', "gk=FILE", "arg", "", "Mixture base distributions")
+    ('m', "mc=FILE", "arg", "", "Mixture coefficients for the states")
+    ('p', "ph=FILE", "arg", "", "HMM definitions")
+    ('\0', "nsegmc=FILE", "arg", "", "mc-file for segmentating the numerator")
+    ('\0', "nseggk=FILE", "arg", "", "gk-file for segmentating the numerator")
+    ('c', "config=FILE", "arg must", "", "feature configuration")
+    ('r', "recipe=FILE", "arg must", "", "recipe file")
+    ('O', "ophn", "", "", "use output phns for training")
+    ('H', "hmmnet", "", "", "use HMM networks for training")
+    ('o', "out=BASENAME", "arg must", "", "base filename for output statistics")
+    ('t', "transitions", "", "", "collect also state transition statistics")
+    ('F', "fw-beam=FLOAT", "arg", "0", "Forward beam (for HMM networks)")
+    ('W', "bw-beam=FLOAT", "arg", "0", "Backward beam (for HMM networks)")
+    ('A', "ac-scale=FLOAT", "arg", "1", "Acoustic scaling (for HMM networks)")
+    ('\0', "num-mult=FLOAT", "arg", "1", "Loglikelihood multiplier for the numerator")
+    ('M', "segmode=MODE", "arg", "bw", "Segmentation mode: bw/vit/mpv")
+    ('\0', "numseg=MODE", "arg", "", "Numerator segmentation mode")
+    ('\0', "ml", "", "", "Collect statistics for ML")
+    ('\0', "mmi", "", "", "Collect statistics for MMI")
+    ('\0', "mpe", "", "", "Collect statistics for MPE/MWE/MPFE")
+    ('\0', "grad", "", "", "Prepare gradient based statistics (with --mpe)")
+    ('\0', "mllt", "", "", "maximum likelihood linear transformation (for --ml)")
+    ('\0', "errmode=MODE", "arg", "", "For --mpe. Modes: mwe/mpe/mpfe/mpfe-cps/mpfe-pdf/snfe")
+    ('\0', "nosil=SIL", "arg", "", "Ignore silence arcs (labeled SIL) in MPE scoring")
+    ('S', "speakers=FILE", "arg", "", "speaker configuration file")
+    ('U', "uttadap", "", "", "Enable utterance adaptation")
+    ('n', "no-train", "", "", "Only collect summary statistics")
+    ('P', "precomplat", "", "", "Use precomputed segmented lattices (with rescoring)")
+    ('\0', "savelat", "", "", "Don't train but only save segmented lattices")
+    ('a', "alignment", "", "", "save output alignments (only with ML training)")
+    ('B', "batch=INT", "arg", "0", "number of batch processes with the same recipe")
+    ('I', "bindex=INT", "arg", "0", "batch process index")
+    ('i', "info=INT", "arg", "0", "info level")
+    ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)");
+  config.default_parse(argc, argv);
+
+  // what this build does not do, refused before anything is read
+  const char *refused[][2] = {{"hmmnet", "-H (HMM network Baum-Welch)"},
+                              {"mmi", "--mmi (discriminative statistics)"},
+                              {"mpe", "--mpe (discriminative statistics)"},
+                              {"grad", "--grad (discriminative statistics)"},
+                              {"mllt", "--mllt"},
+                              {"precomplat", "-P (precomputed lattices)"},
+                              {"savelat", "--savelat"},
+                              {"alignment", "-a (alignment output)"},
+                              {"nseggk", "--nseggk (numerator segmentation model)"},
+                              {"nsegmc", "--nsegmc (numerator segmentation model)"}};
+  for (const auto &r : refused)
+    if (config[r[0]].specified) die(std::string("stats: ") + r[1] + " is not supported; only --ml over .phn files is");
+
+  std::string gk, mc, ph;
+  if (config["base"].specified) {
+    const std::string base = config["base"].get_str();
+    gk = base + ".gk";
+    mc = base + ".mc";
+    ph = base + ".ph";
+  } else if (config["gk"].specified && config["mc"].specified && config["ph"].specified) {
+    gk = config["gk"].get_str();
+    mc = config["mc"].get_str();
+    ph = config["ph"].get_str();
+  } else {
+    die("Must give either --base or all --gk, --mc and --ph");
+  }
+  if (config["batch"].specified ^ config["bindex"].specified) die("Must give both --batch and --bindex");
+  if (!config["ml"].specified) die("At least one mode (--ml, --mmi, --mpe) must be given!");
+  check_pool(gk);
+  if (config["speakers"].specified) check_speakers(config["speakers"].get_str());
+  check_recipe(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int());
+
+  const int device = config["device"].get_int();
+  if (device >= 0 && aasr_set_device(device) != AASR_OK) die(aasr_last_error());
+
+  const std::string cfg = config["config"].get_str();
+  std::ifstream cin_(cfg);
+  if (!cin_) die("could not open " + cfg);
+  std::stringstream ss;
+  ss << cin_.rdbuf();
+  aasr_feat *feat = nullptr;
+  aasr_gmm *gmm = nullptr;
+  aasr_topo *topo = nullptr;
+  if (aasr_feat_create(ss.str().c_str(), &feat) != AASR_OK) die(aasr_last_error());
+  if (aasr_gmm_create_from_files(gk.c_str(), mc.c_str(), ph.c_str(), &gmm) != AASR_OK) die(aasr_last_error());
+  if (aasr_topo_create_from_ph(ph.c_str(), &topo) != AASR_OK) die(aasr_last_error());
+
+  aasr_stats_options opt;
+  aasr_stats_default_options(&opt);
+  opt.transitions = config["transitions"].specified;
+  opt.ophn = config["ophn"].specified;
+  opt.no_train = config["no-train"].specified;
+  opt.uttadap = config["uttadap"].specified;
+  opt.info = config["info"].get_int();
+  opt.num_batches = config["batch"].get_int();
+  opt.batch_index = config["bindex"].get_int();
+  const std::string out = config["out"].get_str();
+  opt.out = out.c_str();
+  aasr_spkc *spk = nullptr;
+  if (config["speakers"].specified) {
+    if (aasr_spkc_create(feat, gmm, &spk) != AASR_OK) die(aasr_last_error());
+    if (aasr_spkc_read_file(spk, config["speakers"].get_str().c_str()) != AASR_OK) die(aasr_last_error());
+  }
+  opt.speakers = spk;
+  aasr_run_stats st;
+  memset(&st, 0, sizeof st);
+  if (aasr_run_stats_recipe(feat, gmm, topo, config["recipe"].get_str().c_str(), &opt, &st) != AASR_OK)
+    die(aasr_last_error());
+  aasr_spkc_destroy(spk);
+  aasr_topo_destroy(topo);
+  aasr_gmm_destroy(gmm);
+  aasr_feat_destroy(feat);
+  return 0;
+}

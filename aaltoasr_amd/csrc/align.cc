@@ -19,6 +19,7 @@
 #include "aku/str.hh"
 #include "common.h"
 #include "ph_parse.h"
+#include "phn_line.h"
 
 struct aasr_topo {
   struct Hmm {
@@ -138,19 +139,7 @@ void aasr_align_default_options(aasr_align_options *o) {
 
 namespace aasr {
 
-// Transcript lines as align reads them (the rules of aku/PhnReader.cc:294-400, without state-number
-// labels or relative sample numbers):
-//   "label[,more labels] [comment]"                      -- no times
-//   "start end label[.state][,more labels] [comment]"    -- sample numbers at 16 kHz, when the line
-//                                                           starts with a digit
-// Fields end at one blank or tab, the blanks after it are skipped, and the last field allowed takes
-// the rest of the line.  Only the first label names the HMM.  The state number is what follows the
-// first '.', and the label loses that '.' and the one character after it.
-struct PhnLine {
-  int start = -1, end = -1, state = -1;
-  std::string label, comment;
-};
-
+// the fields of a .phn line (phn_line.h)
 static std::vector<std::string> phn_fields(const std::string &text, size_t max_fields) {
   std::vector<std::string> out;
   size_t at = 0;
@@ -179,8 +168,7 @@ static bool phn_next_text(FILE *f, std::string *text) {
 // One transcript entry; false at the end of the file or at a timed line that starts at or after
 // last_frame (> 0).  Times are clipped to [first_frame, last_frame] as PhnReader::set_frame_limits
 // leaves them.
-static bool next_phn_line(FILE *f, float samples_per_frame, int first_frame, int last_frame, int *line_no,
-                          PhnLine *phn) {
+bool next_phn_line(FILE *f, float samples_per_frame, int first_frame, int last_frame, int *line_no, PhnLine *phn) {
   std::string text;
   if (!phn_next_text(f, &text)) {
     if (ferror(f)) raise(AASR_ERR_IO, "transcript: read error on line %d", *line_no);
@@ -220,6 +208,20 @@ static bool next_phn_line(FILE *f, float samples_per_frame, int first_frame, int
   return true;
 }
 
+void phn_skip_to_first_frame(FILE *f, float samples_per_frame, int first_frame, int last_frame, int *line_no) {
+  PhnLine phn;
+  long curpos = ftell(f), oldpos = curpos;
+  while (next_phn_line(f, samples_per_frame, first_frame, last_frame, line_no, &phn)) {
+    oldpos = curpos;
+    curpos = ftell(f);
+    if (phn.end < 0 || phn.end > first_frame) {
+      fseek(f, oldpos, SEEK_SET);
+      (*line_no)--;
+      return;
+    }
+  }
+}
+
 struct Transcript {
   std::vector<int32_t> line_hmms;      // HMM per line, -1: the line adds none
   std::vector<std::string> comments;   // per line
@@ -233,19 +235,7 @@ static Transcript read_transcript(const aasr_topo *topo, const char *path, float
   const float spf = 16000 / frame_rate;
   int line_no = 0;
   PhnLine phn;
-  // PhnReader::set_frame_limits: skip the lines that end before the first frame
-  if (first_frame > 0 || last_frame > 0) {
-    long curpos = ftell(f), oldpos = curpos;
-    while (next_phn_line(f, spf, first_frame, last_frame, &line_no, &phn)) {
-      oldpos = curpos;
-      curpos = ftell(f);
-      if (phn.end < 0 || phn.end > first_frame) {
-        fseek(f, oldpos, SEEK_SET);
-        line_no--;
-        break;
-      }
-    }
-  }
+  if (first_frame > 0 || last_frame > 0) phn_skip_to_first_frame(f, spf, first_frame, last_frame, &line_no);
   Transcript t;
   while (next_phn_line(f, spf, first_frame, last_frame, &line_no, &phn)) {
     if (phn.state == -1 || phn.state == 0) {

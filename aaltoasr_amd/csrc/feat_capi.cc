@@ -165,6 +165,19 @@ aasr_status aasr_feat_run_dev(aasr_feat *h, const int16_t *d_pcm, int64_t n_samp
   });
 }
 
+aasr_status aasr_feat_run_f64_dev(aasr_feat *h, const int16_t *d_pcm, int64_t n_samples, int32_t first_frame,
+                                  int32_t n_frames, double *d_out, void *stream) {
+  return guarded([&] {
+    if (!h || !d_pcm || (n_frames > 0 && !d_out))
+      raise(AASR_ERR_INVALID, "aasr_feat_run_f64_dev: null argument");
+    if (h->mods[0].type == MOD_PRE && (n_samples & 1))
+      raise(AASR_ERR_INVALID, "aasr_feat_run_f64_dev: a pre module takes float input (2 units per value)");
+    if (n_frames <= 0) return;
+    UttBatch b = single(n_samples, first_frame, n_frames);
+    feat_run_batch(h, d_pcm, b, (int)h->mods.size() - 1, nullptr, d_out, (hipStream_t)stream);
+  });
+}
+
 aasr_status aasr_feat_run_batch_dev(aasr_feat *h, const int16_t *d_pcm, const int64_t *pcm_off,
                                     const int64_t *frame_off, int32_t n_utts, float *d_out,
                                     void *stream) {

@@ -129,6 +129,13 @@ aasr_status aasr_feat_run_f64(aasr_feat *h, const int16_t *pcm,
                               int32_t n_frames, const char *module_name,
                               double *out);
 
+/* The double-precision frames of aasr_feat_run_f64 written to device memory: d_pcm holds the
+ * utterance's complete input on the device (int16 units, as aasr_feat_run_dev), d_out receives
+ * [n_frames x dim] doubles.  Enqueued on `stream`, no host wait. */
+aasr_status aasr_feat_run_f64_dev(aasr_feat *h, const int16_t *d_pcm, int64_t n_samples,
+                                  int32_t first_frame, int32_t n_frames, double *d_out,
+                                  void *stream);
+
 /* Batched form for a recipe slice: n_utts utterances concatenated in d_pcm;
  * utterance u occupies samples [pcm_off[u], pcm_off[u+1]) and emits frames
  * 0 .. last_frame(u) into d_out rows [frame_off[u], frame_off[u+1]).
@@ -663,6 +670,82 @@ aasr_status aasr_align_batch_result(const aasr_align_batch *b, int32_t u, int32_
  * utterances at once on the device, .phn files and the -i diagnostics on stderr. */
 aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
                                   const char *recipe_path, const aasr_align_options *opt,
+                                  aasr_run_stats *stats);
+
+/* ---------------------------------------------------------------------------
+ * Maximum-likelihood statistics: aku/stats.cc with --ml over state-segmented .phn files (PhnReader),
+ * accumulated on the device (csrc/stats_accum.hip) and dumped as HmmSet::dump_statistics writes
+ * them (.gks, .mcs, .phs) with the .lls summary, for the reference's estimate / combine_stats.
+ * Diagonal pools without model-side transforms only; -H (hmmnets), MMI / MPE and MLLT are not built.
+ *
+ * Segmentation: PhnReader::next_frame (aku/PhnReader.cc:138-292) as stats configures it -- the emission
+ * pdf of every frame from the first line's start on, and with `transitions` the global index of the
+ * transition taken (HmmSet::read_ph order, -1 on the last frame).  first_frame / last_frame: the recipe's
+ * frame limits (both 0: none); the frames stop at eof_frame (aasr_feat_eof_frame; < 0: no limit).
+ * *n_frames = -1 when the file holds no line ("Could not initialize the utterance segmentation").
+ * *pdf and *transition are malloc'ed (aasr_free).  Host only. */
+aasr_status aasr_stats_read_segmentation(const aasr_topo *topo, const char *path, float frame_rate,
+                                         int32_t first_frame, int32_t last_frame, int32_t eof_frame,
+                                         int32_t transitions, int32_t *start_frame, int32_t **pdf,
+                                         int32_t **transition, int32_t *n_frames);
+
+/* Dump writers over plain host arrays (HmmSet.cc:546-625, Distributions.cc:157-172, 305-315,
+ * 2192-2208).  A Gaussian is written as accumulated when feacount > 0, a mixture when count (its
+ * frames with a positive total likelihood) > 0, a transition when its count > 0.  sum_x / sum_xx are
+ * [pool_size x dim] and go out as float; mode is the statistics mode (1: ML).  Host only. */
+aasr_status aasr_stats_write_gks(const char *path, int32_t pool_size, int32_t dim, int32_t mode,
+                                 const int64_t *feacount, const double *gamma, const double *aux_gamma,
+                                 const double *sum_x, const double *sum_xx);
+aasr_status aasr_stats_write_mcs(const char *path, int32_t num_pdfs, int32_t mode, const int32_t *mix_off,
+                                 const int32_t *mix_idx, const int64_t *count, const double *gamma,
+                                 const double *aux_gamma, const double *mixture_ll);
+aasr_status aasr_stats_write_phs(const char *path, int32_t num_transitions, const int32_t *source,
+                                 const int32_t *target_offset, const double *count);
+aasr_status aasr_stats_write_lls(const char *path, double loglik, int64_t frames);
+
+/* The accumulator of one model and topology, on the device.  Sums of every mixture component
+ * (gamma, aux gamma, sum gamma x, sum gamma x^2), per mixture its frames and mixture_ll, per transition
+ * its count (host).  Deterministic: no atomics, fixed summation order. */
+typedef struct aasr_stats aasr_stats;
+aasr_status aasr_stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats **out);
+void aasr_stats_destroy(aasr_stats *h);
+/* Adds n_frames double frame rows (device, [n_frames x dim]) whose pdfs are pdf[] (host; -1: skip)
+ * on `stream`, no host wait.  d_frame_ll (device, n_frames doubles, or NULL) receives every frame's
+ * safe_log(state likelihood).  Calls on one handle go to one stream. */
+aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int64_t n_frames,
+                                      const int32_t *pdf, double *d_frame_ll, void *stream);
+/* counts the transitions transition[0..n) (-1: none) */
+aasr_status aasr_stats_add_transitions(aasr_stats *h, const int32_t *transition, int64_t n);
+/* sums the Gaussians that several mixtures share and fetches everything to the host (waits) */
+aasr_status aasr_stats_fetch(aasr_stats *h, void *stream);
+/* after a fetch: per pool Gaussian (sum_x / sum_xx [pool x dim]); per pdf its frame count and
+ * mixture_ll and per mixture component (aasr_gmm record order) its gamma; any pointer may be NULL */
+aasr_status aasr_stats_gaussians(const aasr_stats *h, int64_t *feacount, double *gamma, double *aux_gamma,
+                                 double *sum_x, double *sum_xx);
+aasr_status aasr_stats_mixtures(const aasr_stats *h, int64_t *count, double *gamma, double *mixture_ll);
+int32_t aasr_stats_num_transitions(const aasr_stats *h);
+aasr_status aasr_stats_transitions(const aasr_stats *h, int32_t *source, int32_t *target_offset, double *count);
+/* after a fetch: base.phs, base.mcs, base.gks */
+aasr_status aasr_stats_write(const aasr_stats *h, const char *base);
+
+typedef struct aasr_stats_options {
+  int32_t transitions;  /* -t: transition statistics                       */
+  int32_t ophn;         /* -O: read the recipe's alignment= files            */
+  int32_t no_train;     /* -n: only the .lls summary                         */
+  int32_t uttadap;      /* -U: utterance adaptation                          */
+  int32_t info;         /* -i                                                */
+  int32_t num_batches;  /* -B                                                */
+  int32_t batch_index;  /* -I                                                */
+  struct aasr_spkc *speakers; /* -S: speaker configuration or NULL          */
+  const char *out;      /* -o: base name of the output files                 */
+} aasr_stats_options;
+void aasr_stats_default_options(aasr_stats_options *opt);
+
+/* stats main loop (aku/stats.cc:540-795, --ml with .phn segmentations) over one recipe slice: audio,
+ * speaker configuration, features on the device and segmentations per utterance, the accumulation
+ * for many utterances per launch, the dumps and out.lls, the -i messages on stderr. */
+aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
+                                  const char *recipe_path, const aasr_stats_options *opt,
                                   aasr_run_stats *stats);
 
 #ifdef __cplusplus
