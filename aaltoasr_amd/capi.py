@@ -480,6 +480,34 @@ class Gmm:
         L.aasr_debug_set_layouts.restype = None
         L.aasr_debug_set_layouts(self._h, mask)
 
+    def own_layout(self) -> dict:
+        """Diagnostic: the model's own one-pivot layout -- whether its two-term rows are packed, outlier routing
+        (on, outlier components, states that hold them), the centred form for the whole model, states the probe moved."""
+        L = lib()
+        L.aasr_debug_own_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.aasr_debug_own_layout.restype = None
+        out = (C.c_int64 * 6)()
+        L.aasr_debug_own_layout(self._h, out)
+        return {"two_term_rows": bool(out[0]), "routing": bool(out[1]), "outlier_comps": int(out[2]),
+                "outlier_states": int(out[3]), "all_centred": bool(out[4]), "probe_moved": int(out[5])}
+
+    def outlier_path(self):
+        """Diagnostic: (launches of the scoring kernel that merged the outlier components itself, runs of the merge
+        pass) over the scoring calls on this handle so far."""
+        L = lib()
+        L.aasr_debug_outlier_path.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.aasr_debug_outlier_path.restype = None
+        out = (C.c_int64 * 2)()
+        L.aasr_debug_outlier_path(self._h, out)
+        return int(out[0]), int(out[1])
+
+    def set_outlier_fuse(self, on: bool) -> None:
+        """Diagnostic: False leaves the outlier components of every call to the merge pass."""
+        L = lib()
+        L.aasr_debug_set_outlier_fuse.argtypes = [C.c_void_p, C.c_int]
+        L.aasr_debug_set_outlier_fuse.restype = None
+        L.aasr_debug_set_outlier_fuse(self._h, 1 if on else 0)
+
     def active_layout(self) -> int:
         L = lib()
         L.aasr_debug_active_layout.argtypes = [C.c_void_p]

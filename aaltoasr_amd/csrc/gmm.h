@@ -405,7 +405,12 @@ struct aasr_gmm {
   // track parity with outlier components | that state's record << 16 ([S]; models of up to 65 534 states and records);
   // hyb_fuse: set by the scoring launcher around the launch that is to take the partial sums
   aasr::DevBuf<uint32_t> hyb_tab;
-  mutable struct HybFuse { const float *part = nullptr; int64_t pitch = 0; } hyb_fuse;
+  // (used: the HYB instance was launched on them -- where it was not, the merge pass takes the outliers)
+  mutable struct HybFuse { const float *part = nullptr; int64_t pitch = 0; bool used = false; } hyb_fuse;
+  // diagnostics (aasr_debug_outlier_path / aasr_debug_set_outlier_fuse): launches of the HYB instance and runs of the
+  // merge pass since the handle was built, and a switch that leaves every model to the merge pass
+  mutable int64_t hyb_fused_launches = 0, hyb_merge_passes = 0;
+  bool hyb_fuse_off = false;
   // Global constrained MLLR without re-packing: the rows stay those of the unadapted model
   // (rows_unbiased) and log|det| is added to every score at the kernels' output (out_bias_ln)
   bool rows_unbiased = false;

@@ -1732,8 +1732,9 @@ void gmm_cluster_score_launch(aasr_gmm *g, const float *d_frames, int64_t F, flo
       mask_rows = std::max(mask_rows, sub_plans[c].mask_rows);
     }
   } else {
-    // (a global transform over a model with centred-kernel Gaussians carries |det| in the component
-    // weights -- HostModel::logw_bias -- so rows and centred records already hold it)
+    // (a global transform is applied in place, logw_bias == 0: the track kernels take log|det| at their output, the
+    // outlier merge adds it to the centred share, an all-centred model gets it from gmm_add_bias_nofloor after the masked
+    // launch -- exact_part_launch; only rows re-packed for per-class transforms carry |det| in the component weights)
     plan = exact_part_plan(g, cl);
     mask_rows = plan.mask_rows;
   }

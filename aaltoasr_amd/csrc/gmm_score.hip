@@ -1541,9 +1541,10 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
               hyb_pend = 0xffffu;
             }
             if (stc == hyb_st) {
-              // k_outlier_merge's arithmetic: out = log(exp(out) + exp(part)); a part AT the floor holds nothing
-              l0 = merge_floored_shares(l0, hyb_v0 > LOG_TINY_F ? hyb_v0 + pg.hyb_bias : hyb_v0);
-              l1 = merge_floored_shares(l1, hyb_v1 > LOG_TINY_F ? hyb_v1 + pg.hyb_bias : hyb_v1);
+              // k_outlier_merge's arithmetic: out = log(exp(out) + exp(part)); a part AT the floor holds nothing (the
+              // partial sums are floored at 1e-50 / |det|, outlier_part_floor: the floor applies after the bias)
+              l0 = merge_floored_shares(l0, fmaxf(hyb_v0 + pg.hyb_bias, LOG_TINY_F));
+              l1 = merge_floored_shares(l1, fmaxf(hyb_v1 + pg.hyb_bias, LOG_TINY_F));
               hyb_pend = hyb_e_next;
               hyb_st = 0x7fffffff;
             }
@@ -2099,6 +2100,8 @@ static void launch_pl_t(const aasr_gmm *g, const TrackLayout &L, const float *d_
       pg.hyb_part = g->hyb_fuse.part;
       pg.hyb_pitch = g->hyb_fuse.pitch;
       pg.hyb_bias = (float)g->out_bias_ln;
+      g->hyb_fuse.used = true;   // (the callers run the merge pass where no launch took the partial sums)
+      g->hyb_fused_launches++;
       hipLaunchKernelGGL(kern_hyb, dim3(n_items), dim3(NW * 64), smem, stream, d_frames, F,
                          g->dim, g->d_pivot.p, L.a16h.p, split_row, L.close.p, L.sid.p, L.sid_stride,
                          d_out, g->S, pitch, L.ref_ln - (float)g->out_bias_ln, dbg, cl, fop, plan, pg);
@@ -3374,11 +3377,19 @@ static bool launch_centred_ops(const aasr_gmm *g, const CentredOps &ops, int dim
   }
 }
 
+// The floor of a centred launch whose values take log|det| of an in-place global transform afterwards (k_add_bias, the
+// outlier merge): 1e-50 / |det|, so that the floor the reference puts on the TRANSFORMED likelihood is the one that holds
+// (floored at 1e-50 first, a value in [1e-50 / |det|, 1e-50] came out as 1e-50 |det| -- visible from log|det| ~ 11 on).
+static float outlier_part_floor(const aasr_gmm *g) {
+  return std::isfinite(g->out_bias_ln) ? LOG_TINY_F - (float)g->out_bias_ln : LOG_TINY_F;   // (|det| = 0: all at the floor)
+}
+
 static bool launch_centred(const aasr_gmm *g, const float *d_frames, int64_t F, float *d_out,
                            hipStream_t stream, int64_t pitch = 0) {
   CentredOps ops{g->centred_recs.p, g->centred_state_off.p, g->centred_splits.p, g->centred_max_splits,
                  pitch > 0 ? pitch : g->S, 1};
   ops.n_recs = (int64_t)g->host.mix_idx.size();
+  ops.floor_val = outlier_part_floor(g);   // (k_add_bias follows where log|det| != 0 and floors at 1e-50)
   return launch_centred_ops(g, ops, g->centred_dimp, d_frames, F, d_out, stream);
 }
 
@@ -3409,9 +3420,10 @@ __global__ __launch_bounds__(256) void k_outlier_merge(float *__restrict__ out, 
     if (f >= F) break;
     float *o = out + f * S + col;
     // part_bias: log|det| of an in-place global transform -- the matrix path carries it at its output, the centred
-    // records do not (a part AT the floor holds nothing and stays there)
-    float b = tile[lane][ff];
-    if (!floors || b > LOG_TINY_F) b += part_bias;
+    // records do not; the floor applies to the share WITH the bias (the partial sums are floored at 1e-50 / |det|,
+    // outlier_part_floor), and a share at the floor holds nothing
+    float b = tile[lane][ff] + part_bias;
+    if (floors) b = fmaxf(b, LOG_TINY_F);
     const float a = *o;
     const float hi = fmaxf(a, b), lo = fminf(a, b);
     float r = hi;
@@ -3440,6 +3452,8 @@ static void score_outliers(aasr_gmm *g, const float *d_frames, int64_t F, float 
   ops.n_recs = g->hyb_rows;
   ops.crow = crow;
   ops.c1 = c1;
+  ops.floor_val = outlier_part_floor(g);
+  g->hyb_merge_passes++;
   for (int64_t f0 = 0; f0 < F; f0 += pass) {  // pass is a multiple of 512 frames: whole mask words
     const int64_t n = std::min(pass, F - f0);
     if (maskw) {
@@ -3458,12 +3472,13 @@ static void score_outliers(aasr_gmm *g, const float *d_frames, int64_t F, float 
 // Outlier routing with the merge inside the scoring kernel (k_gmm_diag_score_pl<..., HYB>): where the launch that follows
 // is the grouped layout's two-term kernel, the outliers' partial sums of all F frames are formed first (state-major, the
 // centred kernel's coalesced form) and put on the handle for the launcher; returns false where the merge pass has to do
-// it (other layouts / precisions, clustering, more partial sums than a pass holds).
+// it (other layouts / precisions, clustering, more partial sums than a pass holds).  What it returns is an offer: the
+// launcher sets hyb_fuse.used where the HYB instance took it, and the callers run the merge pass where none did.
 static bool hyb_fuse_begin(aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F, hipStream_t stream) {
   g->hyb_fuse = aasr_gmm::HybFuse();
   static const int fuse_env = AASR_EXPERIMENT_ENV("AASR_HYB_FUSE") ? atoi(AASR_EXPERIMENT_ENV("AASR_HYB_FUSE")) : 1;   // EXPERIMENT: 0 = merge pass
   const int64_t Sb = g->hyb_states;
-  if (!fuse_env || !g->hyb_enabled || Sb <= 0 || !g->hyb_tab.p || g->cl.enabled || g->precision != AASR_PREC_F16X2 ||
+  if (!fuse_env || g->hyb_fuse_off || !g->hyb_enabled || Sb <= 0 || !g->hyb_tab.p || g->cl.enabled || g->precision != AASR_PREC_F16X2 ||
       !g->use_bf16x3 || !L.ok || !L.grouped || !L.a16h.p || L.n_pg > 1 || !(g->layout_mask & 1) || L.nk16 <= 0)
     return false;
   const int64_t pass = (F + 63) / 64 * 64;
@@ -3474,6 +3489,7 @@ static bool hyb_fuse_begin(aasr_gmm *g, const TrackLayout &L, const float *d_fra
   }
   CentredOps ops{g->hyb_recs.p, g->hyb_state_off.p, g->hyb_splits.p, g->hyb_max_splits, 1, pass};
   ops.n_recs = g->hyb_rows;
+  ops.floor_val = outlier_part_floor(g);
   if (!launch_centred_ops(g, ops, g->centred_dimp, d_frames, F, g->hyb_scratch.p, stream)) return false;
   g->hyb_fuse.part = g->hyb_scratch.p;
   g->hyb_fuse.pitch = pass;
@@ -3563,6 +3579,19 @@ extern "C" void aasr_debug_own_layout(const aasr_gmm *g, int64_t *out) {
   out[3] = g->hyb_states;
   out[4] = g->ill_conditioned ? 1 : 0;
   out[5] = g->f16_probe_moved;
+}
+
+// Diagnostic: what the scoring calls on this handle did with the outlier components since it was built -- out[0] launches
+// of the scoring kernel's HYB instance (the merge in its close logic), out[1] runs of the merge pass (score_outliers)
+extern "C" void aasr_debug_outlier_path(const aasr_gmm *g, int64_t *out) {
+  if (!g || !out) return;
+  out[0] = g->hyb_fused_launches;
+  out[1] = g->hyb_merge_passes;
+}
+// Diagnostic switch: 0 leaves the outlier components of every call to the merge pass, 1 (the default) lets the launcher
+// fuse the merge into the scoring kernel where its rules admit it
+extern "C" void aasr_debug_set_outlier_fuse(aasr_gmm *g, int on) {
+  if (g) g->hyb_fuse_off = !on;
 }
 
 // Diagnostic (tests, bench.py): the engine parts of a model (gmm_plan_engine_parts) -- out[0] parts, out[1] columns of an
@@ -3807,8 +3836,10 @@ void gmm_classes_exact_launch(aasr_gmm *g, const float *d_frames, int64_t n, flo
   }
 }
 
-// log|det| of an in-place global transform for the kernels that do not take it at their output
-// (diagnostic layouts only: the track kernels fold it into their reference exponent)
+// log|det| of an in-place global transform for the kernels that do not take it at their output: the general kernel (a
+// diagnostic layout) and the centred form of ill-conditioned models, whose launch floors at 1e-50 / |det|
+// (outlier_part_floor) so that this floor is the only one that acts; the track kernels fold log|det| into their reference
+// exponent
 __global__ void k_add_bias(float *__restrict__ out, float bias, int64_t n, int64_t S, int64_t pitch) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -4072,9 +4103,10 @@ void gmm_score_launch_pitched(aasr_gmm *g, const float *d_frames, int64_t F, flo
     return;
   }
   const TrackLayout &L = g->paired.ok ? g->paired : g->tracks;
-  const bool fused = hyb_fuse_begin(g, L, d_frames, F, stream);
+  hyb_fuse_begin(g, L, d_frames, F, stream);
   const bool done = (g->use_bf16x3 && launch_bf16(g, L, d_frames, F, d_out, stream, nullptr, pitch)) ||
                     launch_tracks(g, L, d_frames, F, d_out, stream, nullptr, pitch);
+  const bool fused = g->hyb_fuse.used;   // (not what hyb_fuse_begin offered: what the launch took)
   g->hyb_fuse = aasr_gmm::HybFuse();
   if (!done) raise(AASR_ERR_UNSUPPORTED, "no track kernel instance for this model");
   // the Gaussians the matrix layouts left out (null rows): centred form, merged per state into the padded rows (where
@@ -4238,9 +4270,10 @@ void gmm_score_launch(aasr_gmm *g, const float *d_frames, int64_t F, float *d_ou
   bool done = false;
   bool fused = false;
   if (!done && (g->layout_mask & 1) && g->paired.ok) {
-    fused = hyb_fuse_begin(g, g->paired, d_frames, F, stream);
+    hyb_fuse_begin(g, g->paired, d_frames, F, stream);
     done = (g->use_bf16x3 && launch_bf16(g, g->paired, d_frames, F, d_out, stream)) ||
            launch_tracks(g, g->paired, d_frames, F, d_out, stream);
+    fused = g->hyb_fuse.used;   // (not what hyb_fuse_begin offered: what the launch took)
     g->hyb_fuse = aasr_gmm::HybFuse();
   }
   if (!done && (g->layout_mask & 2) && g->tracks.ok)

@@ -59,6 +59,27 @@ def push_states_over_the_f16_limits(model, states, kappa2=100.0):
     return mean, var, off, idx, w
 
 
+def sharpen_outliers(model, picks, var_scale=2e-3, shift=0.0):
+    """Outlier routing test models: for every (state, n) of `picks` the Gaussians of the state's first n components get
+    their variances multiplied by `var_scale` (sigma ~ 0.045 of its neighbours': kappa = sum_d p (mu - pivot)^2 grows 500-fold,
+    far over every matrix layout's limit) and their means moved `shift` times further from the pool's pivot.  At its own
+    mean such a Gaussian is e^120 above its neighbours (39 dimensions) and a few of its own sigmas away it is nothing: frames
+    placed on it see a state that IS the outlier.  Returns (model, outlier Gaussians per state {state: [pool indices]})."""
+    mean, var, off, idx, w = model
+    mean, var = np.array(mean, np.float64), np.array(var, np.float64)
+    pivot = mean.mean(0)
+    out, done = {}, set()
+    for s, n in picks:
+        gs = [int(g) for g in idx[off[s]:off[s] + n]]
+        out[int(s)] = gs
+        for g in gs:
+            if g not in done:     # (a tied pool: once per Gaussian)
+                var[g] *= var_scale
+                mean[g] = pivot + (mean[g] - pivot) * (1.0 + shift)
+                done.add(g)
+    return (mean, var, off, idx, w), out
+
+
 def make_clustering(mean, n_clusters, seed=SEED + 3, iters=4):
     """Deterministic k-means on the Gaussian means (what aku's gcluster produces in
     spirit): returns gauss_to_cluster [G] int32 with every cluster non-empty."""

@@ -492,4 +492,19 @@ def test_clustering_with_outlier_routed_and_ill_conditioned_models(capi, oracle)
         got = gm.score(frames)
         assert np.array_equal(gm.cluster_exact_counts(len(frames)), want_n)
         assert_ll(got, want, "centred form, clustered (%g, %g)" % (minc, ming))
+    # ... and under one global transform, applied in place: the masked centred launch carries no log|det|, it is added to
+    # the exact parts before the merge (gmm_add_bias_nofloor)
+    for scale in (1.12, 0.9):   # log|det| ~ +4.4 / -4.1
+        A = np.eye(39) * scale * rng.uniform(0.97, 1.03, 39) + 0.01 * rng.standard_normal((39, 39))
+        W = np.hstack([0.05 * rng.standard_normal(39)[:, None], A])
+        assert abs(np.log(abs(np.prod(np.diag(A))))) > 3.5
+        gm.set_cmllr(np.zeros(512, np.int32), W[None])
+        assert gm.active_layout() == 4
+        for minc, ming in ((0.0, 0.25), (0.3, 0.1)):
+            om.set_clustering(32, _pairs(g2c), minc, ming)
+            want, want_n = om.score_clustered_adapted(frames.astype(np.float64), W, want_counts=True)
+            gm.set_clustering_min_evals(minc, ming)
+            got = gm.score(frames)
+            assert np.array_equal(gm.cluster_exact_counts(len(frames)), want_n)
+            assert_ll(got, want, "centred form, clustered (%g, %g), in-place transform x %g" % (minc, ming, scale))
     gm.close()

@@ -204,3 +204,86 @@ def test_routed_scoring_in_many_passes(capi, oracle):
         assert_ll(many[:200], ref, "per-class transforms over outlier-routed Gaussians")
     finally:
         L.aasr_debug_set_pass_bytes(0.0)
+
+
+def _far_model(S, picks, seed, D=39, comps=8, shift=5.0):
+    """Ordinary variances, means moved six times further from the pool's pivot: kappa = sum_d p (mu - pivot)^2 is ~36 times
+    an ordinary Gaussian's (over every matrix layout's limit) while the likelihood's slope stays ordinary, so a frame can
+    be placed to a hundredth of a nat."""
+    base = synth.make_model(D=D, G=S * comps, S=S, comps=comps, seed=seed)
+    return synth.sharpen_outliers(base, picks, var_scale=1.0, shift=shift)
+
+
+def _frames_at_levels(model, outl, levels, xf, seed, n_random=40):
+    """Frames (as the caller passes them: the model sees a * frame + b) on a ray from each outlier state's first outlier,
+    at the points where the state's log-likelihood WITHOUT log|det| equals each of `levels`; then some N(0, 1) ones."""
+    from test_outlier_fused_gpu import _comp_ll, _lse
+    mean, var, off, idx, w = model
+    D = mean.shape[1]
+    rng = np.random.default_rng(seed)
+    a, b = xf
+    out = []
+    for s, gs in outl.items():
+        g = gs[0]
+        u = rng.standard_normal(D)
+        u *= np.sqrt(var[g])
+        for level in levels:
+            def at(t):
+                x = ((mean[g] + t * u - b) / a).astype(np.float32)
+                return x, _lse(_comp_ll(model, s, (x.astype(np.float64) * a + b)[None])[0])[0]
+            lo, hi = 0.0, 200.0
+            assert at(lo)[1] > level > at(hi)[1]
+            for _ in range(70):
+                mid = 0.5 * (lo + hi)
+                lo, hi = (mid, hi) if at(mid)[1] > level else (lo, mid)
+            out.append(at(lo)[0])
+    out = np.array(out, np.float32)
+    return np.concatenate([out, ((rng.standard_normal((n_random, D)) - b) / a).astype(np.float32)])
+
+
+@pytest.mark.parametrize("logdet", [15.0, -15.0])
+def test_the_floor_applies_to_the_transformed_likelihood(capi, oracle, logdet):
+    """The reference floors the TRANSFORMED likelihood at 1e-50.  A path that floors its centred sums first and adds
+    log|det| afterwards returns floor + log|det| for a state whose own value lies in [floor - log|det|, floor]: visible
+    (above ln 2^-150, the line assert_ll draws) from log|det| ~ 11.2 on.  Frames are placed so that the oracle has values
+    across that interval (log|det| = +15), and -- the mirror -- shares that are above the floor before log|det| = -15 and
+    below it after: the whole model in the centred form, and a model with outlier routing on the fused path and on the
+    merge pass."""
+    from test_outlier_fused_gpu import _diag_transform, assert_path, scored
+    floor = np.log(1e-50)
+    D = 39
+    W, xf = _diag_transform(D, logdet, 901)
+    # levels of the state's value before log|det|: below the floor (above it and visible after +15) / above it (below after -15)
+    # (visible after +15: final values above ln 2^-150 = floor + 11.16, i.e. less than 3.84 below the floor before it)
+    levels = [floor - 3.5, floor - 2.5, floor - 1.5, floor - 0.5, floor + 3.0] if logdet > 0 else \
+             [floor + 14.0, floor + 8.0, floor + 1.0, floor + 16.0, floor + 30.0]
+    # the whole model in the centred form
+    S = 16
+    model, outl = _far_model(S, [(s, 8) for s in range(S)], seed=902)
+    g2t = np.zeros(model[0].shape[0], np.int32)
+    fr = _frames_at_levels(model, {s: outl[s] for s in (0, 7, 15)}, levels, xf, 903)
+    ref = oracle.score_adapted(oracle.DiagModel(*model), fr.astype(np.float64), g2t, W)
+    if logdet > 0:   # (the inputs: values the interval holds, visible)
+        assert ((ref > -150.0 * np.log(2.0)) & (ref < floor + logdet)).sum() >= 6
+    g = capi.Gmm.from_arrays(*model)
+    assert g.active_layout() == 4 and g.own_layout()["all_centred"]
+    g.set_cmllr(g2t, W)
+    assert g.active_layout() == 4
+    assert_ll(g.score(fr), ref, "centred form, log|det| = %+g" % logdet)
+    g.close()
+    # outlier routing: the fused merge and the merge pass
+    S = 64
+    model, outl = _far_model(S, [(6, 1), (33, 2), (63, 1)], seed=904)
+    g2t = np.zeros(model[0].shape[0], np.int32)
+    fr = _frames_at_levels(model, outl, levels, xf, 905)
+    ref = oracle.score_adapted(oracle.DiagModel(*model), fr.astype(np.float64), g2t, W)
+    cols = sorted(outl)
+    if logdet > 0:
+        assert ((ref[:, cols] > -150.0 * np.log(2.0)) & (ref[:, cols] < floor + logdet)).sum() >= 6
+    g = capi.Gmm.from_arrays(*model)
+    assert_path(g, model, outl)
+    g.set_cmllr(g2t, W)
+    assert_ll(scored(g, lambda: g.score(fr), True), ref, "fused merge, log|det| = %+g" % logdet)
+    g.set_outlier_fuse(False)
+    assert_ll(scored(g, lambda: g.score(fr), False), ref, "merge pass, log|det| = %+g" % logdet)
+    g.close()
