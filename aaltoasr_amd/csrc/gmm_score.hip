@@ -9,26 +9,23 @@
 //
 // Formulation.  ll_g(x) = c_g - 1/2 sum_d p_gd (x_d - mu_gd)^2 is expanded
 // around a per-dimension pivot v (x' = x - v, mu' = mu - v) into a dense
-// contraction over K = 2*dim + 1:
+// contraction over K = 2*dim + 1 (+ the constant's remainder in the split forms):
 //     log2e * ll = sum_d [p mu' log2e] x'_d + [-p/2 log2e] x'_d^2 + C_g * 1
-// so the frame x Gaussian quadratic forms are an exact-f32 GEMM that runs on
-// the matrix cores (v_mfma_f32_32x32x2_f32: one instruction = one dimension's
-// (x', x'^2) pair), with the mixture log-sum-exp fused behind it.  log(w) of
-// the mixture weight is folded into C_g, the result is in log2 units so the
-// epilogue is max -> v_exp_f32(x - max) -> add -> v_log_f32.
+// so the frame x Gaussian quadratic forms are a GEMM on the matrix cores with the
+// mixture log-sum-exp fused behind it, frame-stationary: a wave keeps the K x 64
+// operand of its 64 frames in registers, the Gaussian rows stream past through LDS.
 //
-// Work decomposition (frame-stationary).  A workgroup of 4 waves owns 256
-// frames; each wave keeps its 64 frames' K x 64 operand in VGPRs for the whole
-// kernel (nkk x 2 registers) and the Gaussian rows stream past in tiles of 64
-// rows: HBM/L2 -> LDS by global_load_lds (double buffered, one barrier per
-// tile), LDS -> A fragments by ds_read_b128.  Each wave computes a 64-row x
-// 64-frame tile as 2x2 MFMA blocks.  The epilogue dumps one 32-row block pair
-// at a time to a wave-private LDS staging area laid out [row][frame], then
-// every lane owns one frame and reduces the rows of each mixture segment
-// (16 rows at a time in registers, merged online) -- no cross-lane traffic,
-// arbitrary components per state, segments may span chunks and tiles.
-//
-// Roofline: FP32 matrix rate, 2*K flop per frame x row pair; see DESIGN.md.
+// Which kernel serves what, in the order they stand in this file:
+//   k_gmm_diag_score           f32 MFMA, LDS-staged epilogue: any layout (diagnostic) and the per-Gaussian view
+//   k_gmm_diag_score_tracks    AASR_PREC_F32: f32 MFMA, track layouts, in-register epilogue
+//   k_gmm_diag_score_bf16x3    AASR_PREC_BF16X3 beyond five K slabs (39 dimensions): phase-shifted wave groups
+//   k_gmm_diag_score_pl        AASR_PREC_F16X2 (the default; what bench.py times) and BF16X3 up to five slabs: the
+//                              software-pipelined kernel; + k_frame_operand, the row cuts, launch_split / launch_bf16
+//   gmm_probe_f16x2            load-time guard of the two-term form
+//   k_gmm_full_score[_bf16x3]  full-covariance pools (f32 / two fp16 / three bf16 terms)
+//   k_gmm_diag_score_centred, k_outlier_merge   beyond every expanded form's limits: no MFMA; outlier routing
+//   k_gmm_diag_score_f64[_classes]              AASR_PREC_F64: the reference's arithmetic in double
+//   then the dispatch: transforms, classes, engine parts, dimension parts, gmm_score_launch*, gmm_gauss_launch
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <unordered_map>
@@ -1157,26 +1154,13 @@ struct PlSmem {
   static constexpr int OG = kBig ? 32 : 16;
   static constexpr int kOutStride = kBig ? 34 : 20;
   static constexpr int kOutFloatsPerWave = GROUPED ? FRAMES_PER_WAVE * kOutStride : 0;
-  static constexpr int kMapBytes = NBUF * 16 * 4;   // MAPPED: the tiles' pair entries, [buffer][track][quad position]
-  static constexpr int kBytes = NBUF * kTileBytes + (WIDE ? 8 : 4) * kOutFloatsPerWave * 4 + kMapBytes;
+  // Padding no kernel touches (until round 6: a side table of 64 bytes per tile buffer).  It stays because workgroups per
+  // CU by LDS is floor(160 KB / kBytes), and without it seven instances sit exactly on a divisor and would gain a resident
+  // workgroup (NK16 = 5, GROUPED, 4 waves, three terms: 82 048 -> 81 920 B = 80 KB, one workgroup per CU -> two): a change
+  // of behaviour that would have to be measured, not a deletion.  Table: profiles/scoring_unit_kernel_digests.txt.
+  static constexpr int kPadBytes = NBUF * 64;
+  static constexpr int kBytes = NBUF * kTileBytes + (WIDE ? 8 : 4) * kOutFloatsPerWave * 4 + kPadBytes;
 };
-
-// MAPPED (GROUPED only; NOT INSTANTIATED since round 6: it served section 0 of round 4's mixed layout, which the engine
-// parts replaced; the branches stay in the kernel's source because the headline instance's code is better left untouched):
-// the section's states are a SUBSET of
-// the model's, so a pair's output columns come from a table instead of its ordinal: per tile, track and quad position
-// `sid` holds column | flags of the pair that closes there (16 words per tile; they ride into LDS with the tile's rows,
-// so the close logic never waits for global memory -- a per-close vector load is waited for in issue order, i.e. behind
-// the tile copy requested just before it: measured +9 %).  Pairs are formed inside groups of 16 output columns, a
-// group is staged and flushed as WHOLE lines exactly as in the unmapped kernel -- the columns of states the section does
-// not hold go out with whatever the staging area holds, and the other section's launch, which comes second, stores its
-// values over them.  (Both other forms were built and measured on configs[2] with 1 % of the states routed away: masked
-// flushes that leave the foreign columns alone +5 %, direct 4-byte stores for the shared groups +12 % -- a partial
-// write of a line costs a fill of that line, and every frame row has such a line wherever a state is missing.)
-constexpr int kMapCol = 0xffffff;      // column field
-constexpr int kMapEmpty = 1 << 28;     // this track holds no state in this pair (column: the partner's)
-constexpr int kMapFlush16 = 1 << 29;   // last pair of its group of 16 columns
-constexpr int kMapFlush32 = 1 << 30;   // ... of its group of 32
 
 // AASR_PL_TRACE (experiment builds only, tools/pl_trace.py): where one workgroup's waves spend their cycles.  Every wave of
 // workgroup AASR_PL_TRACE_BLOCK reads the shader clock (s_memtime) at the phase boundaries of its tile loop and sums the
@@ -1195,29 +1179,14 @@ __device__ unsigned long long g_pl_trace[8][12];
 #define PL_TRACE_DECL
 #define PL_TRACE(k)
 #endif
-#ifndef AASR_PL_PRIO
-#define AASR_PL_PRIO 1   // issue priority of a wave of k_gmm_diag_score_pl inside its matrix phases (0: left alone)
-#endif
-// Priorities of the 8-wave form's two wave groups (AASR_PL_PRIO_SCHEME, round 5; found with the phase trace below).  The
-// two waves of a SIMD share the matrix pipe whenever their matrix phases overlap, and at equal priority the arbiter gives
-// the older wave -- the leading group's -- two thirds of it: the leading wave ran ahead through its H1 and then waited
-// ~1 200 cycles per tile at the barrier for the lagging wave, whose H1 had crawled along beside it, and in that wait (the
-// partner in its close logic, nobody in a matrix phase) the pipe idled 20 % of the time.  Scheme 1: the leading group
-// takes the higher priority in H0 and the lower in H1, the lagging group the reverse -- in the long H1 / H1 overlap the
-// lagging wave now wins, both groups reach the barrier together (waits 560 / 490 cycles in the traced build instead of
-// 1 230 / 450), a tile takes 5 000 cycles instead of 5 450: configs[1] 18.77 -> 18.14 ms (-3.3 %), three alternating
-// runs on one box.  Measured against it: the reverse assignment (scheme 2) 18.60, the lagging group higher throughout
-// (the roles swap: 19.3), priorities 3 / 1 the same as 2 / 1, 1 / 0 18.44, the lagging group's barrier one or two slabs
-// into H0 18.36 / 18.60.  0: every wave AASR_PL_PRIO in its matrix phases (round 4).
-#ifndef AASR_PL_PRIO_SCHEME
-#define AASR_PL_PRIO_SCHEME 1
-#endif
-#ifndef AASR_PL_PRIO_HI
-#define AASR_PL_PRIO_HI 2
-#endif
-#ifndef AASR_PL_PRIO_LO
-#define AASR_PL_PRIO_LO 1
-#endif
+// Issue priorities of the matrix phases (s_setprio; found with the phase trace above).  4-wave form: priority 1 inside a
+// matrix phase, 0 in the close logic, so the wave's matrix instructions do not queue behind the other wave's vector, LDS
+// and store instructions (-0.9 % on configs[2], priority 1 and 3 alike).  8-wave form: the two waves of a SIMD share the
+// matrix pipe whenever their matrix phases overlap, and at equal priority the arbiter gives the older wave -- the leading
+// group's -- two thirds of it: it ran ahead through its H1 and then waited ~1 200 cycles per tile at the barrier.  So the
+// leading group takes priority 2 in H0 and 1 in H1, the lagging group the reverse, and both reach the barrier together:
+// configs[1] 18.77 -> 18.14 ms.  Measured against it and lost (round 5): the reverse assignment 18.60, the lagging group
+// higher throughout 19.3, priorities 1 / 0 18.44 (3 / 1 the same as 2 / 1).
 // HYB (GROUPED, two terms, one pivot, unmasked; round 6): outlier routing without a merge pass.  The Gaussians the matrix
 // layout left out (null rows) are summed per state by k_gmm_diag_score_centred BEFORE this launch, into a state-major
 // buffer; a lane that closes such a state adds the buffer's value for its frame -- the arithmetic of k_outlier_merge,
@@ -1227,7 +1196,7 @@ __device__ unsigned long long g_pl_trace[8][12];
 // each other within a tile's time (the launcher leaves models where they are dense to the engine parts).  (k_outlier_merge's read-modify-write of one column of the score matrix
 // touches a line per frame: 20 us per state and 449 280 frames, more than the gather of a model with engine parts from
 // ~100 states on.)
-template <int NK16, bool GROUPED, bool CL, bool WIDE, int NS, bool MAPPED = false, bool PGF = false, bool HYB = false>
+template <int NK16, bool GROUPED, bool CL, bool WIDE, int NS, bool PGF = false, bool HYB = false>
 __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_score_pl(
     const float *__restrict__ frames, int64_t F, int dim, const float *__restrict__ pivot,
     const uint16_t *__restrict__ apack, const int32_t *__restrict__ split_row,
@@ -1264,59 +1233,50 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
   const int lane = tid & 63;
   constexpr int NBUF = SM::NBUF;
   float *ost = abuf0 + NBUF * kTileFloats + wave * SM::kOutFloatsPerWave;
-  int *emap = (int *)(abuf0 + NBUF * kTileFloats + NW * SM::kOutFloatsPerWave);   // MAPPED: [NBUF][2 tracks][8 positions]
-  // a tile's rows and (MAPPED) its 16 pair entries into tile buffer `b`
-  // The tile copy in the scalar-base form of the LDS-DMA instruction: the tile's address is wave-uniform, so the base goes
+  // A tile's rows into tile buffer `b`: the tile copy in the scalar-base form of the LDS-DMA instruction: the tile's address is wave-uniform, so the base goes
   // in a scalar register pair (two scalar additions per instruction) and the lanes carry ONE constant 32-bit offset,
   // 16 * lane, for the whole launch -- no 64-bit per-lane address to form and to send to the address unit per instruction
-  // (AASR_PL_SADDR_COPY, default 1; 0: the generic per-lane pointers of issue_tile_copy_raw).  configs[1] 17.94 -> 17.84 ms,
-  // configs[2] 10.42 -> 10.38 ms per step, alternating runs on one box; two registers fewer.  (Round 5 also spread the copy
+  // (against the generic per-lane pointers of issue_tile_copy_raw: configs[1] 17.94 -> 17.84 ms, configs[2] 10.42 ->
+  // 10.38 ms per step, alternating runs on one box; two registers fewer).  (Round 5 also spread the copy
   // instructions over the slabs of the H0 that follows the barrier instead of issuing them behind it -- the barrier interval
   // of the phase trace fell from ~550 to ~260 cycles and H0 grew by as much: an LDS-DMA instruction costs the issuing wave
   // 100-150 cycles wherever it stands; 1 % slower with twelve more registers, removed.  The whole copy issued by the
   // leading group alone, whose close logic follows the barrier: +0.7 %, removed.)
-#ifndef AASR_PL_SADDR_COPY
-#define AASR_PL_SADDR_COPY 1
-#endif
   const unsigned lane_off16 = (unsigned)lane * 16u;
   auto issue_tile = [&](int64_t tile, int b) {
-    if (AASR_PL_SADDR_COPY) {
-      constexpr int kChunks = kTileFloats / 4 / 64;   // 1 KB instructions per tile
-      const char *gbase = (const char *)((const float *)apack + (size_t)tile * kTileFloats);
-      const unsigned lbase = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)(abuf0 + b * kTileFloats));
-      // a wave takes CONSECUTIVE 1 KB pieces: one scalar base, one M0, the pieces told apart by the instruction's immediate
-      // offset (it moves the global and the LDS address alike) -- AASR_PL_COPY_IMM, default 1; 0: piece c = wave + k * NW,
-      // a base and an M0 per instruction.  configs[1] 17.91 -> 17.82 ms, three alternating runs on one box.
-#ifndef AASR_PL_COPY_IMM
-#define AASR_PL_COPY_IMM 1
-#endif
-      constexpr int kRounds = (kChunks + NW - 1) / NW;
-      if (AASR_PL_COPY_IMM && kRounds <= 4) {
-        const int w = __builtin_amdgcn_readfirstlane(wave);
-        const int c0 = w * kRounds;   // pieces c0 .. c0 + kRounds - 1 (the last waves may run past the tile: guarded)
-        const unsigned long long sb = (unsigned long long)(uintptr_t)gbase + (unsigned long long)c0 * 1024ull;
-        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sb);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sb >> 32));
-        const unsigned long long sbase = (unsigned long long)lo | ((unsigned long long)hi << 32);
-        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lbase + (unsigned)c0 * 1024u));
-        const int cnt = kChunks - c0 < kRounds ? kChunks - c0 : kRounds;   // wave-uniform
-        // (one statement per count: M0 must hold between the instructions)
-        if (cnt >= 4)
-          asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                       "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072"
-                       : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
-        else if (cnt == 3)
-          asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                       "global_load_lds_dwordx4 %1, %2 offset:2048"
-                       : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
-        else if (cnt == 2)
-          asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024"
-                       : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
-        else if (cnt == 1)
-          asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
-      } else {
+    constexpr int kChunks = kTileFloats / 4 / 64;   // 1 KB instructions per tile
+    const char *gbase = (const char *)((const float *)apack + (size_t)tile * kTileFloats);
+    const unsigned lbase = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)(abuf0 + b * kTileFloats));
+    // a wave takes CONSECUTIVE 1 KB pieces: one scalar base, one M0, the pieces told apart by the instruction's immediate
+    // offset (it moves the global and the LDS address alike); against a base and an M0 per instruction: configs[1]
+    // 17.91 -> 17.82 ms, three alternating runs on one box.  Tiles of more than 4 pieces per wave take a piece per round.
+    constexpr int kRounds = (kChunks + NW - 1) / NW;
+    if (kRounds <= 4) {
+      const int w = __builtin_amdgcn_readfirstlane(wave);
+      const int c0 = w * kRounds;   // pieces c0 .. c0 + kRounds - 1 (the last waves may run past the tile: guarded)
+      const unsigned long long sb = (unsigned long long)(uintptr_t)gbase + (unsigned long long)c0 * 1024ull;
+      const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sb);
+      const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sb >> 32));
+      const unsigned long long sbase = (unsigned long long)lo | ((unsigned long long)hi << 32);
+      const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lbase + (unsigned)c0 * 1024u));
+      const int cnt = kChunks - c0 < kRounds ? kChunks - c0 : kRounds;   // wave-uniform
+      // (one statement per count: M0 must hold between the instructions)
+      if (cnt >= 4)
+        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
+                     "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072"
+                     : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
+      else if (cnt == 3)
+        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
+                     "global_load_lds_dwordx4 %1, %2 offset:2048"
+                     : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
+      else if (cnt == 2)
+        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024"
+                     : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
+      else if (cnt == 1)
+        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
+    } else {
 #pragma unroll
-      for (int k = 0; k < (kChunks + NW - 1) / NW; k++) {
+      for (int k = 0; k < kRounds; k++) {
         const int c = __builtin_amdgcn_readfirstlane(wave) + k * NW;   // wave-uniform
         if (c < kChunks) {
           const unsigned long long sb = (unsigned long long)(uintptr_t)gbase + (unsigned long long)c * 1024ull;
@@ -1327,44 +1287,23 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
           asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(dst), "v"(lane_off16), "s"(sbase) : "memory", "m0");
         }
       }
-      }
-    } else {
-      issue_tile_copy_raw((const float *)apack + (size_t)tile * kTileFloats, abuf0 + b * kTileFloats, kTileFloats, wave, lane, NW);
-    }
-    if (MAPPED && wave == NW - 1 && lane < 16) {
-      const int32_t *src = sid + tile * 16 + lane;
-      const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)(emap + b * 16));
-      asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" : : "s"(dst), "v"(src) : "memory", "m0");
     }
   };
-  // 8-wave form: waves 4-7 pass the tile's barrier in the MIDDLE of their H0 instead of at the end of H1, so they run
-  // three quarters of a tile behind waves 0-3 -- the two waves of a SIMD then never sit in their close logic (or at
+  // 8-wave form: waves 4-7 pass the tile's barrier in front of their H0 instead of at the end of H1, so they run
+  // nearly a whole tile behind waves 0-3 -- the two waves of a SIMD then never sit in their close logic (or at
   // the barrier) at the same time, one of them always has MFMAs to issue.  Three tile buffers make the lag legal: the
   // copy of tile t + 2 is issued by every wave right behind its barrier t (all waves are past tile t - 1 there) and
   // has landed at barrier t + 1, before the lagging group's first read of it.
-#ifdef AASR_PL_NOLAG
-  const int group = 0;
-#else
+  // (The barrier in front of slab 0 / 1 / 2 of H0, configs[2], ms of the scoring stage on one box: 8.47 / 8.55 / 8.53.)
   const int group = WIDE ? __builtin_amdgcn_readfirstlane(wave >> 2) : 0;
-#endif
-  auto matrix_prio = [&](int phase) {
-    if (AASR_PL_PRIO_SCHEME >= 1 && WIDE) {
-      const bool hi = AASR_PL_PRIO_SCHEME == 1 ? ((group == 1) == (phase == 1)) : ((group == 1) != (phase == 1));
-      if (hi) __builtin_amdgcn_s_setprio(AASR_PL_PRIO_HI);
-      else __builtin_amdgcn_s_setprio(AASR_PL_PRIO_LO);
-    } else if (AASR_PL_PRIO > 0) {
-      __builtin_amdgcn_s_setprio(AASR_PL_PRIO);
+  auto matrix_prio = [&](int phase) {   // see "Issue priorities" above the kernel
+    if (WIDE) {
+      if ((group == 1) == (phase == 1)) __builtin_amdgcn_s_setprio(2);
+      else __builtin_amdgcn_s_setprio(1);
+    } else {
+      __builtin_amdgcn_s_setprio(1);
     }
   };
-  // slab of H0 in front of which the lagging group's barrier sits: early in the phase, so that the lagging waves run
-  // nearly a whole tile behind (configs[2], NK16 = 5, ms of the scoring stage on one box: slab 0 8.45, slab 1 8.43,
-  // slab 2 -- the middle, rounds 3's choice -- 8.51, slab 3 8.61; with the issue priority of the matrix phases, below:
-  // slab 0 8.47, slab 1 8.55, slab 2 8.53 -- the barrier in front of the phase)
-#ifdef AASR_PL_JB
-  constexpr int JB = AASR_PL_JB < NK16 ? AASR_PL_JB : 0;
-#else
-  constexpr int JB = 0;
-#endif
   const int n = lane & 31;
   const int h = lane >> 5;  // K half of a slab held by this lane AND its row track
   const int64_t f0 = (int64_t)blk * (NW * FRAMES_PER_WAVE) + wave * FRAMES_PER_WAVE;
@@ -1500,8 +1439,7 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
   };
 
   // close logic of one 32-row block: P[nb][q] = this lane's sum of 2^x over quad q for frame block nb
-  // e0 / e1 (MAPPED): the pair entries of the block's four quad positions on track 0 / 1 (wave-uniform: scalar registers)
-  auto commit = [&](const float (&P)[2][4], unsigned nib, const int (&e0)[4], const int (&e1)[4]) {
+  auto commit = [&](const float (&P)[2][4], unsigned nib) {
     if (AASR_DBG(128)) {   // ablation: no close logic
       asm volatile("" ::"v"(P[0][0]), "v"(P[0][1]), "v"(P[0][2]), "v"(P[0][3]), "v"(P[1][0]), "v"(P[1][1]), "v"(P[1][2]), "v"(P[1][3]));
       return;
@@ -1522,16 +1460,6 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
           if (ok0) orow0[next_sid] = l0;
           if (ok1) orow1[next_sid] = l1;
           next_sid = my_sid[closes];
-        } else if (MAPPED) {
-          const int ent = h ? e1[q] : e0[q];
-          const int col = ent & kMapCol;
-          const int slot = (ent & kMapEmpty) ? OG : (col & (OG - 1));   // an empty track stages into the spare slot
-          ost[n * kOS + slot] = l0;
-          ost[(32 + n) * kOS + slot] = l1;
-          if (ent & (OG == 32 ? kMapFlush32 : kMapFlush16)) {   // the same on both tracks: wave-uniform
-            const int64_t s_base = col & ~(OG - 1);
-            flush_group(s_base, (int)(S - s_base < OG ? S - s_base : OG));
-          }
         } else {
           const int pairs_closed = closes;
           if constexpr (HYB) {
@@ -1608,14 +1536,17 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
     load_frags(abuf0, 0, 0, 0);
   }
   int bi = 0;
-  int ep0[4] = {0, 0, 0, 0}, ep1[4] = {0, 0, 0, 0};   // MAPPED: entries of block 1 of the previous tile
   for (int64_t t = t_begin; t < t_end; t++) {
     float *acur = abuf0 + bi * kTileFloats;
     const int bn = bi + 1 < NBUF ? bi + 1 : 0, bnn = bn + 1 < NBUF ? bn + 1 : 0;
     float *anext = abuf0 + bn * kTileFloats;
     // tile t + 2 goes where tile t - 1 was (three buffers), or into tile t's own buffer when every wave is done
     // with it at the barrier (two buffers, no lagging group)
+    // (Read by nothing since the side table of round 4's mixed layout went; with this copy of the index gone the register
+    // allocator colours the loop's scalar registers differently -- the same instructions, other register numbers.  It
+    // stays so that the kernels are byte for byte the ones that were measured.)
     const int bcur = bi;
+    (void)bcur;
     bi = bn;
     // barrier t of this wave: its share of tile t + 1 has landed, and every wave is past tile t - 1
     auto tile_barrier = [&]() {
@@ -1652,26 +1583,9 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
     mask_v = ((const uint32_t *)close_mask)[((t + 1) >> 1) + lane_zero];
     unsigned long long bits_next = 0;
     if (CL && t + 1 < t_end) bits_next = mrow[(size_t)(t + 1) * TILE_ROWS];
-    // MAPPED: this tile's pair entries (this lane's track) out of the tile buffer's side table, both blocks now -- the
-    // buffer may be handed to tile t + 2 at this tile's barrier, in front of the commit of block 0
-    // (one word per lane, then lane reads: the entries are wave-uniform and live in scalar registers)
-    int en00[4] = {0, 0, 0, 0}, en01[4] = {0, 0, 0, 0}, en10[4] = {0, 0, 0, 0}, en11[4] = {0, 0, 0, 0};   // [block][track]
-    if (MAPPED) {
-      const int ev = emap[bcur * 16 + (lane & 15)];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        en00[q] = __builtin_amdgcn_readlane(ev, q);
-        en10[q] = __builtin_amdgcn_readlane(ev, 4 + q);
-        en01[q] = __builtin_amdgcn_readlane(ev, 8 + q);
-        en11[q] = __builtin_amdgcn_readlane(ev, 12 + q);
-      }
-    }
 
     float P[2][4];
-    // s_setprio: while a wave is in a matrix phase the SIMD's issue arbiter prefers it to the other wave's close logic
-    // (vector, LDS and store instructions), so its matrix instructions do not queue behind them: -0.9 % on configs[2]
-    // (8.49 -> 8.41 ms same box, priority 1 and 3 alike)
-    PL_TRACE(4);   // (what ran since the end of the previous tile's H1: its barrier excluded below)
+    PL_TRACE(4);  // (what ran since the end of the previous tile's H1: its barrier excluded below)
     matrix_prio(0);
     // ---------------- H0: block 0 of tile t  ||  exponentials of block 1 of tile t-1
     {
@@ -1679,7 +1593,7 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
 #pragma unroll
       for (int j = 0; j < NK16; j++) {
         const int cur = j & 1;
-        if (WIDE && j == JB) {
+        if (WIDE && j == 0) {
           if (group == 1) tile_barrier();
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -1711,9 +1625,9 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
         }
       }
     }
-    if (AASR_PL_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     PL_TRACE(0);
-    if (t > t_begin) commit(P, (GROUPED ? mask_prev : (h ? mask_prev >> 8 : mask_prev)) >> 4 & 0xfu, ep0, ep1);
+    if (t > t_begin) commit(P, (GROUPED ? mask_prev : (h ? mask_prev >> 8 : mask_prev)) >> 4 & 0xfu);
     PL_TRACE(1);
     matrix_prio(1);
     // ---------------- H1: block 1 of tile t  ||  exponentials of block 0 of tile t
@@ -1752,7 +1666,7 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
         }
       }
     }
-    if (AASR_PL_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     PL_TRACE(2);
 #ifdef AASR_PL_TRACE
     tr_tiles++;
@@ -1771,15 +1685,10 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
     const unsigned long long ts1 = __builtin_readcyclecounter();
     tr_sub[0] += ts1 - ts0;   // fragment prefetch (issue)
 #endif
-    commit(P, (GROUPED ? mask_cur : (h ? mask_cur >> 8 : mask_cur)) & 0xfu, en00, en01);
+    commit(P, (GROUPED ? mask_cur : (h ? mask_cur >> 8 : mask_cur)) & 0xfu);
 #ifdef AASR_PL_TRACE
     tr_sub[1] += __builtin_readcyclecounter() - ts1;   // close logic of block 0
 #endif
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      ep0[q] = en10[q];
-      ep1[q] = en11[q];
-    }
     mask_prev = mask_cur;
     bits_prev = bits_cur;
     {
@@ -1793,7 +1702,7 @@ __global__ __launch_bounds__(WIDE ? 512 : 256, WIDE ? 1 : 2) void k_gmm_diag_sco
     float P[2][4];
 #pragma unroll
     for (int k = 0; k < 32; k++) epi_step(k, 1, cB0, cB1, bits_prev, P);
-    commit(P, (GROUPED ? mask_prev : (h ? mask_prev >> 8 : mask_prev)) >> 4 & 0xfu, ep0, ep1);
+    commit(P, (GROUPED ? mask_prev : (h ? mask_prev >> 8 : mask_prev)) >> 4 & 0xfu);
   }
 #ifdef AASR_PL_TRACE
   if ((int)blockIdx.x == AASR_PL_TRACE_BLOCK && lane == 0) {
@@ -2038,50 +1947,49 @@ static void launch_bf16_t(const aasr_gmm *g, const TrackLayout &L, const float *
 
 // The three-term bf16 arithmetic on the pipelined kernel as well, up to 39 dimensions (five slabs: with six the 8-wave
 // instance spills).  Round 3 measured it SLOWER there than on the wave-group kernel (33.2 against 32.4 ms per 10^6 frames);
-// with the wave groups' priorities crossed per phase (AASR_PL_PRIO_SCHEME) it is the faster one: 31.08 against 31.65 ms,
-// two alternating runs on one box.  0: k_gmm_diag_score_bf16x3 for every one-pivot three-term layout.
-#ifndef AASR_PL_BF16X3
-#define AASR_PL_BF16X3 1
-#endif
+// with the wave groups' priorities crossed per phase it is the faster one: 31.08 against 31.65 ms, two alternating runs
+// on one box.  Six and eight slabs stay on k_gmm_diag_score_bf16x3.
+// One launch of instance <..., PGF, HYB> of the pipelined kernel under `plan`: the dynamic LDS size is registered once per
+// device and instance; `fop` / `pg` are what tells the three forms apart (launch_pl_t).
+template <int NK16, bool GROUPED, bool CL, bool WIDE, int NS, bool PGF, bool HYB>
+static void launch_pl_instance(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F, float *d_out,
+                               hipStream_t stream, const ClusterArgs &cl, int64_t pitch, const u32x4 *fop,
+                               const CutPlan &plan, const PivotGroups &pg) {
+  constexpr int NW = WIDE ? 8 : 4;
+  const int smem = PlSmem<NK16, GROUPED, WIDE, NS>::kBytes;
+  static const int dbg = AASR_EXPERIMENT_ENV("AASR_DBG") ? atoi(AASR_EXPERIMENT_ENV("AASR_DBG")) : 0;
+  static bool attr_set[64] = {false};
+  auto kern = k_gmm_diag_score_pl<NK16, GROUPED, CL, WIDE, NS, PGF, HYB>;
+  if (!attr_set[g->device & 63]) {
+    AASR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    attr_set[g->device & 63] = true;
+  }
+  const int32_t *split_row = L.splits.p + (size_t)(plan.r_main - 1) * (L.split_cap + 1) * 4;
+  const unsigned n_items = (unsigned)(plan.n_main + (plan.r_rem ? plan.blocks_rem * plan.r_rem : 0));
+  hipLaunchKernelGGL(kern, dim3(n_items), dim3(NW * 64), smem, stream, d_frames, F,
+                     g->dim, g->d_pivot.p, NS == 3 ? L.a16.p : L.a16h.p, split_row, L.close.p, L.sid.p, L.sid_stride,
+                     d_out, g->S, pitch, L.ref_ln - (float)g->out_bias_ln, dbg, cl, fop, plan, pg);
+  AASR_HIP(hipGetLastError());
+}
+
 template <int NK16, bool GROUPED, bool CL, bool WIDE, int NS>
 static void launch_pl_t(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F,
                         float *d_out, hipStream_t stream, const ClusterArgs &cl, int64_t pitch) {
   constexpr int NW = WIDE ? 8 : 4;
   const int64_t blocks = (F + NW * FRAMES_PER_WAVE - 1) / (NW * FRAMES_PER_WAVE);
-  const int smem = PlSmem<NK16, GROUPED, WIDE, NS>::kBytes;
-  static const int dbg = AASR_EXPERIMENT_ENV("AASR_DBG") ? atoi(AASR_EXPERIMENT_ENV("AASR_DBG")) : 0;
-  static bool attr_set[64] = {false};
-  auto kern = k_gmm_diag_score_pl<NK16, GROUPED, CL, WIDE, NS>;
-  if (!attr_set[g->device & 63]) {
-    AASR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    attr_set[g->device & 63] = true;
-  }
-  const int32_t *splits_base = L.splits.p;
   const bool multi = L.n_pg > 1;   // pivot groups: every group at least one cut, its own frame operand
-  const int cap = L.split_cap;   // rows of the cut table
   const CutPlan plan = pick_cut_plan(blocks, (WIDE ? 1.0 : 2.0) * (g->num_cus > 0 ? g->num_cus : 256),
-                                     L.rows_padded / TILE_ROWS, L.max_splits, 3.0, splits_base, multi ? L.n_pg : 1, cap);
-  const int32_t *split_row = splits_base + (size_t)(plan.r_main - 1) * (cap + 1) * 4;
+                                     L.rows_padded / TILE_ROWS, L.max_splits, 3.0, L.splits.p, multi ? L.n_pg : 1, L.split_cap);
   PivotGroups pg;
-  const unsigned n_items = (unsigned)(plan.n_main + (plan.r_rem ? plan.blocks_rem * plan.r_rem : 0));
   if constexpr (GROUPED && NS == 2) {
     // multi-pivot layouts: the workgroups form their group's frame operand themselves (no k_frame_operand launch)
     static const int pgf_env = AASR_EXPERIMENT_ENV("AASR_PGF") ? atoi(AASR_EXPERIMENT_ENV("AASR_PGF")) : 1;   // EXPERIMENT: 0 = images through HBM
     if (multi && pgf_env && L.pg_tab.p) {
-      auto kern_pgf = k_gmm_diag_score_pl<NK16, GROUPED, CL, WIDE, NS, false, true>;
-      static bool attr_set_pgf[64] = {false};
-      if (!attr_set_pgf[g->device & 63]) {
-        AASR_HIP(hipFuncSetAttribute((const void *)kern_pgf, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set_pgf[g->device & 63] = true;
-      }
       pg.colend = L.pg_colend.p;
       pg.pivots = L.pg_pivot.p;
       pg.tabs = L.pg_tab.p;
       pg.sc = L.sc ? 1 : 0;
-      hipLaunchKernelGGL(kern_pgf, dim3(n_items), dim3(NW * 64), smem, stream, d_frames, F,
-                         g->dim, g->d_pivot.p, L.a16h.p, split_row, L.close.p, L.sid.p, L.sid_stride,
-                         d_out, g->S, pitch, L.ref_ln - (float)g->out_bias_ln, dbg, cl, (const u32x4 *)nullptr, plan, pg);
-      AASR_HIP(hipGetLastError());
+      launch_pl_instance<NK16, GROUPED, CL, WIDE, NS, true, false>(g, L, d_frames, F, d_out, stream, cl, pitch, nullptr, plan, pg);
       return;
     }
   }
@@ -2090,30 +1998,17 @@ static void launch_pl_t(const aasr_gmm *g, const TrackLayout &L, const float *d_
   if constexpr (GROUPED && NS == 2 && !CL) {
     // outlier routing with the merge in the close logic: the launcher has put the outliers' partial sums on the handle
     if (!multi && g->hyb_fuse.part && g->hyb_tab.p) {
-      auto kern_hyb = k_gmm_diag_score_pl<NK16, GROUPED, CL, WIDE, NS, false, false, true>;
-      static bool attr_set_hyb[64] = {false};
-      if (!attr_set_hyb[g->device & 63]) {
-        AASR_HIP(hipFuncSetAttribute((const void *)kern_hyb, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set_hyb[g->device & 63] = true;
-      }
       pg.hyb_tab = g->hyb_tab.p;
       pg.hyb_part = g->hyb_fuse.part;
       pg.hyb_pitch = g->hyb_fuse.pitch;
       pg.hyb_bias = (float)g->out_bias_ln;
       g->hyb_fuse.used = true;   // (the callers run the merge pass where no launch took the partial sums)
       g->hyb_fused_launches++;
-      hipLaunchKernelGGL(kern_hyb, dim3(n_items), dim3(NW * 64), smem, stream, d_frames, F,
-                         g->dim, g->d_pivot.p, L.a16h.p, split_row, L.close.p, L.sid.p, L.sid_stride,
-                         d_out, g->S, pitch, L.ref_ln - (float)g->out_bias_ln, dbg, cl, fop, plan, pg);
-      AASR_HIP(hipGetLastError());
+      launch_pl_instance<NK16, GROUPED, CL, WIDE, NS, false, true>(g, L, d_frames, F, d_out, stream, cl, pitch, fop, plan, pg);
       return;
     }
   }
-  hipLaunchKernelGGL(kern, dim3(n_items), dim3(NW * 64), smem, stream, d_frames, F,
-                     g->dim, g->d_pivot.p, NS == 3 ? L.a16.p : L.a16h.p, split_row, L.close.p,
-                     L.sid.p, L.sid_stride,
-                     d_out, g->S, pitch, L.ref_ln - (float)g->out_bias_ln, dbg, cl, fop, plan, pg);
-  AASR_HIP(hipGetLastError());
+  launch_pl_instance<NK16, GROUPED, CL, WIDE, NS, false, false>(g, L, d_frames, F, d_out, stream, cl, pitch, fop, plan, pg);
 }
 
 // the 8-wave form needs three tile buffers + eight staging areas in 160 KB of LDS
@@ -2125,55 +2020,65 @@ static constexpr bool wide_ok() {
          PlSmem<N, true, true, NS>::kBytes <= 160 * 1024;
 }
 
-// NS = 3: three bf16 terms (AASR_PREC_BF16X3) on the wave-group kernel; NS = 2: two fp16 terms (AASR_PREC_F16X2) on
-// the software-pipelined kernel
+// One instance choice of launch_split: NS = 2 and three terms up to five slabs on the software-pipelined kernel, three
+// terms beyond on the wave-group kernel -- or, on a multi-pivot layout (grouped by construction), on the pipelined one,
+// which takes the groups' operand images
+template <int N, int NS, bool GR, bool CLF, bool WD>
+static void launch_split_instance(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F, float *d_out,
+                                  hipStream_t stream, const ClusterArgs &cl, int64_t pitch) {
+  if constexpr (NS == 2 || N <= 5)
+    launch_pl_t<N, GR, CLF, WD, NS>(g, L, d_frames, F, d_out, stream, cl, pitch);
+  else if (L.n_pg > 1) {
+    if constexpr (GR) launch_pl_t<N, true, CLF, WD, NS>(g, L, d_frames, F, d_out, stream, cl, pitch);
+  } else
+    launch_bf16_t<N, GR, CLF, WD, NS>(g, L, d_frames, F, d_out, stream, cl, pitch);
+}
+
+// GROUPED from the layout
+template <int N, int NS, bool CLF, bool WD>
+static void launch_split_tracks(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F, float *d_out,
+                                hipStream_t stream, const ClusterArgs &cl, int64_t pitch) {
+  if (L.grouped) launch_split_instance<N, NS, true, CLF, WD>(g, L, d_frames, F, d_out, stream, cl, pitch);
+  else launch_split_instance<N, NS, false, CLF, WD>(g, L, d_frames, F, d_out, stream, cl, pitch);
+}
+
+// CL from the masks, WIDE from the batch size and the LDS budget
+template <int N, int NS>
+static void launch_split_n(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F, float *d_out,
+                           hipStream_t stream, const ClusterArgs *cl, int64_t pitch, bool wide) {
+  const ClusterArgs none;
+  if (cl && NS == 2 && wide && wide_ok<N, NS>()) {
+    // masked (clustered) runs: the bf16x3 8-wave form with masks needs 254 VGPRs + spills and was measured slower, so it
+    // keeps 4-wave workgroups; the f16x2 kernel has the registers
+    if constexpr (NS == 2) launch_split_tracks<N, NS, true, true>(g, L, d_frames, F, d_out, stream, *cl, pitch);
+  } else if (cl) {
+    launch_split_tracks<N, NS, true, false>(g, L, d_frames, F, d_out, stream, *cl, pitch);
+  } else if (wide && wide_ok<N, NS>()) {
+    launch_split_tracks<N, NS, false, true>(g, L, d_frames, F, d_out, stream, none, pitch);
+  } else {
+    launch_split_tracks<N, NS, false, false>(g, L, d_frames, F, d_out, stream, none, pitch);
+  }
+}
+
+// NS = 3: three bf16 terms (AASR_PREC_BF16X3); NS = 2: two fp16 terms (AASR_PREC_F16X2)
 template <int NS>
 static bool launch_split(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F,
                          float *d_out, hipStream_t stream, const ClusterArgs *cl = nullptr, int64_t pitch = 0) {
   if (pitch <= 0) pitch = g->S;
   if (NS == 3 ? !L.a16.p : !L.a16h.p) return false;
-  const bool grouped = L.grouped;
-  const ClusterArgs none;
   // AASR_BF16_WIDE=0 selects the 4-wave workgroups
   static const int wide_env = AASR_EXPERIMENT_ENV("AASR_BF16_WIDE") ? atoi(AASR_EXPERIMENT_ENV("AASR_BF16_WIDE")) : -1;
   // small batches (a decoder's per-utterance blocks) fill the chip better with 256-frame workgroups
-  const int wide = wide_env >= 0 ? wide_env : (F >= 8192 ? 1 : 0);
+  const bool wide = (wide_env >= 0 ? wide_env : (F >= 8192 ? 1 : 0)) != 0;
   switch (L.nk16) {
-#define AASR_LAUNCH(N, GR, CLF, WD, CLA)                                                   \
-  do {                                                                                     \
-    if constexpr (NS == 2 || (AASR_PL_BF16X3 && N <= 5))                                   \
-      launch_pl_t<N, GR, CLF, WD, NS>(g, L, d_frames, F, d_out, stream, CLA, pitch);        \
-    else if (L.n_pg > 1) {                                                                  \
-      /* three bf16 terms on a multi-pivot layout: the pipelined kernel takes the groups' operand images */ \
-      if constexpr (GR) launch_pl_t<N, true, CLF, WD, NS>(g, L, d_frames, F, d_out, stream, CLA, pitch); \
-    } else                                                                                 \
-      launch_bf16_t<N, GR, CLF, WD, NS>(g, L, d_frames, F, d_out, stream, CLA, pitch);      \
-  } while (0)
-#define AASR_CASE(N)                                                                       \
-  case N:                                                                                  \
-    if (cl && NS == 2 && wide && wide_ok<N, NS>()) {                                       \
-      /* masked (clustered) runs: the bf16x3 8-wave form with masks needs 254 VGPRs + spills and was */ \
-      /* measured slower, so it keeps 4-wave workgroups; the f16x2 kernel has the registers          */ \
-      if constexpr (NS == 2) {                                                             \
-        if (grouped) AASR_LAUNCH(N, true, true, true, *cl);                                \
-        else AASR_LAUNCH(N, false, true, true, *cl);                                       \
-      }                                                                                    \
-    } else if (cl) {                                                                       \
-      if (grouped) AASR_LAUNCH(N, true, true, false, *cl);                                 \
-      else AASR_LAUNCH(N, false, true, false, *cl);                                        \
-    } else if (wide && wide_ok<N, NS>()) {                                                 \
-      if (grouped) AASR_LAUNCH(N, true, false, true, none);                                \
-      else AASR_LAUNCH(N, false, false, true, none);                                       \
-    } else {                                                                               \
-      if (grouped) AASR_LAUNCH(N, true, false, false, none);                               \
-      else AASR_LAUNCH(N, false, false, false, none);                                      \
-    }                                                                                      \
-    return true;
-    AASR_CASE(1) AASR_CASE(2) AASR_CASE(3) AASR_CASE(4) AASR_CASE(5) AASR_CASE(6) AASR_CASE(8)
-#undef AASR_CASE
-#undef AASR_LAUNCH
-    default:
-      return false;
+    case 1: launch_split_n<1, NS>(g, L, d_frames, F, d_out, stream, cl, pitch, wide); return true;
+    case 2: launch_split_n<2, NS>(g, L, d_frames, F, d_out, stream, cl, pitch, wide); return true;
+    case 3: launch_split_n<3, NS>(g, L, d_frames, F, d_out, stream, cl, pitch, wide); return true;
+    case 4: launch_split_n<4, NS>(g, L, d_frames, F, d_out, stream, cl, pitch, wide); return true;
+    case 5: launch_split_n<5, NS>(g, L, d_frames, F, d_out, stream, cl, pitch, wide); return true;
+    case 6: launch_split_n<6, NS>(g, L, d_frames, F, d_out, stream, cl, pitch, wide); return true;
+    case 8: launch_split_n<8, NS>(g, L, d_frames, F, d_out, stream, cl, pitch, wide); return true;
+    default: return false;
   }
 }
 
@@ -2732,16 +2637,13 @@ __global__ __launch_bounds__(256, 2) void k_gmm_full_score_bf16x3(
   }
 }
 
-template <int NK16, int NS = 3, bool CL = false>
-static void launch_full_bf16_t(const aasr_gmm *g, const float *d_frames, int64_t F, float *d_out,
-                               hipStream_t stream, const ClusterArgs &cl = ClusterArgs()) {
-  const FullLayout &L = g->full;
-  const int64_t blocks = (F + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK;
-  const int smem = 2 * NK16 * NS * 2 * 64 * 16;
+// Row-range cuts of a full-covariance launch: the number of cuts that leaves the smallest tail round on the chip (two
+// workgroups per CU resident), preferring fewer cuts
+static int pick_full_cuts(const aasr_gmm *g, int64_t blocks) {
   const double slots = 2.0 * (g->num_cus > 0 ? g->num_cus : 256);
   int R = 1;
   double best_eff = 0;
-  for (int r = 1; r <= L.max_splits; r++) {
+  for (int r = 1; r <= g->full.max_splits; r++) {
     double x = (double)blocks * r / slots;
     double eff = x / std::ceil(x);
     if (x < 1.0) eff = x;
@@ -2750,6 +2652,16 @@ static void launch_full_bf16_t(const aasr_gmm *g, const float *d_frames, int64_t
       R = r;
     }
   }
+  return R;
+}
+
+template <int NK16, int NS = 3, bool CL = false>
+static void launch_full_bf16_t(const aasr_gmm *g, const float *d_frames, int64_t F, float *d_out,
+                               hipStream_t stream, const ClusterArgs &cl = ClusterArgs()) {
+  const FullLayout &L = g->full;
+  const int64_t blocks = (F + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK;
+  const int smem = 2 * NK16 * NS * 2 * 64 * 16;
+  const int R = pick_full_cuts(g, blocks);
   const int32_t *split_row = L.splits.p + (size_t)(R - 1) * (TRACK_MAX_SPLITS + 1) * 8;
   hipLaunchKernelGGL((k_gmm_full_score_bf16x3<NK16, NS, CL>), dim3((unsigned)blocks, (unsigned)R), dim3(256), smem,
                      stream, d_frames, F, g->dim, g->d_pivot.p, NS == 2 ? L.a16h.p : L.a16.p, split_row, L.close.p,
@@ -2763,18 +2675,7 @@ static void launch_full_t(const aasr_gmm *g, const float *d_frames, int64_t F, f
   const FullLayout &L = g->full;
   const int64_t blocks = (F + FRAMES_PER_BLOCK - 1) / FRAMES_PER_BLOCK;
   const int smem = 2 * (NKK / 2) * 64 * 4 * 4;
-  const double slots = 2.0 * (g->num_cus > 0 ? g->num_cus : 256);
-  int R = 1;
-  double best_eff = 0;
-  for (int r = 1; r <= L.max_splits; r++) {
-    double x = (double)blocks * r / slots;
-    double eff = x / std::ceil(x);
-    if (x < 1.0) eff = x;
-    if (eff > best_eff + 0.005) {
-      best_eff = eff;
-      R = r;
-    }
-  }
+  const int R = pick_full_cuts(g, blocks);
   const int32_t *split_row = L.splits.p + (size_t)(R - 1) * (TRACK_MAX_SPLITS + 1) * 8;
   hipLaunchKernelGGL((k_gmm_full_score<NKK, CL>), dim3((unsigned)blocks, (unsigned)R), dim3(256), smem, stream,
                      d_frames, F, g->dim, g->d_pivot.p, L.rows.a.p, split_row, L.close.p, L.gconst.p,
