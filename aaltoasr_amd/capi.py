@@ -1109,6 +1109,18 @@ class Stats:
         check(lib().aasr_stats_accumulate_dev(self._h, _ptr(d_frames), len(p), _ptr(p), _ptr(d_frame_ll),
                                               _stream_handle(stream)))
 
+    def launch_shape(self) -> dict:
+        """Diagnostic: the shape of the accumulation kernel's launch in the last accumulate_dev call that launched it
+        (zeros before the first): its dimension instance, frames per sub-block, whether the mixture records were staged
+        in LDS, the model's largest mixture and the work items."""
+        L = lib()
+        L.aasr_debug_stats_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.aasr_debug_stats_shape.restype = None
+        out = (C.c_int32 * 5)()
+        L.aasr_debug_stats_shape(self._h, out)
+        return {"dimp": int(out[0]), "block": int(out[1]), "lds_recs": int(out[2]), "max_comps": int(out[3]),
+                "items": int(out[4])}
+
     def add_transitions(self, transition) -> None:
         t = np.ascontiguousarray(transition, np.int32)
         check(lib().aasr_stats_add_transitions(self._h, _ptr(t), len(t)))

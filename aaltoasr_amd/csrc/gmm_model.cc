@@ -2573,7 +2573,10 @@ void gmm_build_f64(aasr_gmm *g) {
   if (g->f64_built) return;
   const HostModel &m = g->host;
   const int D = m.dim;
-  // the frame vector lives in registers as doubles: instances up to 192 dimensions (384 of a lane's 512 VGPRs)
+  // the frame vector is a per-lane array of doubles, instances up to 192 dimensions.  What the compiler makes of it in
+  // k_stats_items (code object notes, tests/test_kernel_notes.py): in registers without scratch up to <128> (255 VGPRs
+  // at <96>, 256 + 82 AGPRs at <128>); <192> would need 384 for the frame alone, takes all 512 (256 + 256 AGPRs) and
+  // still spills 97 VGPRs, 248 bytes of scratch per lane
   const int dimp = D <= 64 ? centred_dimp_for(D) : D <= 96 ? 96 : D <= 128 ? 128 : D <= 192 ? 192 : 0;
   if (!dimp) raise(AASR_ERR_UNSUPPORTED, "no f64 kernel instance for dimension %d", D);
   const int rec = 2 * dimp + 2;

@@ -150,6 +150,8 @@ struct aasr_stats {
   std::vector<StatsItem> h_items;
   hipEvent_t staged = nullptr;
   bool staged_pending = false;
+  // shape of the last launch of the item kernel (aasr_debug_stats_shape): dimp, block, lds_recs, max_comps, items
+  int32_t last_shape[5] = {0, 0, 0, 0, 0};
   // host copies after aasr_stats_fetch
   bool fetched = false;
   std::vector<double> h_racc, h_pacc, h_gacc;
@@ -167,6 +169,18 @@ static void check_stats_model(const aasr_gmm *g) {
     raise(AASR_ERR_UNSUPPORTED, "stats: subspace Gaussians are not supported (diagonal pools only)");
   if (g->host.n_transforms > 0)
     raise(AASR_ERR_UNSUPPORTED, "stats: model-side transforms (cmllr) are not supported");
+}
+
+// The item kernel's shape for a model whose largest mixture has max_comps components of rec doubles a record.
+// Sub-block: as many frames as the posteriors of the largest mixture allow in 48 KB of LDS, 64 at least (60 KB then,
+// beyond that the model is refused); the mixture's records are staged in LDS where 64 KB hold them as well.
+static void stats_launch_shape(int max_comps, int rec, int32_t *block, int32_t *lds_recs) {
+  int b = STATS_THREADS;
+  while (b > 64 && (size_t)b * (max_comps + 2) * 8 > 48 * 1024) b -= 64;
+  if ((size_t)b * (max_comps + 2) * 8 > 60 * 1024)
+    raise(AASR_ERR_UNSUPPORTED, "stats: mixtures of %d components exceed the accumulation kernel's LDS", max_comps);
+  *block = b;
+  *lds_recs = (size_t)(b * (max_comps + 2) + max_comps * rec) * 8 + (size_t)b * 8 <= 64 * 1024 ? 1 : 0;
 }
 
 }  // namespace aasr
@@ -197,6 +211,10 @@ aasr_status aasr_stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats *
     gmm_build_f64(gmm);
     h->dimp = gmm->f64_dimp ? gmm->f64_dimp : 0;
     h->rec = 2 * h->dimp + 2;
+    {  // a model no launch shape holds is refused here, where it is known, not at its first frames
+      int32_t block, lds_recs;
+      stats_launch_shape(h->max_comps, h->rec, &block, &lds_recs);
+    }
     // transitions in HmmSet::read_ph order
     TopoTables tt(topo);
     for (size_t s = 0; s < tt.offsets.size(); s++)
@@ -231,6 +249,14 @@ aasr_status aasr_stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats *
 void aasr_stats_destroy(aasr_stats *h) { delete h; }
 
 int32_t aasr_stats_num_transitions(const aasr_stats *h) { return h ? (int32_t)h->tr_source.size() : -1; }
+
+// Diagnostic: the shape of the item kernel's launch in the last aasr_stats_accumulate_dev call that launched one --
+// out[0] the dimension instance (dimp), out[1] frames per sub-block, out[2] 1 when the records were staged in LDS,
+// out[3] the largest mixture, out[4] the number of work items; zeros before the first launch
+void aasr_debug_stats_shape(const aasr_stats *h, int32_t *out) {
+  if (!h || !out) return;
+  std::copy(h->last_shape, h->last_shape + 5, out);
+}
 
 aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int64_t n_frames, const int32_t *pdf,
                                       double *d_frame_ll, void *stream) {
@@ -278,15 +304,10 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
       h->h_item_begin.push_back((int32_t)h->h_items.size());
     }
     if (h->h_items.empty()) return;
-    // sub-block: as many frames as the posteriors of the largest mixture allow in LDS
     StatsParams p{};
     p.max_comps = h->max_comps;
     p.rec = h->rec;
-    p.block = STATS_THREADS;
-    while (p.block > 64 && (size_t)p.block * (p.max_comps + 2) * 8 > 48 * 1024) p.block -= 64;
-    if ((size_t)p.block * (p.max_comps + 2) * 8 > 60 * 1024)
-      raise(AASR_ERR_UNSUPPORTED, "stats: mixtures of %d components exceed the accumulation kernel's LDS", p.max_comps);
-    p.lds_recs = (size_t)(p.block * (p.max_comps + 2) + p.max_comps * p.rec) * 8 + (size_t)p.block * 8 <= 64 * 1024 ? 1 : 0;
+    stats_launch_shape(p.max_comps, p.rec, &p.block, &p.lds_recs);
     h->d_rows.ensure(h->h_rows.size());
     h->d_items.ensure(h->h_items.size());
     h->d_pdfs.ensure(h->h_pdfs.size());
@@ -308,6 +329,8 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
     p.state_off = h->gmm->f64_state_off.p;
     p.slab = h->slab.p;
     p.frame_ll = d_frame_ll;
+    const int32_t shape[5] = {h->dimp, p.block, p.lds_recs, p.max_comps, (int32_t)h->h_items.size()};
+    std::copy(shape, shape + 5, h->last_shape);
     stats_items_launch(p, h->dimp, (int)h->h_items.size(), st);
     stats_pdf_reduce_launch(h->d_pdfs.p, h->d_item_begin.p, (int)h->h_pdfs.size(), h->d_items.p, h->slab.p,
                             h->gmm->f64_state_off.p, h->D, h->racc.p, h->pacc.p, st);
@@ -613,7 +636,10 @@ extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, con
       if (u.start_line > 0 || u.end_line > 0)
         raise(AASR_ERR_UNSUPPORTED, "stats: recipe line limits (start-line / end-line) are not supported");
     aasr_stats *h = nullptr;
-    if (aasr_stats_create(gmm, topo, &h) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+    {  // (a model the accumulation kernel has no shape for keeps its AASR_ERR_UNSUPPORTED)
+      const aasr_status cs = aasr_stats_create(gmm, topo, &h);
+      if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
+    }
     std::unique_ptr<aasr_stats, void (*)(aasr_stats *)> hguard(h, aasr_stats_destroy);
     const TopoTables tt(topo);
     const float fr = aasr_feat_frame_rate(feat);

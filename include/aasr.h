@@ -725,6 +725,11 @@ aasr_status aasr_stats_gaussians(const aasr_stats *h, int64_t *feacount, double 
 aasr_status aasr_stats_mixtures(const aasr_stats *h, int64_t *count, double *gamma, double *mixture_ll);
 int32_t aasr_stats_num_transitions(const aasr_stats *h);
 aasr_status aasr_stats_transitions(const aasr_stats *h, int32_t *source, int32_t *target_offset, double *count);
+/* Diagnostic, read-only: the launch shape of the last aasr_stats_accumulate_dev call that reached the
+ * accumulation kernel -- out[0] the kernel's dimension instance, out[1] frames per sub-block (256, 192,
+ * 128 or 64), out[2] 1 when the mixture records were staged in LDS, out[3] the model's largest mixture,
+ * out[4] work items launched.  Five zeros before the first such call. */
+void aasr_debug_stats_shape(const aasr_stats *h, int32_t *out);
 /* after a fetch: base.phs, base.mcs, base.gks */
 aasr_status aasr_stats_write(const aasr_stats *h, const char *base);
 

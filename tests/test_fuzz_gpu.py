@@ -134,3 +134,17 @@ def test_fitted_model_sweep(capi, oracle, seed, n):
     worst, fails = _load("fuzz_fitted").run(seed, n)
     assert not fails, "\n".join(fails)
     assert worst.get("n parts", 0) >= 3 and worst.get("lna code steps", 0) <= 1
+
+
+@pytest.mark.parametrize("seed,n", [(1, 12), (5, 12)])
+def test_stats_sweep(capi, oracle, seed, n):
+    """tools/fuzz_stats.py: the statistics handle on random models of 1 ... 192 dimensions and largest mixtures of 0 ... 118
+    (ragged, tied, zero weights), 0 to a few thousand frames per pdf, skipped frames, uneven call cuts, against the
+    in-order restatement in double with the tolerances of tests/test_stats_gpu.py.  The seeds' sizes were chosen from the
+    models' shapes alone (fuzz_stats.shapes_of: both draw all four sub-block sizes); the shapes that ran are asserted."""
+    mod = _load("fuzz_stats")
+    worst, fails = mod.run(seed, n)
+    assert not fails, "\n".join(fails)
+    assert worst["shapes"] == mod.shapes_of(seed, n)
+    assert len({s[1] for s in worst["shapes"]}) >= 3 and {s[2] for s in worst["shapes"]} == {0, 1}
+    assert len({s[0] for s in worst["shapes"]}) >= 5

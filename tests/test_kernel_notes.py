@@ -70,3 +70,42 @@ def test_feature_kernels_keep_four_waves_per_simd():
     for name in ("k_temporal_fused<64, 512>", "k_mean_subtract_tiled<128, float, 512>", "k_mean_subtract_tiled<64, float, 256>"):
         hits = [v for k, v in notes.items() if k.endswith(name)]
         assert len(hits) == 1 and hits[0]["scratch"] == 0 and hits[0]["spill_vgpr"] == 0 and hits[0]["vgpr"] <= 128, (name, hits)
+
+
+# ---- the statistics accumulation kernel (csrc/stats_accum.hip) ----------------------------------------------------
+# k_stats_items<DIMP> holds a frame as DIMP doubles per lane (2 DIMP VGPRs) next to its running sums; one instance per
+# padded dimension of gmm_build_f64.
+
+STATS_DIMS = (8, 16, 24, 32, 40, 48, 64, 96, 128, 192)
+
+
+@pytest.fixture(scope="module")
+def stats_notes(capi):
+    import kernel_notes
+    obj = os.path.join(ROOT, "aaltoasr_amd", "lib", "obj", "stats_accum.hip.o")
+    assert os.path.exists(obj)
+    notes = kernel_notes.kernel_notes(obj)
+    return {n: _get(notes, "k_stats_items<%d>" % n) for n in STATS_DIMS}
+
+
+def test_stats_instances_up_to_128_have_no_scratch(stats_notes):
+    for n in STATS_DIMS[:-1]:
+        k = stats_notes[n]
+        assert k["scratch"] == 0 and k["spill_vgpr"] == 0, (n, k)
+        assert k["vgpr"] <= 512, (n, k)     # the unified file of a 256-thread workgroup (338 at <128> when written)
+
+
+def test_stats_instances_of_real_front_ends_stay_in_plain_vgprs(stats_notes):
+    """24 ... 48 padded dimensions (the 39-dimensional front end runs <40>): no scratch, no spilled VGPR, no AGPR
+    copies, and at most 168 VGPRs -- three waves per SIMD (111 / 127 / 143 / 160 when this was written)."""
+    for n in (24, 32, 40, 48):
+        k = stats_notes[n]
+        assert k["scratch"] == 0 and k["spill_vgpr"] == 0 and k["agpr"] == 0 and k["vgpr"] <= 168, (n, k)
+
+
+def test_stats_192_spill_does_not_grow(stats_notes):
+    """<192> is the one instance that spills: its frame alone is 384 VGPRs, the notes say 512 registers (256 + 256
+    AGPRs), 97 spilled VGPRs and 248 bytes of scratch per lane ("ML statistics").  It is correct as it is
+    (tests/test_stats_shapes_gpu.py runs it); this keeps the spill from growing unnoticed.  Less is welcome."""
+    k = stats_notes[192]
+    assert k["scratch"] <= 248 and k["spill_vgpr"] <= 97, k
