@@ -145,6 +145,20 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_stats_default_options.argtypes = [vp]
     L.aasr_stats_default_options.restype = None
     L.aasr_run_stats_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
+    # CMLLR estimation
+    L.aasr_mllr_create.argtypes = [vp, pvp]
+    L.aasr_mllr_destroy.argtypes = [vp]
+    L.aasr_mllr_destroy.restype = None
+    L.aasr_mllr_reset.argtypes = [vp, vp]
+    L.aasr_mllr_accumulate_dev.argtypes = [vp, vp, i64, vp, vp]
+    L.aasr_mllr_fetch.argtypes = [vp, vp]
+    L.aasr_mllr_get.argtypes = [vp, vp, vp, C.POINTER(d)]
+    L.aasr_mllr_solve.argtypes = [i32, vp, vp, d, vp]
+    L.aasr_mllr_compose.argtypes = [i32, vp, vp, vp, vp, vp]
+    L.aasr_mllr_default_options.argtypes = [vp]
+    L.aasr_mllr_default_options.restype = None
+    L.aasr_run_mllr_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
+    L.aasr_spkc_write_text.argtypes = [vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(i64)]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
     L.aasr_set_device.argtypes = [C.c_int]
@@ -852,6 +866,22 @@ class SpeakerConfig:
     def num_changes(self) -> int:
         return lib().aasr_spkc_num_changes(self._h)
 
+    def write_text(self, speakers=None, utterances=None) -> str:
+        """SpeakerConfig::write_speaker_file as text; speakers / utterances: lists of ids to keep (None: all)."""
+        def arr(ids):
+            if ids is None:
+                return None, -1
+            a = (C.c_char_p * max(1, len(ids)))(*[i.encode() for i in ids])
+            return a, len(ids)
+        sp, n_sp = arr(speakers)
+        ut, n_ut = arr(utterances)
+        out, n = C.c_void_p(), C.c_int64()
+        check(lib().aasr_spkc_write_text(self._h, sp, n_sp, ut, n_ut, C.byref(out), C.byref(n)))
+        try:
+            return C.string_at(out, n.value).decode()
+        finally:
+            lib().aasr_free(out)
+
 
 def run_recipe(feat: Feat, gmm: Gmm, recipe_path: str, lnabytes: int = 2, normalize: bool = True,
                num_batches: int = 0, batch_index: int = 0, no_overwrite: bool = False,
@@ -1157,4 +1187,89 @@ def run_stats_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str,
     opts.out = ob
     st = RunStats()
     check(lib().aasr_run_stats_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}
+
+
+# ---- CMLLR estimation ---------------------------------------------------------------------------
+
+class MllrOptions(C.Structure):
+    """aasr_mllr_options: mllr's options (aku/mllr.cc:153-180) for global transforms over .phn files."""
+    _fields_ = [("ophn", C.c_int32), ("info", C.c_int32), ("num_batches", C.c_int32), ("batch_index", C.c_int32),
+                ("minframes", C.c_double), ("module", C.c_char_p), ("speakers", C.c_void_p), ("out", C.c_char_p)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "MllrOptions":
+        o = cls()
+        lib().aasr_mllr_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+class Mllr:
+    """Owner of an aasr_mllr handle: the CMLLR statistics G, k, beta of the current speaker, on the device."""
+
+    def __init__(self, gmm: "Gmm"):
+        h = C.c_void_p()
+        check(lib().aasr_mllr_create(gmm._h, C.byref(h)))
+        self._h = h.value
+        self.D = gmm.dim
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_mllr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None) -> None:
+        check(lib().aasr_mllr_reset(self._h, _stream_handle(stream)))
+
+    def accumulate_dev(self, d_frames, pdf, stream=None) -> None:
+        """d_frames: a float64 device tensor [n x dim]; pdf: host int32 per frame (-1: skip)."""
+        p = np.ascontiguousarray(pdf, np.int32)
+        check(lib().aasr_mllr_accumulate_dev(self._h, _ptr(d_frames), len(p), _ptr(p), _stream_handle(stream)))
+
+    def fetch(self, stream=None):
+        """Waits for the device; -> G [dim][dim + 1][dim + 1], k [dim][dim + 1], beta."""
+        L = lib()
+        check(L.aasr_mllr_fetch(self._h, _stream_handle(stream)))
+        D = self.D
+        G, k, beta = np.zeros((D, D + 1, D + 1)), np.zeros((D, D + 1)), C.c_double()
+        check(L.aasr_mllr_get(self._h, _ptr(G), _ptr(k), C.byref(beta)))
+        return G, k, beta.value
+
+
+def mllr_solve(G, k, beta: float):
+    """MllTrainerComponent::calculate_transform (host only): W [dim][dim + 1], column 0 the bias."""
+    G, k = np.ascontiguousarray(G, np.float64), np.ascontiguousarray(k, np.float64)
+    D = k.shape[0]
+    W = np.zeros((D, D + 1))
+    check(lib().aasr_mllr_solve(D, _ptr(G), _ptr(k), float(beta), _ptr(W)))
+    return W
+
+
+def mllr_compose(W, old_A=None, old_b=None):
+    """MllrTrainer::calculate_transform(LinTransformModule *) (host only): -> float32 A [dim x dim], b [dim]."""
+    W = np.ascontiguousarray(W, np.float64)
+    D = W.shape[0]
+    A, b = np.zeros((D, D), np.float32), np.zeros(D, np.float32)
+    oa = np.ascontiguousarray(old_A, np.float32) if old_A is not None else None
+    ob = np.ascontiguousarray(old_b, np.float32) if old_b is not None else None
+    check(lib().aasr_mllr_compose(D, _ptr(W), _ptr(oa), _ptr(ob), _ptr(A), _ptr(b)))
+    return A, b
+
+
+def run_mllr_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str, speakers: SpeakerConfig,
+                    out: Optional[str] = None, module: Optional[str] = None,
+                    opts: Optional[MllrOptions] = None) -> dict:
+    opts = opts or MllrOptions.defaults()
+    ob, mb = (out.encode() if out else None), (module.encode() if module else None)
+    opts.out, opts.module, opts.speakers = ob, mb, speakers._h
+    st = RunStats()
+    check(lib().aasr_run_mllr_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}

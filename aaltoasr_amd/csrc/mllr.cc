@@ -1,0 +1,609 @@
+// mllr.cc -- constrained MLLR estimation (aku/mllr.cc, aku/MllrTrainer.cc): the statistics handle that drives the
+// device accumulation (mllr_accum.hip), the host solver of MllTrainerComponent::calculate_transform /
+// calculate_alpha (MllrTrainer.cc:165-253) in double with its own LU, and the mllr main loop over a recipe
+// (aasr_run_mllr_recipe, mllr.cc:54-71, 126-145, 213-332).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <memory>
+#include <set>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "feat.h"
+#include "gmm.h"
+#include "mllr.h"
+#include "pipeline.h"
+
+using namespace aasr;
+
+// ---- the statistics handle ---------------------------------------------------------------------
+
+struct aasr_mllr {
+  aasr_gmm *gmm = nullptr;
+  int D = 0, S = 0, max_comps = 0;
+  int64_t SL = 0;  // doubles of the accumulator and of one slab
+  DevBuf<double> inv_var, mean_var, w, u, slab, acc;
+  DevBuf<int32_t> d_pdf, ok;
+  std::vector<int32_t> h_pdf;  // host staging of the last call's pdfs, kept until their upload is done
+  hipEvent_t staged = nullptr;
+  bool staged_pending = false;
+  bool fetched = false;
+  std::vector<double> h_acc;
+  ~aasr_mllr() {
+    if (staged) (void)hipEventDestroy(staged);
+  }
+};
+
+namespace aasr {
+
+static void check_mllr_model(const aasr_gmm *g) {
+  if (g->host.any_full() || !g->host.gauss_bias.empty())
+    raise(AASR_ERR_UNSUPPORTED, "mllr: full-covariance and subspace Gaussians are not supported (diagonal pools only)");
+  if (g->host.n_transforms > 0)
+    raise(AASR_ERR_UNSUPPORTED, "mllr: the statistics are collected on the unadapted model (a model transform is loaded)");
+}
+
+}  // namespace aasr
+
+extern "C" {
+
+aasr_status aasr_mllr_create(aasr_gmm *gmm, aasr_mllr **out) {
+  return guarded([&] {
+    if (!gmm || !out) raise(AASR_ERR_INVALID, "aasr_mllr_create: null argument");
+    *out = nullptr;
+    check_mllr_model(gmm);
+    const HostModel &m = gmm->host;
+    if (m.dim < 1 || m.dim > MLLR_MAX_DIM)
+      raise(AASR_ERR_UNSUPPORTED, "mllr: no accumulation kernel for dimension %d (1 ... %d)", m.dim, MLLR_MAX_DIM);
+    int max_comps = 0;
+    for (int64_t s = 0; s < m.S; s++) max_comps = std::max(max_comps, m.mix_off[(size_t)s + 1] - m.mix_off[(size_t)s]);
+    if (mllr_weights_lds_bytes(m.dim, max_comps) > 60 * 1024)
+      raise(AASR_ERR_UNSUPPORTED, "mllr: mixtures of %d components exceed the weight kernel's LDS", max_comps);
+    require_device();
+    std::unique_ptr<aasr_mllr> h(new aasr_mllr());
+    h->gmm = gmm;
+    h->D = m.dim;
+    h->S = (int)m.S;
+    h->max_comps = max_comps;
+    h->SL = mllr_slab_doubles(h->D);
+    gmm_build_f64(gmm);
+    // per record 1 / covar and mean / covar as MllTrainerComponent::collect_data forms them (MllrTrainer.cc:155-159);
+    // a non-positive variance has precision 0 in the records (gmm_build_f64's rule) and weighs nothing here
+    const size_t K = m.mix_idx.size();
+    std::vector<double> iv(std::max<size_t>(1, K) * h->D, 0.0), mv(std::max<size_t>(1, K) * h->D, 0.0);
+    for (size_t k = 0; k < K; k++) {
+      const int64_t gi = m.mix_idx[k];
+      for (int d = 0; d < h->D; d++) {
+        const double v = m.var[(size_t)gi * h->D + d];
+        iv[k * h->D + d] = v > 0 ? 1 / v : 0;
+        mv[k * h->D + d] = v > 0 ? m.mean[(size_t)gi * h->D + d] / v : 0;
+      }
+    }
+    h->inv_var.upload(iv.data(), iv.size());
+    h->mean_var.upload(mv.data(), mv.size());
+    h->acc.alloc((size_t)h->SL);
+    AASR_HIP(hipMemset(h->acc.p, 0, h->acc.n * sizeof(double)));
+    AASR_HIP(hipEventCreateWithFlags(&h->staged, hipEventDisableTiming));
+    *out = h.release();
+  });
+}
+
+void aasr_mllr_destroy(aasr_mllr *h) { delete h; }
+
+aasr_status aasr_mllr_reset(aasr_mllr *h, void *stream) {
+  return guarded([&] {
+    if (!h) raise(AASR_ERR_INVALID, "aasr_mllr_reset: null argument");
+    AASR_HIP(hipMemsetAsync(h->acc.p, 0, h->acc.n * sizeof(double), (hipStream_t)stream));
+    h->fetched = false;
+  });
+}
+
+aasr_status aasr_mllr_accumulate_dev(aasr_mllr *h, const double *d_frames, int64_t n_frames, const int32_t *pdf,
+                                     void *stream) {
+  return guarded([&] {
+    if (!h || n_frames < 0 || (n_frames > 0 && (!d_frames || !pdf)))
+      raise(AASR_ERR_INVALID, "aasr_mllr_accumulate_dev: bad argument");
+    if (n_frames > INT32_MAX) raise(AASR_ERR_INVALID, "aasr_mllr_accumulate_dev: more than 2^31 frames in one call");
+    if (n_frames == 0) return;
+    check_mllr_model(h->gmm);
+    for (int64_t f = 0; f < n_frames; f++)
+      if (pdf[f] >= h->S)
+        raise(AASR_ERR_INVALID, "aasr_mllr_accumulate_dev: pdf %d of frame %ld out of range", pdf[f], (long)f);
+    const hipStream_t st = (hipStream_t)stream;
+    if (h->staged_pending) AASR_HIP(hipEventSynchronize(h->staged));
+    h->staged_pending = false;
+    h->h_pdf.assign(pdf, pdf + n_frames);
+    h->d_pdf.ensure((size_t)n_frames);
+    AASR_HIP(hipMemcpyAsync(h->d_pdf.p, h->h_pdf.data(), (size_t)n_frames * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    AASR_HIP(hipEventRecord(h->staged, st));
+    h->staged_pending = true;
+    const int64_t launch = (int64_t)MLLR_CHUNK * MLLR_MAX_CHUNKS;
+    const int64_t cap = std::min(launch, n_frames);
+    h->w.ensure((size_t)cap * h->D);
+    h->u.ensure((size_t)cap * (h->D + 1));
+    h->ok.ensure((size_t)cap);
+    h->slab.ensure((size_t)((cap + MLLR_CHUNK - 1) / MLLR_CHUNK) * h->SL);
+    MllrParams p{};
+    p.dim = h->D;
+    p.recs = h->gmm->f64_recs.p;
+    p.dimp = h->gmm->f64_dimp;
+    p.rec = 2 * p.dimp + 2;
+    p.state_off = h->gmm->f64_state_off.p;
+    p.inv_var = h->inv_var.p;
+    p.mean_var = h->mean_var.p;
+    p.max_comps = h->max_comps;
+    p.w = h->w.p;
+    p.u = h->u.p;
+    p.ok = h->ok.p;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += launch) {  // (the launches of a call follow each other on the stream)
+      p.x = d_frames + (size_t)f0 * h->D;
+      p.pdf = h->d_pdf.p + f0;
+      p.n = (int32_t)std::min(launch, n_frames - f0);
+      mllr_weights_launch(p, st);
+      mllr_rank_launch(p, h->slab.p, h->acc.p, st);
+    }
+    h->fetched = false;
+  });
+}
+
+aasr_status aasr_mllr_fetch(aasr_mllr *h, void *stream) {
+  return guarded([&] {
+    if (!h) raise(AASR_ERR_INVALID, "aasr_mllr_fetch: null argument");
+    const hipStream_t st = (hipStream_t)stream;
+    h->h_acc.resize((size_t)h->SL);
+    AASR_HIP(hipMemcpyAsync(h->h_acc.data(), h->acc.p, (size_t)h->SL * sizeof(double), hipMemcpyDeviceToHost, st));
+    AASR_HIP(hipStreamSynchronize(st));
+    h->staged_pending = false;
+    h->fetched = true;
+  });
+}
+
+aasr_status aasr_mllr_get(const aasr_mllr *h, double *G, double *k, double *beta) {
+  return guarded([&] {
+    if (!h) raise(AASR_ERR_INVALID, "aasr_mllr_get: null argument");
+    if (!h->fetched) raise(AASR_ERR_INVALID, "aasr_mllr_get: call aasr_mllr_fetch after the last accumulation");
+    const int D = h->D, E = D + 1, PB = mllr_pb(D), NT = mllr_g_tiles(PB);
+    const double *a = h->h_acc.data();
+    // the tiles on and below the diagonal, mirrored
+    if (G)
+      for (int i = 0; i < D; i++)
+        for (int r = 0; r < E; r++)
+          for (int c = 0; c <= r; c++) {
+            const int R = r / 16, C = c / 16;
+            const double v = a[((size_t)i * NT + (size_t)R * (R + 1) / 2 + C) * 256 + (r % 16) * 16 + c % 16];
+            G[((size_t)i * E + r) * E + c] = v;
+            G[((size_t)i * E + c) * E + r] = v;
+          }
+    const double *kt = a + (size_t)D * NT * 256;
+    auto kat = [&](int r, int c) { return kt[((size_t)(r / 16) * PB + c / 16) * 256 + (r % 16) * 16 + c % 16]; };
+    if (k)
+      for (int i = 0; i < D; i++)
+        for (int c = 0; c < E; c++) k[(size_t)i * E + c] = kat(i, c);
+    if (beta) *beta = kat(D, 0);
+  });
+}
+
+}  // extern "C"
+
+// ---- the host solver ---------------------------------------------------------------------------
+
+namespace aasr {
+
+// LU with partial pivoting of the n x n row-major matrix a in place (dgetrf's algorithm: the pivot of a column is its
+// entry of largest magnitude at or below the diagonal, the first such), the inverse from the factors (dgetri's
+// result); *det: the product of U's diagonal WITHOUT the permutation's sign, which is what the reference multiplies
+// up after LUFactorizeIP (MllrTrainer.cc:207-211).  false: a zero pivot.
+static bool lu_inverse(std::vector<double> &a, int n, double *det) {
+  std::vector<int> piv((size_t)n);
+  for (int c = 0; c < n; c++) {
+    int p = c;
+    double best = std::fabs(a[(size_t)c * n + c]);
+    for (int r = c + 1; r < n; r++)
+      if (std::fabs(a[(size_t)r * n + c]) > best) {
+        best = std::fabs(a[(size_t)r * n + c]);
+        p = r;
+      }
+    piv[(size_t)c] = p;
+    if (!(best > 0)) return false;  // (a NaN column as well)
+    if (p != c)
+      for (int j = 0; j < n; j++) std::swap(a[(size_t)c * n + j], a[(size_t)p * n + j]);
+    const double d = a[(size_t)c * n + c];
+    for (int r = c + 1; r < n; r++) {
+      const double l = a[(size_t)r * n + c] / d;
+      a[(size_t)r * n + c] = l;
+      if (l != 0)
+        for (int j = c + 1; j < n; j++) a[(size_t)r * n + j] -= l * a[(size_t)c * n + j];
+    }
+  }
+  if (det) {
+    double d = 1;
+    for (int i = 0; i < n; i++) d *= a[(size_t)i * n + i];
+    *det = d;
+  }
+  // P A = L U: A^-1 = U^-1 L^-1 P, column by column
+  std::vector<double> inv((size_t)n * n), y((size_t)n);
+  for (int c = 0; c < n; c++) {
+    for (int i = 0; i < n; i++) y[(size_t)i] = 0;
+    y[(size_t)c] = 1;
+    for (int i = 0; i < n; i++) {  // L z = e_c
+      double s = y[(size_t)i];
+      for (int j = 0; j < i; j++) s -= a[(size_t)i * n + j] * y[(size_t)j];
+      y[(size_t)i] = s;
+    }
+    for (int i = n - 1; i >= 0; i--) {  // U v = z
+      double s = y[(size_t)i];
+      for (int j = i + 1; j < n; j++) s -= a[(size_t)i * n + j] * y[(size_t)j];
+      y[(size_t)i] = s / a[(size_t)i * n + i];
+    }
+    for (int i = 0; i < n; i++) inv[(size_t)i * n + c] = y[(size_t)i];
+  }
+  // ... times P: undo the row exchanges as column exchanges, last first
+  for (int c = n - 1; c >= 0; c--)
+    if (piv[(size_t)c] != c)
+      for (int i = 0; i < n; i++) std::swap(inv[(size_t)i * n + c], inv[(size_t)i * n + piv[(size_t)c]]);
+  a.swap(inv);
+  return true;
+}
+
+// x^T (A y) (MllTrainerComponent::get_product)
+static double xAy(const std::vector<double> &x, const double *A, const double *y, int n, std::vector<double> &work) {
+  for (int i = 0; i < n; i++) {
+    double s = 0;
+    for (int j = 0; j < n; j++) s += A[(size_t)i * n + j] * y[j];
+    work[(size_t)i] = s;
+  }
+  double s = 0;
+  for (int i = 0; i < n; i++) s += x[(size_t)i] * work[(size_t)i];
+  return s;
+}
+
+// MllTrainerComponent::calculate_transform (MllrTrainer.cc:165-231)
+static void mllr_solve(int dim, const double *G, const double *k, double beta, double *W) {
+  const int E = dim + 1;
+  std::vector<std::vector<double>> inv_G((size_t)dim);
+  for (int i = 0; i < dim; i++) {
+    inv_G[(size_t)i].assign(G + (size_t)i * E * E, G + (size_t)(i + 1) * E * E);
+    if (!lu_inverse(inv_G[(size_t)i], E, nullptr)) raise(AASR_ERR_INVALID, "mllr: zero pivot in G_%d (singular statistics)", i);
+  }
+  std::vector<double> trans((size_t)dim * E, 0.0), A((size_t)dim * dim), p((size_t)E), w((size_t)E), work((size_t)E);
+  for (int i = 0; i < dim; i++) trans[(size_t)i * E + i + 1] = 1;
+  for (int round = 0; round < 20 * dim; round++) {
+    const int row = round % dim;
+    for (int i = 0; i < dim; i++)
+      for (int j = 0; j < dim; j++) A[(size_t)j * dim + i] = trans[(size_t)i * E + j + 1];
+    double detA = 1;
+    if (!lu_inverse(A, dim, &detA)) raise(AASR_ERR_INVALID, "mllr: zero pivot in A (round %d)", round);
+    p[0] = 0;
+    for (int i = 0; i < dim; i++) p[(size_t)i + 1] = detA * A[(size_t)row * dim + i];  // the cofactor row: detA A^-1
+    const double *Gi = inv_G[(size_t)row].data(), *kr = k + (size_t)row * E;
+    // calculate_alpha (MllrTrainer.cc:233-253)
+    const double c2 = xAy(p, Gi, p.data(), E, work);
+    const double c1 = xAy(p, Gi, kr, E, work);
+    const double a1 = (-c1 + std::sqrt(c1 * c1 + 4 * c2 * beta)) / (2 * c2);
+    const double a2 = (-c1 - std::sqrt(c1 * c1 + 4 * c2 * beta)) / (2 * c2);
+    const double m1 = beta * std::log(std::fabs(a1 * c2 + c1)) - (c2 / 2) * a1 * a1;
+    const double m2 = beta * std::log(std::fabs(a2 * c2 + c1)) - (c2 / 2) * a2 * a2;
+    const double alpha = m1 > m2 ? a1 : a2;
+    for (int i = 0; i < E; i++) p[(size_t)i] = alpha * p[(size_t)i] + kr[i];
+    for (int i = 0; i < E; i++) {  // w = inv_G^T p
+      double s = 0;
+      for (int j = 0; j < E; j++) s += Gi[(size_t)j * E + i] * p[(size_t)j];
+      w[(size_t)i] = s;
+    }
+    for (int i = 0; i < E; i++) trans[(size_t)row * E + i] = w[(size_t)i];
+  }
+  std::copy(trans.begin(), trans.end(), W);
+}
+
+// MllrTrainer::calculate_transform(LinTransformModule *) (MllrTrainer.cc:98-145): W = [b | A], composed with the
+// module's transform when it has one, narrowed to float
+static void mllr_compose(int dim, const double *W, const float *old_A, const float *old_b, float *A_out, float *b_out) {
+  const int E = dim + 1;
+  std::vector<double> A((size_t)dim * dim), b((size_t)dim);
+  for (int i = 0; i < dim; i++) {
+    b[(size_t)i] = W[(size_t)i * E];
+    for (int j = 0; j < dim; j++) A[(size_t)i * dim + j] = W[(size_t)i * E + 1 + j];
+  }
+  if (old_A && old_b) {
+    // line 127 is Blas_Mat_Vec_Mult(old_A, b, b): b is overwritten in place while it is read.  dgemv with beta = 0
+    // clears y first, so with x and y the same vector the result is old_A * 0 = 0, and line 128 leaves b = old_b.
+    // The new bias does not survive the composition in the reference; neither does it here.
+    std::vector<double> nb((size_t)dim);
+    for (int i = 0; i < dim; i++) nb[(size_t)i] = 0.0 + 1.0 * (double)old_b[i];
+    std::vector<double> nA((size_t)dim * dim);
+    for (int i = 0; i < dim; i++)
+      for (int j = 0; j < dim; j++) {
+        double s = 0;
+        for (int l = 0; l < dim; l++) s += A[(size_t)i * dim + l] * (double)old_A[(size_t)l * dim + j];
+        nA[(size_t)i * dim + j] = s;
+      }
+    A.swap(nA);
+    b.swap(nb);
+  }
+  for (int i = 0; i < dim; i++) {
+    b_out[i] = (float)b[(size_t)i];
+    for (int j = 0; j < dim; j++) A_out[(size_t)i * dim + j] = (float)A[(size_t)i * dim + j];
+  }
+}
+
+}  // namespace aasr
+
+extern "C" {
+
+aasr_status aasr_mllr_solve(int32_t dim, const double *G, const double *k, double beta, double *W) {
+  return guarded([&] {
+    if (dim < 1 || !G || !k || !W) raise(AASR_ERR_INVALID, "aasr_mllr_solve: bad argument");
+    mllr_solve(dim, G, k, beta, W);
+  });
+}
+
+aasr_status aasr_mllr_compose(int32_t dim, const double *W, const float *old_A, const float *old_b, float *A, float *b) {
+  return guarded([&] {
+    if (dim < 1 || !W || !A || !b || (!old_A != !old_b)) raise(AASR_ERR_INVALID, "aasr_mllr_compose: bad argument");
+    mllr_compose(dim, W, old_A, old_b, A, b);
+  });
+}
+
+void aasr_mllr_default_options(aasr_mllr_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->minframes = 1000;
+}
+
+}  // extern "C"
+
+// ---- the mllr main loop over a recipe ----------------------------------------------------------
+
+extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                            const aasr_mllr_options *opt, aasr_run_stats *stats) {
+  return guarded([&] {
+    if (!feat || !gmm || !topo || !recipe_path || !opt || !opt->speakers)
+      raise(AASR_ERR_INVALID, "aasr_run_mllr_recipe: null argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    aasr_spkc *spk = opt->speakers;
+    std::vector<RecipeInfo> infos;
+    {
+      std::ifstream rin(recipe_path);
+      if (!rin) raise(AASR_ERR_IO, "could not open recipe %s", recipe_path);
+      std::stringstream ss;
+      ss << rin.rdbuf();
+      // Recipe::read with cluster_speakers = true, then sort_infos (aku/mllr.cc:213-216)
+      infos = recipe_read(ss.str(), opt->num_batches, opt->batch_index, true);
+      std::stable_sort(infos.begin(), infos.end(),
+                       [](const RecipeInfo &a, const RecipeInfo &b) { return a.speaker_id < b.speaker_id; });
+    }
+    for (const RecipeInfo &u : infos)
+      if (u.start_line > 0 || u.end_line > 0)
+        raise(AASR_ERR_UNSUPPORTED, "mllr: recipe line limits (start-line / end-line) are not supported");
+    const int D = aasr_gmm_dim(gmm);
+    if (D != aasr_feat_dim(feat))
+      raise(AASR_ERR_INVALID, "gaussian dimension is %d but feature dimension is %d", D, aasr_feat_dim(feat));
+    const bool global_transform = opt->module && opt->module[0];
+    FeatModule *ltm = nullptr;
+    std::string module;
+    if (global_transform) {
+      module = opt->module;
+      auto it = feat->by_name.find(module);
+      if (it == feat->by_name.end()) raise(AASR_ERR_INVALID, "unknown module requested: %s", module.c_str());
+      ltm = &feat->mods[(size_t)it->second];
+      if (ltm->type != MOD_LIN_TRANSFORM || ltm->dim != D || ltm->src_dim != D)
+        raise(AASR_ERR_INVALID, "mllr: -M %s is not a lin_transform module of %d x %d", module.c_str(), D, D);
+    } else {
+      if (aasr_spkc_set_model(spk, gmm) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      spkc_cmllr_disable_loading(spk);  // the statistics are collected on the unadapted model (aku/mllr.cc:263-266)
+    }
+    aasr_mllr *h = nullptr;
+    {
+      const aasr_status cs = aasr_mllr_create(gmm, &h);
+      if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
+    }
+    std::unique_ptr<aasr_mllr, void (*)(aasr_mllr *)> hguard(h, aasr_mllr_destroy);
+    const float fr = aasr_feat_frame_rate(feat);
+    hipStream_t stream;
+    AASR_HIP(hipStreamCreate(&stream));
+    std::unique_ptr<void, void (*)(void *)> sguard((void *)stream, [](void *s) { (void)hipStreamDestroy((hipStream_t)s); });
+    // a change of feature parameters waits for the features queued with the old ones
+    struct Unhook {
+      aasr_spkc *s;
+      ~Unhook() { spkc_set_before_change(s, nullptr); }
+    } unhook{spk};
+    spkc_set_before_change(spk, [stream]() { AASR_HIP(hipStreamSynchronize(stream)); });
+
+    DevBuf<int16_t> d_pcm;
+    DevBuf<double> d_x;
+    const int64_t max_group_frames = (int64_t)1 << 18;
+    std::set<std::string> updated;
+    std::string cur_speaker;
+    bool have_trainer = false;
+    int64_t num_frames = 0;
+    const int E = D + 1;
+    std::vector<double> G((size_t)D * E * E), k((size_t)D * E), W((size_t)D * E);
+
+    // calculate_transform (aku/mllr.cc:39-52) for cur_speaker
+    auto finish_speaker = [&]() {
+      if (opt->info > 0) {
+        printf("%s: ", cur_speaker.c_str());
+        fflush(stdout);
+        fprintf(stderr, "Calculating transform for %s\n", cur_speaker.c_str());
+      }
+      double beta = 0;
+      if (aasr_mllr_fetch(h, stream) != AASR_OK || aasr_mllr_get(h, G.data(), k.data(), &beta) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      try {
+        mllr_solve(D, G.data(), k.data(), beta, W.data());
+      } catch (Error &e) {
+        raise(e.code, "speaker %s: %s", cur_speaker.c_str(), e.msg.c_str());
+      }
+      if (global_transform) {
+        std::vector<float> Af((size_t)D * D), bf((size_t)D);
+        const bool defined = ltm->matrix_defined && ltm->bias_defined;  // LinTransformModule::is_defined
+        mllr_compose(D, W.data(), defined ? ltm->matrix.data() : nullptr, defined ? ltm->bias.data() : nullptr, Af.data(),
+                     bf.data());
+        spkc_feature_rewritten(spk, module);  // (the stream is idle: the fetch waited)
+        ltm->matrix = Af;
+        ltm->bias = bf;
+        ltm->matrix_defined = ltm->bias_defined = true;
+        ltm->d_matrix.upload(ltm->matrix.data(), ltm->matrix.size());
+        ltm->d_bias.upload(ltm->bias.data(), ltm->bias.size());
+      } else {
+        spkc_cmllr_add_global_transform(spk, W);
+        if (opt->info > 0) {  // MllrTrainer.cc:78-80: an ostream's default formatting of a double
+          std::ostringstream os;
+          os << beta << " frames, " << 1 << " transform matrices";
+          printf("%s\n", os.str().c_str());
+          fflush(stdout);
+        }
+      }
+      if (aasr_mllr_reset(h, stream) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      have_trainer = false;
+    };
+
+    struct Pending {
+      std::vector<int16_t> pcm;
+      int32_t start_frame = 0;
+      std::vector<int32_t> pdf;
+    };
+    size_t next = 0;
+    while (next < infos.size()) {
+      if (infos[next].speaker_id.empty()) raise(AASR_ERR_INVALID, "Speaker ID is missing");
+      // set_speaker (aku/mllr.cc:54-71): the previous speaker's transform first
+      if (infos[next].speaker_id != cur_speaker) {
+        if (have_trainer) finish_speaker();
+        cur_speaker = infos[next].speaker_id;
+        updated.insert(cur_speaker);
+        have_trainer = true;
+        if (aasr_spkc_set_speaker(spk, cur_speaker.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      }
+      // a group: utterances of this speaker, their frames in one device buffer, one accumulation
+      std::vector<Pending> group;
+      int64_t rows_total = 0;
+      size_t samples = 1;
+      const size_t group_first = next;
+      while (next < infos.size() && infos[next].speaker_id == cur_speaker && group.size() < 1024 &&
+             rows_total < max_group_frames) {
+        const RecipeInfo &u = infos[next];
+        if (opt->info > 0) {
+          fprintf(stderr, "Processing file: %s (%d/%d)", u.audio_path.c_str(), (int)next + 1, (int)infos.size());
+          if (u.start_time || u.end_time) fprintf(stderr, " (%.2f-%.2f)", u.start_time, u.end_time);
+          fprintf(stderr, "\n");
+        }
+        int16_t *pcm = nullptr;
+        int64_t n_samples = 0;
+        int32_t rate = 0;
+        if (aasr_feat_input_is_features(feat)) {
+          std::ifstream in(u.audio_path, std::ios::binary);
+          if (!in) raise(AASR_ERR_IO, "could not open %s", u.audio_path.c_str());
+          const std::string bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+          if (aasr_audio_decode(feat, bytes.data(), (int64_t)bytes.size(), &pcm, &n_samples, &rate) != AASR_OK)
+            raise(AASR_ERR_IO, "%s: %s", u.audio_path.c_str(), aasr_last_error());
+        } else if (aasr_audio_read(feat, u.audio_path.c_str(), &pcm, &n_samples, &rate) != AASR_OK) {
+          raise(AASR_ERR_IO, "%s", aasr_last_error());
+        }
+        Pending pd;
+        pd.pcm.assign(pcm, pcm + n_samples);
+        aasr_free(pcm);
+        const int eof = aasr_feat_eof_frame(feat, n_samples);
+        int first = 0, last = 0;
+        if (u.start_time > 0 || u.end_time > 0) {
+          first = (int)(u.start_time * fr);
+          last = (int)(u.end_time * fr);
+        }
+        int32_t *seg_pdf = nullptr, *seg_tr = nullptr, n = 0, start = 0;
+        if (aasr_stats_read_segmentation(topo, (opt->ophn ? u.alignment_path : u.transcript_path).c_str(), fr, first, last, eof,
+                                         0, &start, &seg_pdf, &seg_tr, &n) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        if (n < 0) {  // get_segmentator (aku/mllr.cc:111-115)
+          fprintf(stderr, "Could not initialize the utterance for PhnReader.");
+          fprintf(stderr, "Current file was: %s\n", u.audio_path.c_str());
+          pd.pcm.clear();
+          n = 0;
+        }
+        pd.start_frame = start;
+        // train_mllr hands the segmentator's PDF index to model.state() and takes that state's emission_pdf
+        // (aku/mllr.cc:136-140): a double lookup.  In the .ph files this engine reads a state's emission pdf is the
+        // state's own index (HmmSet::read_ph, legacy format) and the engine takes state == pdf throughout, so
+        // both lookups are the identity here and the segmentation's index is used as it is.
+        pd.pdf.assign(seg_pdf, seg_pdf + n);
+        aasr_free(seg_pdf);
+        aasr_free(seg_tr);
+        rows_total += n;
+        samples += pd.pcm.size();
+        group.push_back(std::move(pd));
+        next++;
+      }
+      d_x.ensure((size_t)std::max<int64_t>(1, rows_total) * D);
+      if (samples > d_pcm.n) {
+        AASR_HIP(hipStreamSynchronize(stream));
+        d_pcm.alloc(samples);
+      }
+      std::vector<int32_t> pdfs;
+      pdfs.reserve((size_t)rows_total);
+      size_t pcm_at = 0;
+      int64_t row = 0;
+      for (size_t gi = 0; gi < group.size(); gi++) {
+        Pending &pd = group[gi];
+        const RecipeInfo &u = infos[group_first + gi];
+        // set_utterance per line (aku/mllr.cc:289-290); a parameter change waits for the queued features
+        if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        const int64_t n = (int64_t)pd.pdf.size();
+        if (n > 0) {
+          if (!pd.pcm.empty())
+            AASR_HIP(hipMemcpyAsync(d_pcm.p + pcm_at, pd.pcm.data(), pd.pcm.size() * sizeof(int16_t), hipMemcpyHostToDevice,
+                                    stream));
+          // the frames carry the speaker's CURRENT transform, as the reference's feature generator does
+          if (aasr_feat_run_f64_dev(feat, d_pcm.p + pcm_at, (int64_t)pd.pcm.size(), pd.start_frame, (int32_t)n,
+                                    d_x.p + (size_t)row * D, stream) != AASR_OK)
+            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+          pcm_at += pd.pcm.size();
+        }
+        pdfs.insert(pdfs.end(), pd.pdf.begin(), pd.pdf.end());
+        row += n;
+      }
+      if (rows_total > 0) {
+        if (aasr_mllr_accumulate_dev(h, d_x.p, rows_total, pdfs.data(), stream) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        AASR_HIP(hipStreamSynchronize(stream));  // the group's host audio and pdfs go out of scope
+      }
+      num_frames += rows_total;
+    }
+    if (have_trainer) finish_speaker();
+
+    // the new speaker configuration (aku/mllr.cc:318-332)
+    if (opt->out) {
+      std::vector<const char *> sp;
+      int32_t n_sp = -1, n_ut = -1;
+      if (opt->num_batches > 1) {
+        if (opt->batch_index == 1) updated.insert("default");
+        for (const std::string &s : updated) sp.push_back(s.c_str());
+        n_sp = (int32_t)sp.size();
+        n_ut = 0;
+      }
+      char *text = nullptr;
+      int64_t len = 0;
+      if (aasr_spkc_write_text(spk, sp.data(), n_sp, nullptr, n_ut, &text, &len) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      std::unique_ptr<char, void (*)(void *)> tguard(text, free);
+      std::ofstream of(opt->out, std::ios::binary);
+      if (!of) raise(AASR_ERR_IO, "could not open %s for writing", opt->out);
+      of.write(text, (std::streamsize)len);
+      if (!of) raise(AASR_ERR_IO, "write error on %s", opt->out);
+    }
+    if (stats) {
+      stats->utterances = (int64_t)infos.size();
+      stats->frames = num_frames;
+      stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      stats->seconds_device = 0;
+      stats->seconds_copy_out = 0;
+    }
+  });
+}

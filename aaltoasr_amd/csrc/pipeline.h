@@ -49,5 +49,13 @@ void spkc_set_speaker(aasr_spkc *h, const std::string &speaker_id);
 void spkc_set_utterance(aasr_spkc *h, const std::string &utterance_id);
 // called right before any module's device parameters change
 void spkc_set_before_change(aasr_spkc *h, std::function<void()> fn);
+// what the mllr tool does to the configuration (aku/mllr.cc:257-267, MllrTrainer.cc:63-145):
+// a feature module's parameters were rewritten behind the handle (the change hook runs, the next set_speaker
+// applies its block whatever was applied last)
+void spkc_feature_rewritten(aasr_spkc *h, const std::string &module);
+// ConstrainedMllr::disable_loading on module("cmllr"): no speaker's transform reaches the model any more
+void spkc_cmllr_disable_loading(aasr_spkc *h);
+// ConstrainedMllr::add_transformation_couple + set_unit_mode(UNIT_NO): W [dim][dim + 1] under the root node's unit list
+void spkc_cmllr_add_global_transform(aasr_spkc *h, const std::vector<double> &W);
 
 }  // namespace aasr

@@ -55,6 +55,7 @@ struct aasr_spkc {
   bool has_cmllr = false;    // module("cmllr") has been requested
   bool trans_is_reset = true;
   bool cmllr_loaded = false;
+  bool cmllr_disabled = false;  // ConstrainedMllr::disable_loading (the mllr tool)
   int unit_mode = aasr::UNIT_NO;
   std::map<std::vector<std::string>, std::vector<double>> trans;  // W [dim][dim+1]
   bool device_adapted = false;
@@ -305,7 +306,7 @@ static void unit_gaussians(const aasr_spkc *h, const std::vector<std::string> &e
 // ModelTransformer::load_transforms -> ConstrainedMllr::load_transform
 // (aku/ModelModules.cc:42-50, 164-232)
 static void load_transforms(aasr_spkc *h) {
-  if (h->has_cmllr && !h->cmllr_loaded) {
+  if (h->has_cmllr && !h->cmllr_loaded && !h->cmllr_disabled) {
     aasr_gmm *g = h->gmm;
     if (!g) raise(AASR_ERR_INVALID, "SpeakerConfig: model transform without a model");
     if (h->trans.empty()) {
@@ -434,6 +435,31 @@ void spkc_set_speaker(aasr_spkc *h, const std::string &speaker_id) {
 }
 
 void spkc_set_before_change(aasr_spkc *h, std::function<void()> fn) { h->before_change = std::move(fn); }
+
+void spkc_feature_rewritten(aasr_spkc *h, const std::string &module) {
+  note_change(h);
+  h->applied.erase(module);
+}
+
+// ModelModule::disable_loading (aku/ModelModules.hh:32-35): m_disabled, then reset_transform
+void spkc_cmllr_disable_loading(aasr_spkc *h) {
+  model_module(h, "cmllr");
+  h->cmllr_disabled = true;
+  h->unit_mode = UNIT_PHONE;  // aku/mllr.cc:266, until the first transform sets UNIT_NO
+  if (h->device_adapted) {
+    note_change(h);
+    gmm_set_transforms(h->gmm, 0, nullptr, nullptr);
+    h->device_adapted = false;
+  }
+  h->cmllr_loaded = false;
+}
+
+// the root node of a UNIT_NO tree holds one UnitGlobal whose identifier is "" (aku/RegClassTree.hh:141,
+// 195-209): that list is the transform's key
+void spkc_cmllr_add_global_transform(aasr_spkc *h, const std::vector<double> &W) {
+  h->trans[std::vector<std::string>(1, std::string())] = W;
+  h->unit_mode = UNIT_NO;
+}
 
 }  // namespace aasr
 

@@ -753,6 +753,58 @@ aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_top
                                   const char *recipe_path, const aasr_stats_options *opt,
                                   aasr_run_stats *stats);
 
+/* ---------------------------------------------------------------------------
+ * Constrained MLLR estimation: aku/mllr.cc over state-segmented .phn files, one global transform per
+ * speaker -- for a lin_transform feature module (-M) or as a model-side cmllr block (unitmode UNIT_NO).
+ *
+ * The accumulator of one model, on the device, for the CURRENT speaker: MllrTrainer::collect_data
+ * (aku/MllrTrainer.cc:22-60, 147-163) for xi = [1, x]:
+ *   G_i += sum_g (gamma_g / var_gi) xi xi^T,  k_i += sum_g (gamma_g mu_gi / var_gi) xi,  beta += sum_g gamma_g
+ * with gamma_g = lik_g / sum lik (the mixture weights are not used, as in the reference; a frame whose sum is
+ * 0 or not finite adds nothing).  Diagonal pools of 1 ... 63 dimensions (AASR_ERR_UNSUPPORTED beyond), the
+ * unadapted model.  Deterministic: no atomics, fixed summation order. */
+typedef struct aasr_mllr aasr_mllr;
+aasr_status aasr_mllr_create(aasr_gmm *gmm, aasr_mllr **out);
+void aasr_mllr_destroy(aasr_mllr *h);
+/* zeroes the sums (the next speaker), enqueued on `stream` */
+aasr_status aasr_mllr_reset(aasr_mllr *h, void *stream);
+/* Adds n_frames double frame rows (device, [n_frames x dim]) whose pdfs are pdf[] (host; -1: skip) on
+ * `stream`, no host wait.  Calls on one handle go to one stream. */
+aasr_status aasr_mllr_accumulate_dev(aasr_mllr *h, const double *d_frames, int64_t n_frames,
+                                     const int32_t *pdf, void *stream);
+/* fetches the sums to the host (waits) */
+aasr_status aasr_mllr_fetch(aasr_mllr *h, void *stream);
+/* after a fetch: G [dim][dim + 1][dim + 1] (symmetric), k [dim][dim + 1], *beta; any pointer may be NULL */
+aasr_status aasr_mllr_get(const aasr_mllr *h, double *G, double *k, double *beta);
+/* MllTrainerComponent::calculate_transform (aku/MllrTrainer.cc:165-253) in double: W [dim][dim + 1],
+ * column 0 the bias.  A zero pivot in a G_i or in A is AASR_ERR_INVALID.  Host only. */
+aasr_status aasr_mllr_solve(int32_t dim, const double *G, const double *k, double beta, double *W);
+/* MllrTrainer::calculate_transform(LinTransformModule *) (aku/MllrTrainer.cc:98-145): W as the float matrix
+ * A [dim x dim] and bias b [dim] of a lin_transform module, composed with the module's old_A / old_b
+ * (both NULL: the module has no transform yet) exactly as the reference composes them.  Host only. */
+aasr_status aasr_mllr_compose(int32_t dim, const double *W, const float *old_A, const float *old_b,
+                              float *A, float *b);
+
+typedef struct aasr_mllr_options {
+  int32_t ophn;         /* -O: read the recipe's alignment= files                          */
+  int32_t info;         /* -i                                                              */
+  int32_t num_batches;  /* -B                                                              */
+  int32_t batch_index;  /* -I                                                              */
+  double minframes;     /* -f (a tree's merge threshold; without a tree it changes nothing) */
+  const char *module;   /* -M: the lin_transform module, or NULL for a model transform     */
+  struct aasr_spkc *speakers; /* -S: the speaker configuration (required)                  */
+  const char *out;      /* -o: the speaker file to write, or NULL                          */
+} aasr_mllr_options;
+void aasr_mllr_default_options(aasr_mllr_options *opt);
+
+/* mllr main loop (aku/mllr.cc:213-332) over one recipe slice (read with cluster_speakers, sorted by
+ * speaker): per speaker the features under its current configuration and the .phn segmentations, the
+ * accumulation on the device, one solve, the transform set on the module / the cmllr block; the -i
+ * messages on stderr and stdout; the speaker file.  seconds_device / seconds_copy_out stay 0. */
+aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
+                                 const char *recipe_path, const aasr_mllr_options *opt,
+                                 aasr_run_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
