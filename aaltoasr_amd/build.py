@@ -95,6 +95,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                       ("align", "aku/main_align.cc"),
                       ("stats", "aku/main_stats.cc"),
                       ("mllr", "aku/main_mllr.cc"),
+                      ("lda", "aku/main_lda.cc"),
                       ("aku_adapter_check", "aku/main_adapter_check.cc"),
                       ("feacat", "aku/main_feacat.cc"),
                       ("plugin_check", "aku/main_plugin_check.cc"),

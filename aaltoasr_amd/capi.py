@@ -158,6 +158,20 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_mllr_default_options.argtypes = [vp]
     L.aasr_mllr_default_options.restype = None
     L.aasr_run_mllr_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
+    L.aasr_scatter_create.argtypes = [i32, i32, pvp]
+    L.aasr_scatter_destroy.argtypes = [vp]
+    L.aasr_scatter_destroy.restype = None
+    L.aasr_scatter_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.aasr_scatter_fetch.argtypes = [vp, vp]
+    L.aasr_scatter_get.argtypes = [vp, vp, vp, vp]
+    L.aasr_debug_scatter_shape.argtypes = [vp, vp]
+    L.aasr_debug_scatter_shape.restype = None
+    L.aasr_debug_scatter_set_slab_bytes.argtypes = [vp, i64]
+    L.aasr_lda_solve.argtypes = [i32, i32, vp, vp, vp, vp, d, i32, vp]
+    L.aasr_lda_select.argtypes = [i32, vp, d, i32, i32, vp, i32, vp]
+    L.aasr_lda_default_options.argtypes = [vp]
+    L.aasr_lda_default_options.restype = None
+    L.aasr_run_lda_recipe.argtypes = [cp, vp, cp, vp, vp]
     L.aasr_spkc_write_text.argtypes = [vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(i64)]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
@@ -1273,3 +1287,104 @@ def run_mllr_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str, 
     st = RunStats()
     check(lib().aasr_run_mllr_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}
+
+
+# ---- LDA estimation -----------------------------------------------------------------------------
+
+class Scatter:
+    """Owner of an aasr_scatter handle: per class gamma, sum gamma x and sum gamma x x^T, on the device."""
+
+    def __init__(self, n_classes: int, dim: int):
+        h = C.c_void_p()
+        check(lib().aasr_scatter_create(n_classes, dim, C.byref(h)))
+        self._h = h.value
+        self.C, self.D = n_classes, dim
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_scatter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def accumulate_dev(self, d_frames, cls, d_weight=None, stream=None) -> None:
+        """d_frames: a float64 device tensor [n x dim]; cls: host int32 per frame (-1: skip); d_weight: a float64
+        device tensor [n] or None (1)."""
+        c = np.ascontiguousarray(cls, np.int32)
+        check(lib().aasr_scatter_accumulate_dev(self._h, _ptr(d_frames), len(c), _ptr(c), _ptr(d_weight),
+                                                _stream_handle(stream)))
+
+    def set_slab_bytes(self, nbytes: int) -> None:
+        """Diagnostic: the bound on a launch's slab memory."""
+        check(lib().aasr_debug_scatter_set_slab_bytes(self._h, nbytes))
+
+    def launch_shape(self) -> dict:
+        """Diagnostic: the kernel instance, the work items and the launches of the last call that added rows."""
+        out = (C.c_int32 * 3)()
+        lib().aasr_debug_scatter_shape(self._h, out)
+        return {"pb": int(out[0]), "items": int(out[1]), "launches": int(out[2])}
+
+    def fetch(self, stream=None):
+        """Waits for the device; -> gamma [C], sum_x [C x dim], sum_xx [C x dim (dim + 1) / 2] (packed lower
+        triangle, row-major with j <= i)."""
+        L = lib()
+        check(L.aasr_scatter_fetch(self._h, _stream_handle(stream)))
+        g, sx = np.zeros(self.C), np.zeros((self.C, self.D))
+        sxx = np.zeros((self.C, self.D * (self.D + 1) // 2))
+        check(L.aasr_scatter_get(self._h, _ptr(g), _ptr(sx), _ptr(sxx)))
+        return g, sx, sxx
+
+
+def lda_solve(gamma, sum_x, sum_xx, selected, max_gamma: float, target_dim: int):
+    """lda.cc:380-446 (host only): -> lda [target_dim x dim]; rows by falling eigenvalue of the projected covariance,
+    every row's largest-magnitude entry positive."""
+    g, sx = np.ascontiguousarray(gamma, np.float64), np.ascontiguousarray(sum_x, np.float64)
+    sxx, sel = np.ascontiguousarray(sum_xx, np.float64), np.ascontiguousarray(selected, np.int32)
+    n, D = sx.shape
+    out = np.zeros((target_dim, D))
+    check(lib().aasr_lda_solve(n, D, _ptr(g), _ptr(sx), _ptr(sxx), _ptr(sel), float(max_gamma), target_dim, _ptr(out)))
+    return out
+
+
+def lda_select(count, mingamma: float, maxmem: int, dim: int, silence=()):
+    """lda.cc:113-115, 247-263 (host only): -> 0 / 1 per state."""
+    c = np.ascontiguousarray(count, np.float64)
+    sil = np.ascontiguousarray(silence, np.int32)
+    out = np.zeros(len(c), np.int32)
+    check(lib().aasr_lda_select(len(c), _ptr(c), float(mingamma), maxmem, dim, _ptr(sil) if len(sil) else None, len(sil),
+                                _ptr(out)))
+    return out
+
+
+class LdaOptions(C.Structure):
+    """aasr_lda_options: lda's options (aku/lda.cc:51-72) over .phn files."""
+    _fields_ = [("ophn", C.c_int32), ("info", C.c_int32), ("target_dim", C.c_int32), ("maxmem", C.c_int32),
+                ("no_silence", C.c_int32), ("mingamma", C.c_double), ("maxgamma", C.c_double), ("module", C.c_char_p),
+                ("speakers", C.c_char_p), ("out", C.c_char_p), ("state_gamma", C.c_void_p),
+                ("seconds_scatter", C.c_double), ("seconds_features", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "LdaOptions":
+        o = cls()
+        lib().aasr_lda_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_lda_recipe(cfg_text: str, topo: Topology, recipe_path: str, module: str, target_dim: int,
+                   out: Optional[str] = None, speakers: Optional[str] = None, opts: Optional[LdaOptions] = None) -> dict:
+    """-> the run's counts and device times, and "state_gamma": the scatter handle's gamma of every state."""
+    opts = opts or LdaOptions.defaults()
+    mb, ob, sb = module.encode(), (out.encode() if out else None), (speakers.encode() if speakers else None)
+    opts.module, opts.out, opts.speakers, opts.target_dim = mb, ob, sb, target_dim
+    sg = np.zeros(topo.num_states())
+    opts.state_gamma = sg.ctypes.data
+    st = RunStats()
+    check(lib().aasr_run_lda_recipe(cfg_text.encode(), topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total,
+            "seconds_scatter": opts.seconds_scatter, "seconds_features": opts.seconds_features, "state_gamma": sg}

@@ -805,6 +805,84 @@ aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
                                  const char *recipe_path, const aasr_mllr_options *opt,
                                  aasr_run_stats *stats);
 
+/* ---------------------------------------------------------------------------
+ * LDA estimation: aku/lda.cc over state-segmented .phn files.
+ *
+ * The class-scatter accumulator, on the device: FullStatisticsAccumulator::accumulate
+ * (aku/Distributions.cc:133-141) per class c over many frames at once,
+ *   gamma_c += w_t,  sum_x_c += w_t x_t,  sum_xx_c += w_t x_t x_t^T
+ * on the FP64 matrix pipe (csrc/scatter_accum.hip).  1 ... 127 dimensions (AASR_ERR_UNSUPPORTED beyond).
+ * Deterministic: no atomics, fixed summation order; the same calls give the same bytes. */
+typedef struct aasr_scatter aasr_scatter;
+aasr_status aasr_scatter_create(int32_t n_classes, int32_t dim, aasr_scatter **out);
+void aasr_scatter_destroy(aasr_scatter *h);
+/* Adds n_frames double frame rows (device, [n_frames x dim]) to the classes cls[] (host; -1: skip, any other value
+ * outside 0 ... n_classes - 1: AASR_ERR_INVALID, nothing is added) with the weights d_weight (device, n_frames
+ * doubles; NULL: 1) on `stream`, no host wait.  Calls on one handle go to one stream. */
+aasr_status aasr_scatter_accumulate_dev(aasr_scatter *h, const double *d_frames, int64_t n_frames, const int32_t *cls,
+                                        const double *d_weight, void *stream);
+/* fetches the sums to the host (waits) */
+aasr_status aasr_scatter_fetch(aasr_scatter *h, void *stream);
+/* after a fetch: gamma [n_classes], sum_x [n_classes x dim], sum_xx [n_classes x dim (dim + 1) / 2] -- the packed
+ * lower triangle, row-major with j <= i, the order FullStatisticsAccumulator::dump_statistics writes; any pointer
+ * may be NULL */
+aasr_status aasr_scatter_get(const aasr_scatter *h, double *gamma, double *sum_x, double *sum_xx);
+/* Diagnostic, read-only: out[0] the kernel's instance PB (16 PB >= dim + 1), out[1] work items and out[2] launches
+ * of the last aasr_scatter_accumulate_dev call that had rows to add.  Zeros before the first. */
+void aasr_debug_scatter_shape(const aasr_scatter *h, int32_t *out);
+/* Diagnostic: the bound on a launch's slab memory in bytes (default 64 MiB, csrc/scatter.h; at least one item's
+ * slab is always allowed), so that a test reaches several launches with a few thousand rows. */
+aasr_status aasr_debug_scatter_set_slab_bytes(aasr_scatter *h, int64_t bytes);
+
+/* lda.cc:380-446 in double, without LAPACK.  From the sums of the classes with selected[c] != 0, added in class
+ * order: the data mean and covariance, B = sum min(gamma_c, max_gamma) (mu_c - mu)(mu_c - mu)^T and
+ * W = sum min(gamma_c, max_gamma) Sigma_c; the target_dim leading eigenvectors of W^-1 B (from the
+ * Cholesky-reduced symmetric problem, cyclic Jacobi), each of unit Euclidean length as dgeev returns them, as the
+ * columns of P; lda = Lambda^-1/2 V^T P^T with (Lambda, V) the eigen-decomposition of P^T Sigma_data P, so that
+ * lda Sigma_data lda^T = I.  lda is [target_dim x dim], row-major.
+ * Row order and sign, which the reference leaves to LAPACK, are defined here: rows by DESCENDING eigenvalue of
+ * the projected covariance P^T Sigma_data P, and every row's entry of largest magnitude (the first such) is
+ * POSITIVE.
+ * AASR_ERR_INVALID, and no matrix: fewer selected classes than target_dim + 1; a selected class without frames;
+ * a W that is not positive definite; a projected covariance with a non-positive eigenvalue.  Host only. */
+aasr_status aasr_lda_solve(int32_t n_classes, int32_t dim, const double *gamma, const double *sum_x,
+                           const double *sum_xx, const int32_t *selected, double max_gamma, int32_t target_dim,
+                           double *lda);
+/* lda.cc:113-115, 247-263: which states get an accumulator.  The states by falling count -- a tie goes to the
+ * LOWER state index (the reference's std::sort leaves it open) -- the first maxmem 10^6 / (8 dim^2) of them
+ * (at most n_states) with count >= mingamma; then, when n_silence > 0, without the listed states.
+ * selected [n_states] receives 0 / 1.  Host only. */
+aasr_status aasr_lda_select(int32_t n_states, const double *count, double mingamma, int32_t maxmem, int32_t dim,
+                            const int32_t *silence, int32_t n_silence, int32_t *selected);
+
+typedef struct aasr_lda_options {
+  int32_t ophn;         /* -O: read the recipe's alignment= files                       */
+  int32_t info;         /* -i                                                           */
+  int32_t target_dim;   /* -d: must equal the module's dimension                        */
+  int32_t maxmem;       /* -m, in MB: caps the number of states with an accumulator     */
+  int32_t no_silence;   /* --no-silence: without the states of _ and __                 */
+  double mingamma;      /* --mingamma: minimum frame count of a state                   */
+  double maxgamma;      /* --maxgamma: a state's weight in B and W is capped here       */
+  const char *module;   /* -M: the lin_transform module                                 */
+  const char *speakers; /* -S: path of a speaker configuration, or NULL                 */
+  const char *out;      /* -w: the feature configuration to write, or NULL              */
+  double *state_gamma;  /* NULL, or [aasr_topo_num_states]: receives the handle's gamma of every state */
+  double seconds_scatter; /* out: device time of the scatter launches (events)          */
+  double seconds_features; /* out: device time of the feature chain of pass 2 (events)  */
+} aasr_lda_options;
+void aasr_lda_default_options(aasr_lda_options *opt);
+
+/* lda main loop (aku/lda.cc:143-463) over .phn segmentations.  feat_cfg_text: the feature configuration.
+ * Before the device is opened: -M must name a lin_transform module whose configured `dim` equals -d.
+ * Pass 1, host: per-state frame counts from the segmentations, frames past the feature end not counted
+ * (lda.cc:228); the selection (aasr_lda_select).  Pass 2: the features AT THE MODULE'S SOURCE
+ * (lda.cc:105-109, 226, 349) in double on the device under the speaker configuration, one scatter accumulation
+ * per group of utterances with unselected states as class -1.  Then aasr_lda_solve; the matrix becomes the
+ * module's transformation as LinTransformModule::set_transformation_matrix sets it (narrowed to float) and
+ * the configuration is written to opt->out.  A missing _ or __ HMM is AASR_ERR_INVALID. */
+aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr_topo *topo, const char *recipe_path,
+                                aasr_lda_options *opt, aasr_run_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
