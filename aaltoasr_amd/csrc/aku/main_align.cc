@@ -11,13 +11,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../../include/aasr.h"
-#include "conf.hh"
-
-static void die(const std::string &msg) {
-  fprintf(stderr, "exception: %s\n", msg.c_str());
-  exit(1);
-}
+#include "tool_common.hh"
 
 int main(int argc, char *argv[]) {
   aku::conf::Config config;
@@ -44,18 +38,7 @@ int main(int argc, char *argv[]) {
   config.default_parse(argc, argv);
 
   std::string gk, mc, ph;
-  if (config["base"].specified) {
-    const std::string base = config["base"].get_str();
-    gk = base + ".gk";
-    mc = base + ".mc";
-    ph = base + ".ph";
-  } else if (config["gk"].specified && config["mc"].specified && config["ph"].specified) {
-    gk = config["gk"].get_str();
-    mc = config["mc"].get_str();
-    ph = config["ph"].get_str();
-  } else {
-    die("Must give either --base or all --gk, --mc and --ph");
-  }
+  resolve_model_files(config, &gk, &mc, &ph);
   const int device = config["device"].get_int();
   if (device >= 0 && aasr_set_device(device) != AASR_OK) die(aasr_last_error());
 

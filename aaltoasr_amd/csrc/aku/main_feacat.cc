@@ -17,14 +17,9 @@
 #include <string>
 
 #include "FeatureGenerator.hh"
-#include "conf.hh"
 #include "SpeakerConfig.hh"
+#include "tool_common.hh"
 #include "ziggurat.hh"
-
-static void die(const std::string &msg) {
-  fprintf(stderr, "exception: %s\n", msg.c_str());
-  exit(1);
-}
 
 int main(int argc, char *argv[]) {
   // option table of aku/feacat.cc:50-63, grammar of conf.hh

@@ -16,25 +16,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../../include/aasr.h"
-#include "conf.hh"
-
-static void die(const std::string &msg) {
-  fprintf(stderr, "exception: %s\n", msg.c_str());
-  exit(1);
-}
-
-// a speaker file's "model <module>" entries set model-side transforms (ModelTransformer); lda has no model
-static void check_speakers(const std::string &path) {
-  std::ifstream in(path);
-  if (!in) die("could not open " + path);
-  std::string line;
-  while (std::getline(in, line)) {
-    std::istringstream ls(line);
-    std::string first;
-    if (ls >> first && first == "model") die("lda: speaker files with model transforms (" + line + ") are not supported");
-  }
-}
+#include "tool_common.hh"
 
 int main(int argc, char *argv[]) {
   aku::conf::Config config;
@@ -72,7 +54,7 @@ int main(int argc, char *argv[]) {
   if (!config["ph"].specified) die("Must give --ph");
   aasr_topo *topo = nullptr;
   if (aasr_topo_create_from_ph(config["ph"].get_str().c_str(), &topo) != AASR_OK) die(aasr_last_error());
-  if (config["speakers"].specified) check_speakers(config["speakers"].get_str());
+  if (config["speakers"].specified) check_speakers(config["speakers"].get_str(), "lda");
 
   const std::string cfg = config["config"].get_str();
   std::ifstream cin_(cfg);

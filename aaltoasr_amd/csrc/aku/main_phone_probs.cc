@@ -16,13 +16,7 @@
 #include <sstream>
 #include <string>
 
-#include "../../../include/aasr.h"
-#include "conf.hh"
-
-static void die(const std::string &msg) {
-  fprintf(stderr, "exception: %s\n", msg.c_str());
-  exit(1);
-}
+#include "tool_common.hh"
 
 int main(int argc, char *argv[]) {
   // the reference's option table (aku/phone_probs.cc:60-81) and grammar (conf.hh), plus the two
@@ -63,18 +57,7 @@ int main(int argc, char *argv[]) {
   const std::string clusters = config["clusters"].specified ? config["clusters"].get_str() : "";
   const std::string model_cache = config["model-cache"].get_str();
   std::string gk, mc, ph, out_dir;
-  if (config["base"].specified) {
-    const std::string base = config["base"].get_str();
-    gk = base + ".gk";
-    mc = base + ".mc";
-    ph = base + ".ph";
-  } else if (config["gk"].specified && config["mc"].specified && config["ph"].specified) {
-    gk = config["gk"].get_str();
-    mc = config["mc"].get_str();
-    ph = config["ph"].get_str();
-  } else {
-    die("Must give either --base or all --gk, --mc and --ph");
-  }
+  resolve_model_files(config, &gk, &mc, &ph);
   const double eval_minc = config["eval-minc"].get_double(), eval_ming = config["eval-ming"].get_double();
   if (config["output-dir"].specified) out_dir = config["output-dir"].get_str();
   if (config["batch"].specified ^ config["bindex"].specified) die("Must give both --batch and --bindex");

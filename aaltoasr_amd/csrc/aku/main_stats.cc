@@ -16,73 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/aasr.h"
-#include "conf.hh"
-
-static void die(const std::string &msg) {
-  fprintf(stderr, "exception: %s\n", msg.c_str());
-  exit(1);
-}
-
-// PDFPool::read_gk's header and per-Gaussian tags, without the values: diagonal pools only
-static void check_pool(const std::string &gk) {
-  std::ifstream in(gk);
-  if (!in) die("could not open " + gk);
-  int size = 0, dim = 0;
-  std::string kind;
-  in >> size >> dim >> kind;
-  if (!in) die("could not read the header of " + gk);
-  if (kind == "diagonal_cov") return;
-  if (kind != "variable") die("stats: only diagonal Gaussians are supported (" + gk + " is a " + kind + " pool)");
-  std::string tag, value;
-  for (int g = 0; g < size; g++) {
-    if (!(in >> tag)) die("could not read " + gk);
-    if (tag != "diag")
-      die("stats: only diagonal Gaussians are supported (" + gk + " holds '" + tag + "' Gaussians)");
-    for (int i = 0; i < 2 * dim; i++) in >> value;
-  }
-}
-
-// a speaker file's "model <module>" entries set model-side transforms (ModelTransformer)
-static void check_speakers(const std::string &path) {
-  std::ifstream in(path);
-  if (!in) die("could not open " + path);
-  std::string line;
-  while (std::getline(in, line)) {
-    std::istringstream ls(line);
-    std::string first;
-    if (ls >> first && first == "model")
-      die("stats: speaker files with model transforms (" + line + ") are not supported");
-  }
-}
-
-// recipe lines with start-line / end-line, refused as align refuses them
-static void check_recipe(const std::string &path, int num_batches, int batch_index) {
-  std::ifstream in(path);
-  if (!in) die("could not open " + path);
-  std::stringstream ss;
-  ss << in.rdbuf();
-  char *table = nullptr;
-  int64_t len = 0;
-  if (aasr_recipe_read_all(ss.str().c_str(), num_batches, batch_index, 0, &table, &len) != AASR_OK)
-    die(aasr_last_error());
-  const std::string t(table, (size_t)len);
-  aasr_free(table);
-  std::istringstream lines(t);
-  std::string line;
-  while (std::getline(lines, line)) {
-    std::vector<std::string> fl;
-    size_t a = 0;
-    for (;;) {
-      const size_t b = line.find('\x1f', a);
-      fl.push_back(line.substr(a, b == std::string::npos ? std::string::npos : b - a));
-      if (b == std::string::npos) break;
-      a = b + 1;
-    }
-    if (fl.size() == 13 && (atoi(fl[9].c_str()) > 0 || atoi(fl[10].c_str()) > 0))
-      die("stats: recipe line limits (start-line / end-line) are not supported");
-  }
-}
+#include "tool_common.hh"
 
 int main(int argc, char *argv[]) {
   aku::conf::Config config;
@@ -140,23 +74,13 @@ int main(int argc, char *argv[]) {
     if (config[r[0]].specified) die(std::string("stats: ") + r[1] + " is not supported; only --ml over .phn files is");
 
   std::string gk, mc, ph;
-  if (config["base"].specified) {
-    const std::string base = config["base"].get_str();
-    gk = base + ".gk";
-    mc = base + ".mc";
-    ph = base + ".ph";
-  } else if (config["gk"].specified && config["mc"].specified && config["ph"].specified) {
-    gk = config["gk"].get_str();
-    mc = config["mc"].get_str();
-    ph = config["ph"].get_str();
-  } else {
-    die("Must give either --base or all --gk, --mc and --ph");
-  }
+  resolve_model_files(config, &gk, &mc, &ph);
   if (config["batch"].specified ^ config["bindex"].specified) die("Must give both --batch and --bindex");
   if (!config["ml"].specified) die("At least one mode (--ml, --mmi, --mpe) must be given!");
-  check_pool(gk);
-  if (config["speakers"].specified) check_speakers(config["speakers"].get_str());
-  check_recipe(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int());
+  check_pool(gk, "stats");
+  if (config["speakers"].specified) check_speakers(config["speakers"].get_str(), "stats");
+  check_recipe_line_limits(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int(), false,
+                           "stats");
 
   const int device = config["device"].get_int();
   if (device >= 0 && aasr_set_device(device) != AASR_OK) die(aasr_last_error());

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "ph_parse.h"
 #include "phn_line.h"
+#include "recipe_pass.h"
 
 struct aasr_topo {
   struct Hmm {
@@ -512,59 +513,12 @@ aasr_status aasr_align_batch_result(const aasr_align_batch *b, int32_t u, int32_
 
 namespace aasr {
 
+// what align adds to a recipe line
 struct AlignUtt {
-  std::string audio, transcript, alignment, speaker, utterance;
-  float start_time = 0, end_time = 0;
-  int start_line = 0, end_line = 0;
+  RecipeInfo info;
   int start_frame = 0, end_frame = 0, eof_frame = 0, rows = 0;
   Transcript tr;
 };
-
-static std::vector<AlignUtt> read_align_recipe(const char *recipe_path, int num_batches, int batch_index) {
-  FILE *f = fopen(recipe_path, "rb");
-  if (!f) raise(AASR_ERR_IO, "could not open recipe %s", recipe_path);
-  std::string text;
-  char buf[4096];
-  size_t n;
-  while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
-  fclose(f);
-  char *table = nullptr;
-  int64_t len = 0;
-  // align reads its recipe with cluster_speakers = true (aku/align.cc:237-239)
-  if (aasr_recipe_read_all(text.c_str(), num_batches, batch_index, 1, &table, &len) != AASR_OK)
-    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-  const std::string t(table, (size_t)len);
-  aasr_free(table);
-  std::vector<AlignUtt> out;
-  size_t pos = 0;
-  while (pos < t.size()) {
-    size_t eol = t.find('\n', pos);
-    if (eol == std::string::npos) eol = t.size();
-    std::vector<std::string> fl;
-    size_t a = pos;
-    while (a <= eol) {
-      size_t b = t.find('\x1f', a);
-      if (b == std::string::npos || b > eol) b = eol;
-      fl.push_back(t.substr(a, b - a));
-      a = b + 1;
-    }
-    if (fl.size() == 13) {
-      AlignUtt u;
-      u.audio = fl[0];
-      u.transcript = fl[2];
-      u.alignment = fl[3];
-      u.start_time = (float)atof(fl[7].c_str());
-      u.end_time = (float)atof(fl[8].c_str());
-      u.start_line = atoi(fl[9].c_str());
-      u.end_line = atoi(fl[10].c_str());
-      u.speaker = fl[11];
-      u.utterance = fl[12];
-      out.push_back(u);
-    }
-    pos = eol + 1;
-  }
-  return out;
-}
 
 // the printing half of align.cc:viterbi_align over the committed positions of one utterance
 static void write_alignment(const aasr_topo *topo, const AlignUtt &u, float frame_rate, bool print_all_states,
@@ -589,8 +543,8 @@ static void write_alignment(const aasr_topo *topo, const AlignUtt &u, float fram
       }
     }
   }
-  FILE *f = fopen(u.alignment.c_str(), "w");
-  if (!f) raise(AASR_ERR_IO, "could not open %s for writing", u.alignment.c_str());
+  FILE *f = fopen(u.info.alignment_path.c_str(), "w");
+  if (!f) raise(AASR_ERR_IO, "could not open %s for writing", u.info.alignment_path.c_str());
   std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
   char line[4096];
   std::string out;
@@ -619,7 +573,7 @@ static void write_alignment(const aasr_topo *topo, const AlignUtt &u, float fram
   }
   if (finished) emit(print_start, u.start_frame + n_committed + 1);
   if (!out.empty() && fwrite(out.data(), 1, out.size(), f) != out.size())
-    raise(AASR_ERR_IO, "write error on %s", u.alignment.c_str());
+    raise(AASR_ERR_IO, "write error on %s", u.info.alignment_path.c_str());
 }
 
 }  // namespace aasr
@@ -635,10 +589,13 @@ extern "C" aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, con
       const aasr_status st = aasr_topo_validate(topo, gmm);
       if (st != AASR_OK) raise(st, "%s", last_error().c_str());
     }
-    if (aasr_gmm_dim(gmm) != aasr_feat_dim(feat))
-      raise(AASR_ERR_INVALID, "gaussian dimension is %d but feature dimension is %d", aasr_gmm_dim(gmm),
-            aasr_feat_dim(feat));
-    std::vector<AlignUtt> utts = read_align_recipe(recipe_path, opt->num_batches, opt->batch_index);
+    check_feature_dim(gmm, feat);
+    // align reads its recipe with cluster_speakers = true (aku/align.cc:237-239)
+    std::vector<AlignUtt> utts;
+    for (RecipeInfo &info : read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, true)) {
+      utts.emplace_back();
+      utts.back().info = std::move(info);
+    }
     const float fr = aasr_feat_frame_rate(feat);
     const int S = aasr_gmm_num_states(gmm), D = aasr_gmm_dim(gmm);
     const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
@@ -665,29 +622,27 @@ extern "C" aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, con
       std::vector<float> feats32;
       while (next < utts.size() && group.size() < 256) {
         AlignUtt &u = utts[next];
-        if (u.start_line > 0 || u.end_line > 0)
+        const RecipeInfo &info = u.info;
+        if (info.start_line > 0 || info.end_line > 0)  // (here, not up front: the groups before this line are written)
           raise(AASR_ERR_UNSUPPORTED, "align: recipe line limits (start-line / end-line) are not supported");
         if (opt->speakers) {
-          if (aasr_spkc_set_speaker(opt->speakers, u.speaker.c_str()) != AASR_OK)
+          if (aasr_spkc_set_speaker(opt->speakers, info.speaker_id.c_str()) != AASR_OK)
             raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          if (!u.utterance.empty() && aasr_spkc_set_utterance(opt->speakers, u.utterance.c_str()) != AASR_OK)
+          if (!info.utterance_id.empty() && aasr_spkc_set_utterance(opt->speakers, info.utterance_id.c_str()) != AASR_OK)
             raise(AASR_ERR_INVALID, "%s", aasr_last_error());
         }
         int16_t *pcm = nullptr;
         int64_t n_samples = 0;
         int32_t rate = 0;
-        if (aasr_audio_read(feat, u.audio.c_str(), &pcm, &n_samples, &rate) != AASR_OK)
+        if (aasr_audio_read(feat, info.audio_path.c_str(), &pcm, &n_samples, &rate) != AASR_OK)
           raise(AASR_ERR_IO, "%s", aasr_last_error());
         std::unique_ptr<int16_t, void (*)(int16_t *)> pguard(pcm, [](int16_t *p) { aasr_free(p); });
         u.eof_frame = aasr_feat_eof_frame(feat, n_samples);
-        int first = 0, last = 0;
-        if (u.start_time > 0 || u.end_time > 0) {
-          first = (int)(u.start_time * fr);
-          last = (int)(u.end_time * fr);
-        }
+        int first, last;
+        frame_range(info, fr, &first, &last);
         u.start_frame = first;
-        u.end_frame = (int)(u.end_time * fr);
-        u.tr = read_transcript(topo, u.transcript.c_str(), fr, first, last);
+        u.end_frame = (int)(info.end_time * fr);
+        u.tr = read_transcript(topo, info.transcript_path.c_str(), fr, first, last);
         int stop = u.eof_frame;
         if (u.end_frame > 0) stop = std::min(stop, u.end_frame);
         u.rows = std::max(1, stop - u.start_frame);
@@ -756,28 +711,21 @@ extern "C" aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, con
           raise(AASR_ERR_INVALID, "%s", aasr_last_error());
         if (status == ALIGN_ERROR)
           raise(AASR_ERR_INVALID, "align: the search failed on %s (transcription or pruning does not fit the audio)",
-                u.audio.c_str());
+                u.info.audio_path.c_str());
         if (curr_beam != orig_beam) {
           std::cerr << "Restoring original beam " << orig_beam << " and original state beam " << orig_sbeam
                     << std::endl;
           curr_beam = orig_beam;
           curr_sbeam = orig_sbeam;
         }
-        auto processing = [&] {
-          if (opt->info > 0) {
-            fprintf(stderr, "Processing file: %s", u.audio.c_str());
-            if (u.start_time || u.end_time) fprintf(stderr, " (%.2f-%.2f)", u.start_time, u.end_time);
-            fprintf(stderr, "\n");
-          }
-        };
-        processing();
+        announce(u.info, opt->info);
         for (int i = 0; i < n_fail; i++) {
           curr_beam *= 2;
           curr_sbeam *= 2;
           std::cerr << "Too low beams, doubling to beam " << curr_beam << " and state beam " << curr_sbeam
                     << std::endl;
           if (curr_beam <= opt->maxbeam)
-            processing();
+            announce(u.info, opt->info);
           else
             std::cerr << "Have to stop trying, beam already over max" << std::endl;
         }
@@ -795,12 +743,6 @@ extern "C" aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, con
         frames_total += n_committed;
       }
     }
-    if (stats) {
-      stats->utterances = (int64_t)utts.size();
-      stats->frames = frames_total;
-      stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      stats->seconds_device = 0;
-      stats->seconds_copy_out = 0;
-    }
+    fill_run_stats(stats, (int64_t)utts.size(), frames_total, t0, 0);
   });
 }

@@ -9,17 +9,14 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <fstream>
-#include <iterator>
 #include <memory>
 #include <numeric>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "feat.h"
-#include "pipeline.h"
+#include "recipe_pass.h"
 #include "scatter.h"
 
 using namespace aasr;
@@ -483,17 +480,8 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
       silence.insert(silence.end(), st.begin(), st.end());
     }
     const int S = aasr_topo_num_states(topo);
-    std::vector<RecipeInfo> infos;
-    {
-      std::ifstream rin(recipe_path);
-      if (!rin) raise(AASR_ERR_IO, "could not open recipe %s", recipe_path);
-      std::stringstream ss;
-      ss << rin.rdbuf();
-      infos = recipe_read(ss.str(), 1, 1, true);  // lda.cc:144
-    }
-    for (const RecipeInfo &u : infos)
-      if (u.start_line > 0 || u.end_line > 0)
-        raise(AASR_ERR_UNSUPPORTED, "lda: recipe line limits (start-line / end-line) are not supported");
+    const std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, 1, 1, true);  // lda.cc:144
+    refuse_line_limits(infos, "lda");
 
     // ---- the device
     std::unique_ptr<aasr_feat> feat(feat_create(feat_cfg_text));
@@ -517,58 +505,14 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
     const float fr = aasr_feat_frame_rate(feat.get());
 
     // ---- pass 1: the states' frame counts, from the segmentations and the audio lengths
-    struct Utt {
-      int32_t start = 0;
-      std::vector<int32_t> pdf;
-    };
-    std::vector<Utt> utts(infos.size());
+    const TopoTables tt(topo);
+    std::vector<Segmentation> utts(infos.size());
     std::vector<double> count((size_t)S, 0.0);
-    auto read_audio = [&](const RecipeInfo &u, std::vector<int16_t> &out) {
-      int16_t *pcm = nullptr;
-      int64_t n_samples = 0;
-      int32_t rate = 0;
-      if (aasr_feat_input_is_features(feat.get())) {
-        std::ifstream in(u.audio_path, std::ios::binary);
-        if (!in) raise(AASR_ERR_IO, "could not open %s", u.audio_path.c_str());
-        const std::string bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-        if (aasr_audio_decode(feat.get(), bytes.data(), (int64_t)bytes.size(), &pcm, &n_samples, &rate) != AASR_OK)
-          raise(AASR_ERR_IO, "%s: %s", u.audio_path.c_str(), aasr_last_error());
-      } else if (aasr_audio_read(feat.get(), u.audio_path.c_str(), &pcm, &n_samples, &rate) != AASR_OK) {
-        raise(AASR_ERR_IO, "%s", aasr_last_error());
-      }
-      out.assign(pcm, pcm + n_samples);
-      aasr_free(pcm);
-    };
-    auto announce = [&](const RecipeInfo &u) {
-      if (opt->info <= 0) return;
-      fprintf(stderr, "Processing file: %s", u.audio_path.c_str());
-      if (u.start_time || u.end_time) fprintf(stderr, " (%.2f-%.2f)", u.start_time, u.end_time);
-      fprintf(stderr, "\n");
-    };
-    std::vector<int16_t> pcm;
     for (size_t f = 0; f < infos.size(); f++) {
       const RecipeInfo &u = infos[f];
-      announce(u);
-      read_audio(u, pcm);
-      const int eof = aasr_feat_eof_frame(feat.get(), (int64_t)pcm.size());
-      int first = 0, last = 0;
-      if (u.start_time > 0 || u.end_time > 0) {
-        first = (int)(u.start_time * fr);
-        last = (int)(u.end_time * fr);
-      }
-      int32_t *seg_pdf = nullptr, *seg_tr = nullptr, n = 0, start = 0;
-      if (aasr_stats_read_segmentation(topo, (opt->ophn ? u.alignment_path : u.transcript_path).c_str(), fr, first, last, eof, 0,
-                                       &start, &seg_pdf, &seg_tr, &n) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      if (n < 0) {  // lda.cc:212-218
-        fprintf(stderr, "Could not initialize the utterance for PhnReader.");
-        fprintf(stderr, "Current file was: %s\n", u.audio_path.c_str());
-        n = 0;
-      }
-      utts[f].start = start;
-      utts[f].pdf.assign(seg_pdf, seg_pdf + n);
-      aasr_free(seg_pdf);
-      aasr_free(seg_tr);
+      announce(u, opt->info);
+      const int eof = aasr_feat_eof_frame(feat.get(), (int64_t)load_utterance_input(feat.get(), u).size());
+      utts[f] = read_state_sequence(topo, tt, u, opt->ophn != 0, fr, eof);
       for (int32_t s : utts[f].pdf) {
         if (s >= S) raise(AASR_ERR_INVALID, "%s: state %d outside the model", u.transcript_path.c_str(), s);
         if (s >= 0) count[(size_t)s] += 1;
@@ -593,9 +537,8 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
       if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
     }
     std::unique_ptr<aasr_scatter, void (*)(aasr_scatter *)> hguard(h, aasr_scatter_destroy);
-    hipStream_t stream;
-    AASR_HIP(hipStreamCreate(&stream));
-    std::unique_ptr<void, void (*)(void *)> sguard((void *)stream, [](void *s) { (void)hipStreamDestroy((hipStream_t)s); });
+    GroupStager stager(feat.get(), spk, source);
+    const hipStream_t stream = stager.stream;
     hipEvent_t ev[3];
     for (hipEvent_t &e : ev) AASR_HIP(hipEventCreate(&e));
     struct EvGuard {
@@ -604,61 +547,36 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
         for (int i = 0; i < 3; i++) (void)hipEventDestroy(e[i]);
       }
     } evguard{ev};
-    if (spk) spkc_set_before_change(spk, [stream]() { AASR_HIP(hipStreamSynchronize(stream)); });
-    DevBuf<int16_t> d_pcm;
-    DevBuf<double> d_x;
     const int64_t max_group_frames = (int64_t)1 << 18;
     int64_t num_frames = 0;
     size_t next = 0;
     while (next < infos.size()) {
       const size_t group_first = next;
       std::vector<std::vector<int16_t>> audio;
+      std::vector<int32_t> start, rows, cls;
       int64_t rows_total = 0;
-      size_t samples = 1;
       while (next < infos.size() && audio.size() < 1024 && rows_total < max_group_frames) {
-        announce(infos[next]);
+        const Segmentation &ut = utts[next];
+        announce(infos[next], opt->info);
         audio.emplace_back();
-        if (!utts[next].pdf.empty()) read_audio(infos[next], audio.back());
-        rows_total += (int64_t)utts[next].pdf.size();
-        samples += audio.back().size();
+        if (!ut.pdf.empty()) audio.back() = load_utterance_input(feat.get(), infos[next]);
+        start.push_back(ut.start_frame);
+        rows.push_back((int32_t)ut.pdf.size());
+        for (int32_t s : ut.pdf) cls.push_back(s >= 0 && selected[(size_t)s] ? s : -1);
+        rows_total += (int64_t)ut.pdf.size();
         next++;
       }
-      d_x.ensure((size_t)std::max<int64_t>(1, rows_total) * D);
-      if (samples > d_pcm.n) {
-        AASR_HIP(hipStreamSynchronize(stream));
-        d_pcm.alloc(samples);
-      }
-      std::vector<int32_t> cls;
-      cls.reserve((size_t)rows_total);
-      size_t pcm_at = 0;
-      int64_t row = 0;
-      AASR_HIP(hipEventRecord(ev[0], stream));
-      for (size_t gi = 0; gi < audio.size(); gi++) {
-        const RecipeInfo &u = infos[group_first + gi];
-        const Utt &ut = utts[group_first + gi];
-        if (spk) {  // lda.cc:284-289; a parameter change waits for the queued features
-          if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        }
-        const int64_t n = (int64_t)ut.pdf.size();
-        if (n > 0) {
-          const std::vector<int16_t> &a = audio[gi];
-          if (!a.empty())
-            AASR_HIP(hipMemcpyAsync(d_pcm.p + pcm_at, a.data(), a.size() * sizeof(int16_t), hipMemcpyHostToDevice, stream));
-          UttBatch b;
-          b.n_utts = 1;
-          b.frame_off = {0, n};
-          b.pcm_off = {0, (int64_t)a.size()};
-          b.first = {ut.start};
-          feat_run_batch(feat.get(), d_pcm.p + pcm_at, b, source, nullptr, d_x.p + (size_t)row * D, stream);
-          pcm_at += a.size();
-        }
-        for (int32_t s : ut.pdf) cls.push_back(s >= 0 && selected[(size_t)s] ? s : -1);
-        row += n;
-      }
+      stager.stage(audio, start, rows, [&](size_t i) {
+        if (i == 0) AASR_HIP(hipEventRecord(ev[0], stream));  // the features' interval opens once the buffers stand
+        if (!spk) return;
+        // lda.cc:284-289; a parameter change waits for the queued features
+        const RecipeInfo &u = infos[group_first + i];
+        if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      });
       AASR_HIP(hipEventRecord(ev[1], stream));
-      if (rows_total > 0 && aasr_scatter_accumulate_dev(h, d_x.p, rows_total, cls.data(), nullptr, stream) != AASR_OK)
+      if (rows_total > 0 && aasr_scatter_accumulate_dev(h, stager.d_x.p, rows_total, cls.data(), nullptr, stream) != AASR_OK)
         raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       AASR_HIP(hipEventRecord(ev[2], stream));
       AASR_HIP(hipStreamSynchronize(stream));  // the group's host audio goes out of scope
@@ -669,7 +587,6 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
       opt->seconds_scatter += ms * 1e-3;
       num_frames += rows_total;
     }
-    if (spk) spkc_set_before_change(spk, nullptr);
 
     // ---- the LDA (lda.cc:375-462)
     if (opt->info > 0) {
@@ -695,17 +612,8 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
     ltm->d_matrix.upload(ltm->matrix.data(), ltm->matrix.size());
     if (opt->out) {
       const std::string text = feat_write_configuration(feat.get());
-      std::ofstream of(opt->out, std::ios::binary);
-      if (!of) raise(AASR_ERR_IO, "could not open %s for writing", opt->out);
-      of.write(text.data(), (std::streamsize)text.size());
-      if (!of) raise(AASR_ERR_IO, "write error on %s", opt->out);
+      write_text_file(opt->out, text.data(), text.size());
     }
-    if (stats) {
-      stats->utterances = (int64_t)infos.size();
-      stats->frames = num_frames;
-      stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      stats->seconds_device = opt->seconds_scatter + opt->seconds_features;
-      stats->seconds_copy_out = 0;
-    }
+    fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, opt->seconds_scatter + opt->seconds_features);
   });
 }

@@ -9,8 +9,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <fstream>
-#include <iterator>
 #include <memory>
 #include <set>
 #include <sstream>
@@ -21,7 +19,7 @@
 #include "feat.h"
 #include "gmm.h"
 #include "mllr.h"
-#include "pipeline.h"
+#include "recipe_pass.h"
 
 using namespace aasr;
 
@@ -370,23 +368,13 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
       raise(AASR_ERR_INVALID, "aasr_run_mllr_recipe: null argument");
     const auto t0 = std::chrono::steady_clock::now();
     aasr_spkc *spk = opt->speakers;
-    std::vector<RecipeInfo> infos;
-    {
-      std::ifstream rin(recipe_path);
-      if (!rin) raise(AASR_ERR_IO, "could not open recipe %s", recipe_path);
-      std::stringstream ss;
-      ss << rin.rdbuf();
-      // Recipe::read with cluster_speakers = true, then sort_infos (aku/mllr.cc:213-216)
-      infos = recipe_read(ss.str(), opt->num_batches, opt->batch_index, true);
-      std::stable_sort(infos.begin(), infos.end(),
-                       [](const RecipeInfo &a, const RecipeInfo &b) { return a.speaker_id < b.speaker_id; });
-    }
-    for (const RecipeInfo &u : infos)
-      if (u.start_line > 0 || u.end_line > 0)
-        raise(AASR_ERR_UNSUPPORTED, "mllr: recipe line limits (start-line / end-line) are not supported");
+    // Recipe::read with cluster_speakers = true, then sort_infos (aku/mllr.cc:213-216)
+    std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, true);
+    std::stable_sort(infos.begin(), infos.end(),
+                     [](const RecipeInfo &a, const RecipeInfo &b) { return a.speaker_id < b.speaker_id; });
+    refuse_line_limits(infos, "mllr");
     const int D = aasr_gmm_dim(gmm);
-    if (D != aasr_feat_dim(feat))
-      raise(AASR_ERR_INVALID, "gaussian dimension is %d but feature dimension is %d", D, aasr_feat_dim(feat));
+    check_feature_dim(gmm, feat);
     const bool global_transform = opt->module && opt->module[0];
     FeatModule *ltm = nullptr;
     std::string module;
@@ -407,19 +395,10 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
       if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
     }
     std::unique_ptr<aasr_mllr, void (*)(aasr_mllr *)> hguard(h, aasr_mllr_destroy);
+    const TopoTables tt(topo);
     const float fr = aasr_feat_frame_rate(feat);
-    hipStream_t stream;
-    AASR_HIP(hipStreamCreate(&stream));
-    std::unique_ptr<void, void (*)(void *)> sguard((void *)stream, [](void *s) { (void)hipStreamDestroy((hipStream_t)s); });
-    // a change of feature parameters waits for the features queued with the old ones
-    struct Unhook {
-      aasr_spkc *s;
-      ~Unhook() { spkc_set_before_change(s, nullptr); }
-    } unhook{spk};
-    spkc_set_before_change(spk, [stream]() { AASR_HIP(hipStreamSynchronize(stream)); });
-
-    DevBuf<int16_t> d_pcm;
-    DevBuf<double> d_x;
+    GroupStager stager(feat, spk);
+    const hipStream_t stream = stager.stream;
     const int64_t max_group_frames = (int64_t)1 << 18;
     std::set<std::string> updated;
     std::string cur_speaker;
@@ -467,11 +446,6 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
       have_trainer = false;
     };
 
-    struct Pending {
-      std::vector<int16_t> pcm;
-      int32_t start_frame = 0;
-      std::vector<int32_t> pdf;
-    };
     size_t next = 0;
     while (next < infos.size()) {
       if (infos[next].speaker_id.empty()) raise(AASR_ERR_INVALID, "Speaker ID is missing");
@@ -484,93 +458,37 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
         if (aasr_spkc_set_speaker(spk, cur_speaker.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       }
       // a group: utterances of this speaker, their frames in one device buffer, one accumulation
-      std::vector<Pending> group;
-      int64_t rows_total = 0;
-      size_t samples = 1;
       const size_t group_first = next;
-      while (next < infos.size() && infos[next].speaker_id == cur_speaker && group.size() < 1024 &&
+      std::vector<std::vector<int16_t>> audio;
+      std::vector<int32_t> start, rows, pdfs;
+      int64_t rows_total = 0;
+      while (next < infos.size() && infos[next].speaker_id == cur_speaker && audio.size() < 1024 &&
              rows_total < max_group_frames) {
         const RecipeInfo &u = infos[next];
-        if (opt->info > 0) {
-          fprintf(stderr, "Processing file: %s (%d/%d)", u.audio_path.c_str(), (int)next + 1, (int)infos.size());
-          if (u.start_time || u.end_time) fprintf(stderr, " (%.2f-%.2f)", u.start_time, u.end_time);
-          fprintf(stderr, "\n");
-        }
-        int16_t *pcm = nullptr;
-        int64_t n_samples = 0;
-        int32_t rate = 0;
-        if (aasr_feat_input_is_features(feat)) {
-          std::ifstream in(u.audio_path, std::ios::binary);
-          if (!in) raise(AASR_ERR_IO, "could not open %s", u.audio_path.c_str());
-          const std::string bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-          if (aasr_audio_decode(feat, bytes.data(), (int64_t)bytes.size(), &pcm, &n_samples, &rate) != AASR_OK)
-            raise(AASR_ERR_IO, "%s: %s", u.audio_path.c_str(), aasr_last_error());
-        } else if (aasr_audio_read(feat, u.audio_path.c_str(), &pcm, &n_samples, &rate) != AASR_OK) {
-          raise(AASR_ERR_IO, "%s", aasr_last_error());
-        }
-        Pending pd;
-        pd.pcm.assign(pcm, pcm + n_samples);
-        aasr_free(pcm);
-        const int eof = aasr_feat_eof_frame(feat, n_samples);
-        int first = 0, last = 0;
-        if (u.start_time > 0 || u.end_time > 0) {
-          first = (int)(u.start_time * fr);
-          last = (int)(u.end_time * fr);
-        }
-        int32_t *seg_pdf = nullptr, *seg_tr = nullptr, n = 0, start = 0;
-        if (aasr_stats_read_segmentation(topo, (opt->ophn ? u.alignment_path : u.transcript_path).c_str(), fr, first, last, eof,
-                                         0, &start, &seg_pdf, &seg_tr, &n) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        if (n < 0) {  // get_segmentator (aku/mllr.cc:111-115)
-          fprintf(stderr, "Could not initialize the utterance for PhnReader.");
-          fprintf(stderr, "Current file was: %s\n", u.audio_path.c_str());
-          pd.pcm.clear();
-          n = 0;
-        }
-        pd.start_frame = start;
+        announce(u, opt->info, (int)next, (int)infos.size());
+        audio.push_back(load_utterance_input(feat, u));
         // train_mllr hands the segmentator's PDF index to model.state() and takes that state's emission_pdf
         // (aku/mllr.cc:136-140): a double lookup.  In the .ph files this engine reads a state's emission pdf is the
         // state's own index (HmmSet::read_ph, legacy format) and the engine takes state == pdf throughout, so
         // both lookups are the identity here and the segmentation's index is used as it is.
-        pd.pdf.assign(seg_pdf, seg_pdf + n);
-        aasr_free(seg_pdf);
-        aasr_free(seg_tr);
-        rows_total += n;
-        samples += pd.pcm.size();
-        group.push_back(std::move(pd));
+        const Segmentation seg =
+            read_state_sequence(topo, tt, u, opt->ophn != 0, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()));
+        if (!seg.initialized) audio.back().clear();
+        start.push_back(seg.start_frame);
+        rows.push_back((int32_t)seg.pdf.size());
+        pdfs.insert(pdfs.end(), seg.pdf.begin(), seg.pdf.end());
+        rows_total += (int64_t)seg.pdf.size();
         next++;
       }
-      d_x.ensure((size_t)std::max<int64_t>(1, rows_total) * D);
-      if (samples > d_pcm.n) {
-        AASR_HIP(hipStreamSynchronize(stream));
-        d_pcm.alloc(samples);
-      }
-      std::vector<int32_t> pdfs;
-      pdfs.reserve((size_t)rows_total);
-      size_t pcm_at = 0;
-      int64_t row = 0;
-      for (size_t gi = 0; gi < group.size(); gi++) {
-        Pending &pd = group[gi];
-        const RecipeInfo &u = infos[group_first + gi];
+      // the frames carry the speaker's CURRENT transform, as the reference's feature generator does
+      stager.stage(audio, start, rows, [&](size_t i) {
         // set_utterance per line (aku/mllr.cc:289-290); a parameter change waits for the queued features
+        const RecipeInfo &u = infos[group_first + i];
         if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
           raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        const int64_t n = (int64_t)pd.pdf.size();
-        if (n > 0) {
-          if (!pd.pcm.empty())
-            AASR_HIP(hipMemcpyAsync(d_pcm.p + pcm_at, pd.pcm.data(), pd.pcm.size() * sizeof(int16_t), hipMemcpyHostToDevice,
-                                    stream));
-          // the frames carry the speaker's CURRENT transform, as the reference's feature generator does
-          if (aasr_feat_run_f64_dev(feat, d_pcm.p + pcm_at, (int64_t)pd.pcm.size(), pd.start_frame, (int32_t)n,
-                                    d_x.p + (size_t)row * D, stream) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          pcm_at += pd.pcm.size();
-        }
-        pdfs.insert(pdfs.end(), pd.pdf.begin(), pd.pdf.end());
-        row += n;
-      }
+      });
       if (rows_total > 0) {
-        if (aasr_mllr_accumulate_dev(h, d_x.p, rows_total, pdfs.data(), stream) != AASR_OK)
+        if (aasr_mllr_accumulate_dev(h, stager.d_x.p, rows_total, pdfs.data(), stream) != AASR_OK)
           raise(AASR_ERR_INVALID, "%s", aasr_last_error());
         AASR_HIP(hipStreamSynchronize(stream));  // the group's host audio and pdfs go out of scope
       }
@@ -593,17 +511,8 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
       if (aasr_spkc_write_text(spk, sp.data(), n_sp, nullptr, n_ut, &text, &len) != AASR_OK)
         raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       std::unique_ptr<char, void (*)(void *)> tguard(text, free);
-      std::ofstream of(opt->out, std::ios::binary);
-      if (!of) raise(AASR_ERR_IO, "could not open %s for writing", opt->out);
-      of.write(text, (std::streamsize)len);
-      if (!of) raise(AASR_ERR_IO, "write error on %s", opt->out);
+      write_text_file(opt->out, text, (size_t)len);
     }
-    if (stats) {
-      stats->utterances = (int64_t)infos.size();
-      stats->frames = num_frames;
-      stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      stats->seconds_device = 0;
-      stats->seconds_copy_out = 0;
-    }
+    fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
   });
 }

@@ -1,7 +1,7 @@
-// stats.cc -- ML statistics collection (aku/stats.cc with --ml over .phn segmentations): the
-// segmentation reader (PhnReader::next_frame as stats configures it), the statistics handle that
-// drives the device accumulation (stats_accum.hip), the dump writers of HmmSet::dump_statistics and
-// the stats main loop over a recipe (aasr_run_stats_recipe, stats.cc:73-170, 540-620, 740-795).
+// stats.cc -- ML statistics collection (aku/stats.cc with --ml over .phn segmentations): the statistics
+// handle that drives the device accumulation (stats_accum.hip), the dump writers of
+// HmmSet::dump_statistics and the stats main loop over a recipe (aasr_run_stats_recipe,
+// stats.cc:73-170, 540-620, 740-795).  The segmentation reader is recipe_pass.cc's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,15 +10,13 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
-#include <iterator>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "gmm.h"
-#include "phn_line.h"
-#include "pipeline.h"
+#include "recipe_pass.h"
 #include "stats.h"
 
 using namespace aasr;
@@ -26,111 +24,6 @@ using namespace aasr;
 namespace aasr {
 
 static double safe_log(double x) { return x < 1e-50 ? std::log(1e-50) : std::log(x); }
-
-// What the segmentation reader needs of the topology: per HMM its states, per state its
-// transitions' target offsets and the global index of its first transition (HmmSet::read_ph numbers
-// transitions state by state, HmmSet.cc:319-328).
-struct TopoTables {
-  std::vector<std::vector<int32_t>> hmm_states;
-  std::vector<std::vector<int32_t>> offsets;
-  std::vector<std::vector<double>> probs;
-  std::vector<int32_t> tr_base;
-  int32_t n_transitions = 0;
-  explicit TopoTables(const aasr_topo *topo) {
-    const int H = aasr_topo_num_hmms(topo), S = aasr_topo_num_states(topo);
-    hmm_states.resize((size_t)std::max(0, H));
-    for (int h = 0; h < H; h++) {
-      hmm_states[(size_t)h].resize((size_t)std::max(0, aasr_topo_hmm_num_states(topo, h)));
-      if (aasr_topo_hmm_states(topo, h, hmm_states[(size_t)h].data()) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-    }
-    offsets.resize((size_t)std::max(0, S));
-    probs.resize((size_t)std::max(0, S));
-    for (int s = 0; s < S; s++) {
-      const int n = aasr_topo_state_num_transitions(topo, s);
-      offsets[(size_t)s].resize((size_t)n);
-      probs[(size_t)s].resize((size_t)n);
-      if (aasr_topo_state_transitions(topo, s, offsets[(size_t)s].data(), probs[(size_t)s].data()) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      tr_base.push_back(n_transitions);
-      n_transitions += n;
-    }
-  }
-};
-
-struct Segmentation {
-  bool initialized = false;  // init_utterance_segmentation succeeded
-  int32_t start_frame = 0;   // frame of pdf[0]
-  std::vector<int32_t> pdf;  // per frame
-  std::vector<int32_t> tr;   // per frame: global transition index, -1: none
-};
-
-// PhnReader::next_frame (aku/PhnReader.cc:138-292) with state_num_labels = false and
-// relative_sample_numbers = false, driven as stats.cc:simple_train drives it: frames until the
-// reader's end, the frame loop leaving at eof_frame (< 0: no limit) after next_frame has run for it.
-static Segmentation read_segmentation(const aasr_topo *topo, const TopoTables &tt, const char *path, float frame_rate,
-                                      int first_frame, int last_frame, int eof_frame, bool transitions) {
-  FILE *f = fopen(path, "r");
-  if (!f) raise(AASR_ERR_IO, "PhnReader::open(): could not open %s", path);
-  std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
-  const float spf = 16000 / frame_rate;
-  int line_no = 0;
-  if (first_frame > 0 || last_frame > 0) phn_skip_to_first_frame(f, spf, first_frame, last_frame, &line_no);
-  Segmentation seg;
-  PhnLine cur;
-  if (!next_phn_line(f, spf, first_frame, last_frame, &line_no, &cur)) return seg;
-  seg.initialized = true;
-  int frame = -1;
-  bool eof_flag = false;
-  while (!eof_flag) {
-    frame = frame == -1 ? cur.start : frame + 1;
-    if (cur.state < 0) raise(AASR_ERR_INVALID, "PhnReader::next_frame(): A state segmented phn file is required");
-    const int h = aasr_topo_hmm_index(topo, cur.label.c_str());
-    if (h < 0) raise(AASR_ERR_INVALID, "Unknown HMM in transcription: '%s' in %s", cur.label.c_str(), path);
-    const std::vector<int32_t> &states = tt.hmm_states[(size_t)h];
-    if (cur.state >= (int)states.size())
-      raise(AASR_ERR_INVALID, "%s: state %d of HMM %s does not exist", path, cur.state, cur.label.c_str());
-    const int state = states[(size_t)cur.state];
-    bool new_phn_loaded = false;
-    const PhnLine prev = cur;
-    while (frame + 1 >= cur.end) {
-      if (!next_phn_line(f, spf, first_frame, last_frame, &line_no, &cur)) {
-        eof_flag = true;
-        break;
-      }
-      new_phn_loaded = true;
-    }
-    int transition = -1;
-    if (transitions && !eof_flag) {
-      const std::vector<int32_t> &off = tt.offsets[(size_t)state];
-      int found = -1;
-      if (new_phn_loaded) {
-        const int cur_state = prev.state;
-        const int n_states = (int)tt.hmm_states[(size_t)aasr_topo_hmm_index(topo, prev.label.c_str())].size();
-        for (size_t i = 0; i < off.size(); i++) {
-          const int next_state = off[i] + cur_state;
-          if ((next_state >= n_states && cur.state == 0) || (off[i] != 0 && next_state == cur.state)) {
-            found = (int)i;
-            break;
-          }
-        }
-      } else {
-        for (size_t i = 0; i < off.size(); i++)
-          if (off[i] == 0) {
-            found = (int)i;
-            break;
-          }
-      }
-      if (found < 0) raise(AASR_ERR_INVALID, "PhnReader::next_frame(): Correct transition was not found");
-      transition = tt.tr_base[(size_t)state] + found;
-    }
-    if (eof_frame >= 0 && frame >= eof_frame) break;  // EOF in FeatureGenerator (stats.cc:105-112)
-    if (seg.pdf.empty()) seg.start_frame = frame;
-    seg.pdf.push_back(state);  // legacy .ph: a state's emission pdf is the state itself
-    seg.tr.push_back(transition);
-  }
-  return seg;
-}
 
 }  // namespace aasr
 
@@ -551,6 +444,7 @@ aasr_status aasr_stats_read_segmentation(const aasr_topo *topo, const char *path
       raise(AASR_ERR_INVALID, "out of memory");
     }
     std::copy(seg.pdf.begin(), seg.pdf.end(), *pdf);
+    std::fill(*transition, *transition + n, -1);  // (what the reader leaves out when no transitions are asked for)
     std::copy(seg.tr.begin(), seg.tr.end(), *transition);
     *start_frame = seg.start_frame;
     *n_frames = seg.initialized ? (int32_t)n : -1;
@@ -565,62 +459,6 @@ void aasr_stats_default_options(aasr_stats_options *o) {
 
 // ---- the stats main loop over a recipe ---------------------------------------------------------
 
-namespace aasr {
-
-struct StatsUtt {
-  std::string audio, transcript, alignment, speaker, utterance;
-  float start_time = 0, end_time = 0;
-  int start_line = 0, end_line = 0;
-};
-
-static std::vector<StatsUtt> read_stats_recipe(const char *recipe_path, int num_batches, int batch_index) {
-  FILE *f = fopen(recipe_path, "rb");
-  if (!f) raise(AASR_ERR_IO, "could not open recipe %s", recipe_path);
-  std::string text;
-  char buf[4096];
-  size_t n;
-  while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
-  fclose(f);
-  char *table = nullptr;
-  int64_t len = 0;
-  // stats reads its recipe with cluster_speakers = false (aku/stats.cc:422-424)
-  if (aasr_recipe_read_all(text.c_str(), num_batches, batch_index, 0, &table, &len) != AASR_OK)
-    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-  const std::string t(table, (size_t)len);
-  aasr_free(table);
-  std::vector<StatsUtt> out;
-  size_t pos = 0;
-  while (pos < t.size()) {
-    size_t eol = t.find('\n', pos);
-    if (eol == std::string::npos) eol = t.size();
-    std::vector<std::string> fl;
-    size_t a = pos;
-    while (a <= eol) {
-      size_t b = t.find('\x1f', a);
-      if (b == std::string::npos || b > eol) b = eol;
-      fl.push_back(t.substr(a, b - a));
-      a = b + 1;
-    }
-    if (fl.size() == 13) {
-      StatsUtt u;
-      u.audio = fl[0];
-      u.transcript = fl[2];
-      u.alignment = fl[3];
-      u.start_time = (float)atof(fl[7].c_str());
-      u.end_time = (float)atof(fl[8].c_str());
-      u.start_line = atoi(fl[9].c_str());
-      u.end_line = atoi(fl[10].c_str());
-      u.speaker = fl[11];
-      u.utterance = fl[12];
-      out.push_back(u);
-    }
-    pos = eol + 1;
-  }
-  return out;
-}
-
-}  // namespace aasr
-
 extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
                                              const char *recipe_path, const aasr_stats_options *opt,
                                              aasr_run_stats *stats) {
@@ -628,13 +466,10 @@ extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, con
     if (!feat || !gmm || !topo || !recipe_path || !opt || (!opt->no_train && !opt->out))
       raise(AASR_ERR_INVALID, "aasr_run_stats_recipe: null argument");
     const auto t0 = std::chrono::steady_clock::now();
-    if (aasr_gmm_dim(gmm) != aasr_feat_dim(feat))
-      raise(AASR_ERR_INVALID, "gaussian dimension is %d but feature dimension is %d", aasr_gmm_dim(gmm),
-            aasr_feat_dim(feat));
-    std::vector<StatsUtt> utts = read_stats_recipe(recipe_path, opt->num_batches, opt->batch_index);
-    for (const StatsUtt &u : utts)
-      if (u.start_line > 0 || u.end_line > 0)
-        raise(AASR_ERR_UNSUPPORTED, "stats: recipe line limits (start-line / end-line) are not supported");
+    check_feature_dim(gmm, feat);
+    // stats reads its recipe with cluster_speakers = false (aku/stats.cc:422-424)
+    const std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, false);
+    refuse_line_limits(infos, "stats");
     aasr_stats *h = nullptr;
     {  // (a model the accumulation kernel has no shape for keeps its AASR_ERR_UNSUPPORTED)
       const aasr_status cs = aasr_stats_create(gmm, topo, &h);
@@ -643,133 +478,73 @@ extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, con
     std::unique_ptr<aasr_stats, void (*)(aasr_stats *)> hguard(h, aasr_stats_destroy);
     const TopoTables tt(topo);
     const float fr = aasr_feat_frame_rate(feat);
-    const int D = aasr_gmm_dim(gmm);
-    const bool accumulate = !opt->no_train;
-    hipStream_t stream;
-    AASR_HIP(hipStreamCreate(&stream));
-    std::unique_ptr<void, void (*)(void *)> sguard((void *)stream, [](void *s) { (void)hipStreamDestroy((hipStream_t)s); });
-    // -S: a speaker change that rewrites feature parameters waits for the features queued with the old ones;
-    // utterances whose settings stay the same stay in flight together
-    struct Unhook {
-      aasr_spkc *s;
-      ~Unhook() {
-        if (s) spkc_set_before_change(s, nullptr);
-      }
-    } unhook{opt->speakers};
-    if (opt->speakers) spkc_set_before_change(opt->speakers, [stream]() { AASR_HIP(hipStreamSynchronize(stream)); });
-    DevBuf<int16_t> d_pcm;
-    DevBuf<double> d_x, d_ll;
+    const bool accumulate = !opt->no_train, transitions = opt->transitions != 0;
+    GroupStager stager(feat, opt->speakers);
+    const hipStream_t stream = stager.stream;
+    DevBuf<double> d_ll;
     double total_ll = 0;
     int64_t num_frames = 0;
     // groups of utterances accumulated in one launch; their frames stay on the device
     const int64_t max_group_frames = (int64_t)1 << 20;
-    struct Pending {
-      size_t utt;
-      std::vector<int16_t> pcm;
-      Segmentation seg;
-    };
     size_t next = 0;
-    while (next < utts.size()) {
+    while (next < infos.size()) {
       // host side first: audio and segmentation, the -i messages in recipe order
-      std::vector<Pending> group;
+      const size_t group_first = next;
+      std::vector<std::vector<int16_t>> audio;
+      std::vector<Segmentation> segs;
+      std::vector<int32_t> start, rows, pdfs;
       int64_t rows_total = 0;
-      while (next < utts.size() && group.size() < 1024 && rows_total < max_group_frames) {
-        const StatsUtt &u = utts[next];
-        if (opt->info > 0) {
-          fprintf(stderr, "Processing file: %s", u.audio.c_str());
-          if (u.start_time || u.end_time) fprintf(stderr, " (%.2f-%.2f)", u.start_time, u.end_time);
-          fprintf(stderr, "\n");
-        }
-        int16_t *pcm = nullptr;
-        int64_t n_samples = 0;
-        int32_t rate = 0;
-        if (aasr_feat_input_is_features(feat)) {  // a pre module: feacat's feature file, in the engine's input units
-          std::ifstream in(u.audio, std::ios::binary);
-          if (!in) raise(AASR_ERR_IO, "could not open %s", u.audio.c_str());
-          const std::string bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-          if (aasr_audio_decode(feat, bytes.data(), (int64_t)bytes.size(), &pcm, &n_samples, &rate) != AASR_OK)
-            raise(AASR_ERR_IO, "%s: %s", u.audio.c_str(), aasr_last_error());
-        } else if (aasr_audio_read(feat, u.audio.c_str(), &pcm, &n_samples, &rate) != AASR_OK) {
-          raise(AASR_ERR_IO, "%s", aasr_last_error());
-        }
-        Pending pd;
-        pd.utt = next;
-        pd.pcm.assign(pcm, pcm + n_samples);
-        aasr_free(pcm);
-        const int eof = aasr_feat_eof_frame(feat, n_samples);
-        int first = 0, last = 0;
-        if (u.start_time > 0 || u.end_time > 0) {
-          first = (int)(u.start_time * fr);
-          last = (int)(u.end_time * fr);
-        }
-        pd.seg = read_segmentation(topo, tt, (opt->ophn ? u.alignment : u.transcript).c_str(), fr, first, last, eof,
-                                   opt->transitions != 0);
-        next++;
-        if (!pd.seg.initialized) {
+      while (next < infos.size() && audio.size() < 1024 && rows_total < max_group_frames) {
+        const RecipeInfo &u = infos[next++];
+        announce(u, opt->info);
+        audio.push_back(load_utterance_input(feat, u));
+        int first, last;
+        frame_range(u, fr, &first, &last);
+        segs.push_back(read_segmentation(topo, tt, (opt->ophn ? u.alignment_path : u.transcript_path).c_str(), fr, first,
+                                         last, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), transitions));
+        const Segmentation &seg = segs.back();
+        if (!seg.initialized) {
           fprintf(stderr, "Could not initialize the utterance segmentation.\n");
           fprintf(stderr, "Giving up for this file\n");
-          pd.pcm.clear();  // no frames; kept in the group for its speaker settings (stats.cc:560-565 run first)
+          audio.back().clear();  // no frames; kept in the group for its speaker settings (stats.cc:560-565 run first)
         }
-        rows_total += (int64_t)pd.seg.pdf.size();
-        group.push_back(std::move(pd));
+        start.push_back(seg.start_frame);
+        rows.push_back((int32_t)seg.pdf.size());
+        pdfs.insert(pdfs.end(), seg.pdf.begin(), seg.pdf.end());
+        rows_total += (int64_t)seg.pdf.size();
       }
-      // features of the group into one device buffer, speaker configuration per utterance
-      d_x.ensure((size_t)std::max<int64_t>(1, rows_total) * D);
       d_ll.ensure((size_t)std::max<int64_t>(1, rows_total));
-      std::vector<int32_t> pdfs;
-      pdfs.reserve((size_t)rows_total);
-      size_t samples = 1;
-      for (const Pending &pd : group) samples += pd.pcm.size();
-      if (samples > d_pcm.n) {
-        AASR_HIP(hipStreamSynchronize(stream));
-        d_pcm.alloc(samples);
-      }
-      size_t pcm_at = 0;
-      int64_t row = 0;
-      for (Pending &pd : group) {
-        const StatsUtt &u = utts[pd.utt];
-        if (opt->speakers) {  // (a parameter change waits for the queued features: the hook above)
-          if (aasr_spkc_set_speaker(opt->speakers, u.speaker.c_str()) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          if (opt->uttadap && !u.utterance.empty() && aasr_spkc_set_utterance(opt->speakers, u.utterance.c_str()) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          check_stats_model(gmm);
-        }
-        const int64_t n = (int64_t)pd.seg.pdf.size();
-        if (n > 0) {  // (the group's audio stays on the host until the group's wait below)
-          if (!pd.pcm.empty())
-            AASR_HIP(hipMemcpyAsync(d_pcm.p + pcm_at, pd.pcm.data(), pd.pcm.size() * sizeof(int16_t),
-                                    hipMemcpyHostToDevice, stream));
-          if (aasr_feat_run_f64_dev(feat, d_pcm.p + pcm_at, (int64_t)pd.pcm.size(), pd.seg.start_frame, (int32_t)n,
-                                    d_x.p + (size_t)row * D, stream) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          pcm_at += pd.pcm.size();
-        }
-        pdfs.insert(pdfs.end(), pd.seg.pdf.begin(), pd.seg.pdf.end());
-        if (accumulate && opt->transitions && aasr_stats_add_transitions(h, pd.seg.tr.data(), n) != AASR_OK)
+      // features of the group into one device buffer, speaker configuration per utterance
+      stager.stage(audio, start, rows, [&](size_t i) {
+        if (!opt->speakers) return;
+        const RecipeInfo &u = infos[group_first + i];
+        if (aasr_spkc_set_speaker(opt->speakers, u.speaker_id.c_str()) != AASR_OK)
           raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        row += n;
-      }
+        if (opt->uttadap && !u.utterance_id.empty() &&
+            aasr_spkc_set_utterance(opt->speakers, u.utterance_id.c_str()) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        check_stats_model(gmm);
+      });
+      if (accumulate && transitions)
+        for (const Segmentation &seg : segs)
+          if (aasr_stats_add_transitions(h, seg.tr.data(), (int64_t)seg.tr.size()) != AASR_OK)
+            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       if (rows_total == 0) continue;
-      if (aasr_stats_accumulate_dev(h, d_x.p, rows_total, pdfs.data(), d_ll.p, stream) != AASR_OK)
+      if (aasr_stats_accumulate_dev(h, stager.d_x.p, rows_total, pdfs.data(), d_ll.p, stream) != AASR_OK)
         raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       // the .lls figure in frame order: state likelihoods, then the transition taken (stats.cc:130-160)
       std::vector<double> ll((size_t)rows_total);
       AASR_HIP(hipMemcpyAsync(ll.data(), d_ll.p, ll.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
       AASR_HIP(hipStreamSynchronize(stream));
-      row = 0;
-      for (const Pending &pd : group) {
-        for (size_t f = 0; f < pd.seg.pdf.size(); f++) {
-          total_ll += ll[(size_t)row + f];  // safe_log(1.0 * state_likelihood): the kernel's safe_log(total)
-          const int t = pd.seg.tr[f];
-          if (opt->transitions && accumulate && t >= 0) {
-            const int s = h->tr_source[(size_t)t];
-            total_ll += safe_log(1.0 * tt.probs[(size_t)s][(size_t)(t - tt.tr_base[(size_t)s])]);
-          }
+      size_t row = 0;
+      for (const Segmentation &seg : segs)
+        for (size_t f = 0; f < seg.pdf.size(); f++) {
+          total_ll += ll[row++];  // safe_log(1.0 * state_likelihood): the kernel's safe_log(total)
+          if (!(transitions && accumulate) || seg.tr[f] < 0) continue;
+          const int t = seg.tr[f], s = h->tr_source[(size_t)t];
+          total_ll += safe_log(1.0 * tt.probs[(size_t)s][(size_t)(t - tt.tr_base[(size_t)s])]);
         }
-        row += (int64_t)pd.seg.pdf.size();
-        num_frames += (int64_t)pd.seg.pdf.size();
-      }
+      num_frames += rows_total;
     }
     if (opt->info > 0) {
       fprintf(stderr, "Finished collecting statistics (%i/%i)\n", opt->batch_index, opt->num_batches);
@@ -784,12 +559,6 @@ extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, con
       const aasr_status st = aasr_stats_write_lls((out + ".lls").c_str(), total_ll, num_frames);
       if (st != AASR_OK) raise(st, "%s", last_error().c_str());
     }
-    if (stats) {
-      stats->utterances = (int64_t)utts.size();
-      stats->frames = num_frames;
-      stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      stats->seconds_device = 0;
-      stats->seconds_copy_out = 0;
-    }
+    fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
   });
 }
