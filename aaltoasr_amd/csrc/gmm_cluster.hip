@@ -824,7 +824,7 @@ __global__ __launch_bounds__(64) void k_cluster_select_heap(
 }
 
 // ----------------------------------------------------------------- expand --
-// Per-lane selection bits for the track kernels (see ClusterArgs in gmm_score.hip): for the wave
+// Per-lane selection bits for the track kernels (see ClusterArgs in gmm_score_common.h): for the wave
 // that owns the 64 frames of `word`, lane (n, h) and tile t,
 //   bit ((mb*4 + q)*4 + e)*2 + side  =  selected(row t*64 + 32 mb + 8q + 4h + e, frame 32 side + n).
 // A workgroup takes one word and a run of tiles: the word's cluster masks (C + 1 words, the last

@@ -704,7 +704,7 @@ void gmm_build(aasr_gmm *g, const HostModel &model) {
 // PIVOT GROUPS, every group a run of whole tiles expanded around its own pivot, the frame operand gets one image per
 // group (k_frame_operand, 320 B per frame and group), and a row cut never straddles two groups (build_split_table_pg).
 // The output columns follow the sorted order (every group starts on a whole 128-byte line), consumers read a score row
-// through a column map (gmm_engine_colmap); public-layout callers get the columns gathered back (gmm_score.hip).
+// through a column map (gmm_engine_colmap); public-layout callers get the columns gathered back (gmm_score.hip, launch_engine_parts_public).
 // ---------------------------------------------------------------------------
 static void build_pg_model(aasr_gmm *g) {
   HostModel &m = g->host;

@@ -6,6 +6,7 @@ its prologue); since the frame operand is formed by k_frame_operand and only loa
 at all -- and a spill that enters the tile loop would cost far more than the few percent any scheduling change gains,
 silently.  So the build fails this test when the bench instance (or any two-term instance the default paths launch)
 starts to use scratch memory."""
+import glob
 import os
 import sys
 
@@ -15,12 +16,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
+def _scoring_objects():
+    """the objects of the scoring unit's files: one per csrc/gmm_score*.hip (the map of the files: gmm_score.hip)"""
+    srcs = sorted(glob.glob(os.path.join(ROOT, "aaltoasr_amd", "csrc", "gmm_score*.hip")))
+    assert os.path.join(ROOT, "aaltoasr_amd", "csrc", "gmm_score.hip") in srcs and len(srcs) > 1, srcs
+    objs = [os.path.join(ROOT, "aaltoasr_amd", "lib", "obj", os.path.basename(s) + ".o") for s in srcs]
+    for obj in objs:
+        assert os.path.exists(obj), obj
+    return objs
+
+
 @pytest.fixture(scope="module")
 def notes(capi):
     import kernel_notes
-    obj = os.path.join(ROOT, "aaltoasr_amd", "lib", "obj", "gmm_score.hip.o")
-    assert os.path.exists(obj)
-    return kernel_notes.kernel_notes(obj)
+    out = {}
+    for obj in _scoring_objects():
+        out.update(kernel_notes.kernel_notes(obj))
+    return out
+
+
+def test_no_scoring_kernel_is_instantiated_in_two_files(capi):
+    """Every kernel instance of the scoring unit lives in exactly one of its files: a second copy would be compiled,
+    shipped and loaded twice, and the `notes` dictionary above would hide one of them."""
+    import kernel_notes
+    seen = {}
+    for obj in _scoring_objects():
+        for name in kernel_notes.kernel_notes(obj):
+            seen.setdefault(name, []).append(os.path.basename(obj))
+    twice = {n: o for n, o in seen.items() if len(o) > 1}
+    assert not twice, twice
 
 
 def _get(notes, name):

@@ -1,4 +1,4 @@
-"""Outlier routing with the merge fused into the scoring kernel (k_gmm_diag_score_pl<..., HYB>, gmm_score.hip): which
+"""Outlier routing with the merge fused into the scoring kernel (k_gmm_diag_score_pl<..., HYB>, gmm_score_pl.h): which
 kernel ran, its table and frame edges, and its arithmetic against the merge pass.
 
 The models production loads have a few Gaussians far over the matrix layouts' conditioning limits (variance-floored
@@ -28,7 +28,7 @@ from aaltoasr_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-WIDE_FROM = 8192   # launch_split (gmm_score.hip): the 8-wave form from this many frames on, the 4-wave form below
+WIDE_FROM = 8192   # launch_split (gmm_score_pl.h): the 8-wave form from this many frames on, the 4-wave form below
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------

@@ -2,10 +2,10 @@
 """kernel_notes.py -- register / scratch / LDS figures of the kernels in a compiled object, read from the code object's
 notes (no GPU needed):
 
-    python tools/kernel_notes.py [pattern] [object]      default object: aaltoasr_amd/lib/obj/gmm_score.hip.o
-    python tools/kernel_notes.py --digest [object ...]   default objects: aaltoasr_amd/lib/obj/gmm_score*.hip.o
+    python tools/kernel_notes.py [pattern] [object ...]  default objects: aaltoasr_amd/lib/obj/gmm_score*.hip.o
+    python tools/kernel_notes.py --digest [object ...]   default objects: the same (the files of the scoring unit)
 
-The first form prints one line per kernel whose demangled name contains `pattern`.
+The first form prints one line per kernel of the objects whose demangled name contains `pattern`.
 
 --digest prints one line per kernel of the given objects (hipcc objects or a linked libaasr.so), sorted by name: the
 demangled name, SHA-256 over the kernel's machine code bytes, SHA-256 over its 64-byte kernel descriptor, and the notes
@@ -162,8 +162,8 @@ if __name__ == "__main__":
         sys.stderr.write("%d kernels, table sha256 %s\n" % (len(lines), hashlib.sha256("\n".join(lines).encode()).hexdigest()))
         sys.exit(0)
     pat = sys.argv[1] if len(sys.argv) > 1 else ""
-    obj = sys.argv[2] if len(sys.argv) > 2 else os.path.join(OBJDIR, "gmm_score.hip.o")
-    for name, k in sorted(kernel_notes(obj).items()):
+    objs = sys.argv[2:] or sorted(glob.glob(os.path.join(OBJDIR, "gmm_score*.hip.o")))
+    for name, k in sorted(((n, k) for obj in objs for n, k in kernel_notes(obj).items()), key=lambda r: r[0]):
         if pat in name:
             print("%-70s vgpr %3d agpr %3d sgpr %3d spill v %3d s %3d scratch %4d B" % (
                 name[-70:], k["vgpr"], k["agpr"], k["sgpr"], k["spill_vgpr"], k["spill_sgpr"], k["scratch"]))
