@@ -172,6 +172,16 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_lda_default_options.argtypes = [vp]
     L.aasr_lda_default_options.restype = None
     L.aasr_run_lda_recipe.argtypes = [cp, vp, cp, vp, vp]
+    # Gaussian-pool clustering
+    L.aasr_gcluster_assign.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+    L.aasr_gcluster_centres.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.aasr_debug_gcluster_chunk.argtypes = []
+    L.aasr_debug_gcluster_chunk.restype = i32
+    L.aasr_gcluster_default_options.argtypes = [vp]
+    L.aasr_gcluster_default_options.restype = None
+    L.aasr_run_gcluster.argtypes = [cp, cp, vp]
+    L.aasr_gcluster_arrays.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.aasr_gmm_cluster.argtypes = [vp, i32, i32]
     L.aasr_spkc_write_text.argtypes = [vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(i64)]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
@@ -413,6 +423,12 @@ class Gmm:
         gi = np.ascontiguousarray([p[0] for p in pairs], np.int32)
         ci = np.ascontiguousarray([p[1] for p in pairs], np.int32)
         check(lib().aasr_gmm_set_clustering(self._h, n_clusters, len(gi), _ptr(gi), _ptr(ci)))
+
+    def cluster(self, n_clusters: int, info: int = 0) -> int:
+        """gcluster on the model's own Gaussians (means and covariance diagonals), installed as read_clustering would
+        install the file the tool writes; -> the number of clusters (those that kept members)."""
+        check(lib().aasr_gmm_cluster(self._h, n_clusters, info))
+        return self.num_clusters
 
     def set_clustering_min_evals(self, min_clusters: float = 1.0, min_gaussians: float = 1.0) -> None:
         """HmmSet::set_clustering_min_evals: ratios of clusters / pool Gaussians."""
@@ -1388,3 +1404,73 @@ def run_lda_recipe(cfg_text: str, topo: Topology, recipe_path: str, module: str,
     check(lib().aasr_run_lda_recipe(cfg_text.encode(), topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total,
             "seconds_scatter": opts.seconds_scatter, "seconds_features": opts.seconds_features, "state_gamma": sg}
+
+
+# ---- Gaussian-pool clustering -------------------------------------------------------------------
+
+def gcluster_chunk() -> int:
+    """Diagnostic: the centres the assignment kernel walks at a time."""
+    return int(lib().aasr_debug_gcluster_chunk())
+
+
+def gcluster_assign(mean, cov, ldet, c_mean, c_cov, c_ldet, c_valid, euclid: bool = False):
+    """One assignment pass of gcluster on the device: -> (index [G] int32, distance [G]).  euclid: the norm of the mean
+    difference over all centres (only mean and c_mean are read); otherwise the Kullback-Leibler divergence over the
+    centres with c_valid != 0."""
+    f64 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
+    mean, cov, ldet, c_mean, c_cov, c_ldet = f64(mean), f64(cov), f64(ldet), f64(c_mean), f64(c_cov), f64(c_ldet)
+    c_valid = None if c_valid is None else np.ascontiguousarray(c_valid, np.int32)
+    G, D = mean.shape
+    Cn = c_mean.shape[0]
+    if c_mean.shape[1] != D:
+        raise ValueError("centres of %d dimensions for Gaussians of %d" % (c_mean.shape[1], D))
+    idx, dist = np.zeros(G, np.int32), np.zeros(G)
+    check(lib().aasr_gcluster_assign(D, G, _ptr(mean), _ptr(cov), _ptr(ldet), Cn, _ptr(c_mean), _ptr(c_cov), _ptr(c_ldet),
+                                     _ptr(c_valid), 1 if euclid else 0, _ptr(idx), _ptr(dist)))
+    return idx, dist
+
+
+def gcluster_centres(mean, cov, cluster_map, n_clusters: int):
+    """compute_cluster_statistics on the device: -> (c_mean, c_cov [C x D], c_ldet [C], c_valid [C] int32)."""
+    mean, cov = np.ascontiguousarray(mean, np.float64), np.ascontiguousarray(cov, np.float64)
+    m = np.ascontiguousarray(cluster_map, np.int32)
+    G, D = mean.shape
+    if len(m) != G or cov.shape != mean.shape:
+        raise ValueError("mean, cov and the map disagree in shape")
+    cm, cc = np.zeros((n_clusters, D)), np.zeros((n_clusters, D))
+    cl, cv = np.zeros(n_clusters), np.zeros(n_clusters, np.int32)
+    check(lib().aasr_gcluster_centres(D, G, _ptr(mean), _ptr(cov), n_clusters, _ptr(m), _ptr(cm), _ptr(cc), _ptr(cl), _ptr(cv)))
+    return cm, cc, cl, cv
+
+
+class GclusterOptions(C.Structure):
+    """aasr_gcluster_options: gcluster's options (aku/gcluster.cc:359-369)."""
+    _fields_ = [("clusters", C.c_int32), ("iterations", C.c_int32), ("info", C.c_int32), ("full", C.c_int32),
+                ("progress", C.c_int32), ("regtree", C.c_char_p), ("base", C.c_char_p), ("written", C.c_int32),
+                ("seconds_steps", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "GclusterOptions":
+        o = cls()
+        lib().aasr_gcluster_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def gcluster(gk_path: str, out_path: str, clusters: int = 1000, info: int = 0, opts: Optional[GclusterOptions] = None) -> dict:
+    """The gcluster tool's run: reads the .gk, writes the .gcl; -> the clusters written and the steps' time."""
+    opts = opts or GclusterOptions.defaults()
+    opts.clusters, opts.info = clusters, info
+    check(lib().aasr_run_gcluster(gk_path.encode(), out_path.encode(), C.byref(opts)))
+    return {"written": int(opts.written), "seconds_steps": float(opts.seconds_steps)}
+
+
+def gcluster_arrays(mean, cov, clusters: int = 1000, info: int = 0):
+    """The same run on arrays: -> (cluster of every Gaussian [G] int32, renumbered; clusters written; steps' seconds)."""
+    mean, cov = np.ascontiguousarray(mean, np.float64), np.ascontiguousarray(cov, np.float64)
+    G, D = mean.shape
+    opts = GclusterOptions.defaults(clusters=clusters, info=info)
+    out = np.zeros(G, np.int32)
+    check(lib().aasr_gcluster_arrays(D, G, _ptr(mean), _ptr(cov), C.byref(opts), _ptr(out)))
+    return out, int(opts.written), float(opts.seconds_steps)

@@ -84,6 +84,8 @@ struct HostModel {
 void model_files_fingerprint(const char *gk, const char *mc, const char *ph, uint64_t fp[6]);
 
 HostModel read_model_files(const char *gk, const char *mc, const char *ph);
+// the .gk part of it alone (PDFPool::read_gk): dim, G, mean, var, cov / is_full, gauss_bias of m
+void read_gk_pool(const char *gk, HostModel &m);
 // model_cache.cc: parsed model <-> one binary blob (magic, sizes, arrays, FNV-1a checksum)
 void write_model_cache(const HostModel &m, const char *path);
 HostModel read_model_cache(const char *path);

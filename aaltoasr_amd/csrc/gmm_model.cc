@@ -198,8 +198,7 @@ static void read_subspace_gaussian(std::istream &in, bool pcgmm, const SubspaceT
   }
 }
 
-HostModel read_model_files(const char *gk, const char *mc, const char *ph) {
-  HostModel m;
+void read_gk_pool(const char *gk, HostModel &m) {
   {
     std::ifstream in(gk);
     if (!in) raise(AASR_ERR_IO, "PDFPool::read_gk(): could not open %s", gk);
@@ -260,6 +259,11 @@ HostModel read_model_files(const char *gk, const char *mc, const char *ph) {
         raise(AASR_ERR_INVALID, "Error in reading Gaussian specifications");
     }
   }
+}
+
+HostModel read_model_files(const char *gk, const char *mc, const char *ph) {
+  HostModel m;
+  read_gk_pool(gk, m);
   {
     std::ifstream in(mc);
     if (!in) raise(AASR_ERR_IO, "HmmSet::read_mc(): could not open %s", mc);

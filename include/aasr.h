@@ -883,6 +883,61 @@ void aasr_lda_default_options(aasr_lda_options *opt);
 aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr_topo *topo, const char *recipe_path,
                                 aasr_lda_options *opt, aasr_run_stats *stats);
 
+/* ---------------------------------------------------------------------------
+ * Clustering of the Gaussian pool: aku/gcluster.cc in its default (diagonal) mode, one group.
+ *
+ * Every Gaussian is its mean and the diagonal of its covariance.  C centres start as the means of the first C
+ * entries of a random permutation (libc rand() from seed 1, as a fresh process has it: the run entries call srand(1)
+ * so that a call gives what the tool gives); every Gaussian goes to the centre of the nearest mean (Euclidean, all
+ * centres); then four passes of: centre = mean of its members' means and covariances, every Gaussian to the valid
+ * centre of the smallest Kullback-Leibler divergence.  A centre without members is invalid from then on.  The written
+ * clusters are the valid ones, renumbered in order.
+ *
+ * The assignment passes and the centre sums run on the device (csrc/kl_cluster.hip) with the reference's own
+ * operations in its own order -- no atomics, no reciprocal, no fused product -- so the result is the reference's map,
+ * not one near it; log-determinants are summed on the host with the C library's log.  Any dimension >= 1. */
+
+/* One assignment pass over plain host arrays: mean, cov [n_gauss x dim], ldet [n_gauss]; c_mean, c_cov
+ * [n_clusters x dim], c_ldet, c_valid [n_clusters].  euclid != 0: out_dist = sqrt(sum_k (mean - c_mean)^2) over ALL
+ * centres (cov, ldet, c_cov, c_ldet, c_valid are not read and may be NULL).  euclid == 0: out_dist =
+ * (c_ldet - ldet + sum_k (cov + (mean - c_mean)^2) / c_cov - dim) / 2 over the centres with c_valid != 0.
+ * out_index [n_gauss]: the first centre of the smallest distance below 1e100, or 0 (out_dist 1e100) when there is
+ * none -- also when centre 0 is invalid, as in the reference. */
+aasr_status aasr_gcluster_assign(int32_t dim, int32_t n_gauss, const double *mean, const double *cov, const double *ldet,
+                                 int32_t n_clusters, const double *c_mean, const double *c_cov, const double *c_ldet,
+                                 const int32_t *c_valid, int32_t euclid, int32_t *out_index, double *out_dist);
+/* compute_cluster_statistics: per cluster the sums of its members' (map [n_gauss], every entry in
+ * 0 ... n_clusters - 1) means and covariances in Gaussian order, times 1 / count; c_valid = count > 0;
+ * c_ldet = sum_k log(c_cov) on the host.  A cluster without members gets zeros. */
+aasr_status aasr_gcluster_centres(int32_t dim, int32_t n_gauss, const double *mean, const double *cov, int32_t n_clusters,
+                                  const int32_t *map, double *c_mean, double *c_cov, double *c_ldet, int32_t *c_valid);
+/* Diagnostic: the number of centres the assignment kernel walks at a time (its tie rule has to hold across them). */
+int32_t aasr_debug_gcluster_chunk(void);
+
+typedef struct aasr_gcluster_options {
+  int32_t clusters;     /* -C: at least 2, at most the number of Gaussians                          */
+  int32_t iterations;   /* -t: below 1 is an error; the single-group run makes four passes whatever it says */
+  int32_t info;         /* -i: 1 the iterations' average divergence and the count written, 2 every Gaussian */
+  int32_t full;         /* -F given: full-covariance centres, AASR_ERR_UNSUPPORTED                  */
+  int32_t progress;     /* the tool's "make initial clusters" / "start clustering" lines on stderr  */
+  const char *regtree;  /* -R, or NULL; with base: per-class groups, AASR_ERR_UNSUPPORTED           */
+  const char *base;     /* -b, or NULL                                                              */
+  int32_t written;      /* out: clusters written (the valid ones)                                   */
+  double seconds_steps; /* out: host clock around the five assignment + centre steps, each to its synchronisation */
+} aasr_gcluster_options;
+void aasr_gcluster_default_options(aasr_gcluster_options *opt);
+/* gcluster's main: reads gk_path (any pool the engine reads; full-covariance and subspace Gaussians by their
+ * covariance diagonal), clusters, writes out_path ("n\n" then "gaussian cluster\n" per Gaussian).  The reference's
+ * errors with its messages, all before the device is opened: "Invalid number of clusters", "Invalid number of
+ * iterations", "Both tree and model must be given", "Not enough Gaussians to cluster!". */
+aasr_status aasr_run_gcluster(const char *gk_path, const char *out_path, aasr_gcluster_options *opt);
+/* The same run on plain arrays: cluster_of [n_gauss] receives the renumbered cluster of every Gaussian. */
+aasr_status aasr_gcluster_arrays(int32_t dim, int32_t n_gauss, const double *mean, const double *cov,
+                                 aasr_gcluster_options *opt, int32_t *cluster_of);
+/* The same run on a loaded model's Gaussians; the result is installed as aasr_gmm_read_clustering installs the file
+ * the tool would have written (its reader's last pair counted twice included). */
+aasr_status aasr_gmm_cluster(aasr_gmm *h, int32_t n_clusters, int32_t info);
+
 #ifdef __cplusplus
 }
 #endif
