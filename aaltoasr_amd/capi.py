@@ -182,6 +182,23 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_run_gcluster.argtypes = [cp, cp, vp]
     L.aasr_gcluster_arrays.argtypes = [i32, i32, vp, vp, vp, vp]
     L.aasr_gmm_cluster.argtypes = [vp, i32, i32]
+    # feature normalization and PCA
+    L.aasr_moments_create.argtypes = [i32, i32, pvp]
+    L.aasr_moments_destroy.argtypes = [vp]
+    L.aasr_moments_destroy.restype = None
+    L.aasr_moments_accumulate_dev.argtypes = [vp, vp, i64, vp, i32, vp]
+    L.aasr_moments_fetch.argtypes = [vp, vp]
+    L.aasr_moments_num_segments.argtypes = [vp]
+    L.aasr_moments_num_segments.restype = i64
+    L.aasr_moments_get.argtypes = [vp, vp, vp, vp, vp]
+    L.aasr_moments_blocked.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.aasr_debug_moments_shape.argtypes = [vp, vp]
+    L.aasr_debug_moments_shape.restype = None
+    L.aasr_debug_moments_set_launch_segments.argtypes = [vp, i32]
+    L.aasr_feanorm_pca.argtypes = [i32, vp, vp, i32, vp, vp]
+    L.aasr_feanorm_default_options.argtypes = [vp]
+    L.aasr_feanorm_default_options.restype = None
+    L.aasr_run_feanorm_recipe.argtypes = [cp, cp, vp, vp]
     L.aasr_spkc_write_text.argtypes = [vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(i64)]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
@@ -1474,3 +1491,108 @@ def gcluster_arrays(mean, cov, clusters: int = 1000, info: int = 0):
     out = np.zeros(G, np.int32)
     check(lib().aasr_gcluster_arrays(D, G, _ptr(mean), _ptr(cov), C.byref(opts), _ptr(out)))
     return out, int(opts.written), float(opts.seconds_steps)
+
+
+# ---- feature normalization and PCA ---------------------------------------------------------------
+
+MOMENTS_DIAG, MOMENTS_FULL = 0, 1
+
+
+class Moments:
+    """Owner of an aasr_moments handle: per segment (a contiguous run of frame rows) the count, sum x and sum x^2
+    (MOMENTS_DIAG) or sum x x^T (MOMENTS_FULL), on the device."""
+
+    def __init__(self, dim: int, mode: int = MOMENTS_DIAG):
+        h = C.c_void_p()
+        check(lib().aasr_moments_create(dim, mode, C.byref(h)))
+        self._h = h.value
+        self.D, self.full = dim, mode == MOMENTS_FULL
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_moments_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def accumulate_dev(self, d_frames, segments, stream=None) -> None:
+        """d_frames: a float64 device tensor [n x dim]; segments: host int32 [m x 3] = first row, length, utterance."""
+        s = np.ascontiguousarray(segments, np.int32).reshape(-1, 3)
+        check(lib().aasr_moments_accumulate_dev(self._h, _ptr(d_frames), int(d_frames.shape[0]), _ptr(s), len(s),
+                                                _stream_handle(stream)))
+
+    def set_launch_segments(self, n: int) -> None:
+        """Diagnostic: at most n segments a launch."""
+        check(lib().aasr_debug_moments_set_launch_segments(self._h, n))
+
+    def launch_shape(self) -> dict:
+        """Diagnostic: the full-mode kernel's instance, the work items and the launches of the last call."""
+        out = (C.c_int32 * 3)()
+        lib().aasr_debug_moments_shape(self._h, out)
+        return {"pb": int(out[0]), "items": int(out[1]), "launches": int(out[2])}
+
+    def _xx(self) -> int:
+        return self.D * (self.D + 1) // 2 if self.full else self.D
+
+    def fetch(self, stream=None):
+        """Waits for the device; per segment in the order given -> count [n], utterance [n], sum_x [n x dim], sum_xx
+        ([n x dim] sum x^2, or [n x dim (dim + 1) / 2] the packed lower triangle of sum x x^T)."""
+        L = lib()
+        check(L.aasr_moments_fetch(self._h, _stream_handle(stream)))
+        n = int(L.aasr_moments_num_segments(self._h))
+        c, u = np.zeros(n), np.zeros(n, np.int32)
+        sx, sxx = np.zeros((n, self.D)), np.zeros((n, self._xx()))
+        check(L.aasr_moments_get(self._h, _ptr(c), _ptr(u), _ptr(sx), _ptr(sxx)))
+        return c, u, sx, sxx
+
+    def blocked(self, block_size: int, keep=None):
+        """After a fetch: feanorm's blocked sums over the segments (keep [n]: 0 leaves one out) -> count, sum_x [dim],
+        sum_xx."""
+        k = None if keep is None else np.ascontiguousarray(keep, np.int32)
+        c, sx, sxx = C.c_double(), np.zeros(self.D), np.zeros(self._xx())
+        check(lib().aasr_moments_blocked(self._h, block_size, _ptr(k), C.byref(c), _ptr(sx), _ptr(sxx)))
+        return c.value, sx, sxx
+
+
+def feanorm_pca(cov, scale=None, unit_determinant: bool = False):
+    """feanorm.cc:281-325 (host only): -> (pca [dim x dim], eigenvalues [dim] ascending); rows by ascending eigenvalue,
+    every row's largest-magnitude entry positive."""
+    cov = np.ascontiguousarray(cov, np.float64)
+    d = cov.shape[0]
+    sc = None if scale is None else np.ascontiguousarray(scale, np.float64)
+    out, ev = np.zeros((d, d)), np.zeros(d)
+    check(lib().aasr_feanorm_pca(d, _ptr(cov), _ptr(sc), 1 if unit_determinant else 0, _ptr(out), _ptr(ev)))
+    return out, ev
+
+
+class FeanormOptions(C.Structure):
+    """aasr_feanorm_options: feanorm's options (aku/feanorm.cc:48-62)."""
+    _fields_ = [("info", C.c_int32), ("block_size", C.c_int32), ("cov", C.c_int32), ("print", C.c_int32),
+                ("unit_determinant", C.c_int32), ("module", C.c_char_p), ("pca", C.c_char_p), ("speakers", C.c_char_p),
+                ("utt", C.c_char_p), ("out", C.c_char_p), ("blocks", C.c_double), ("seconds_moments", C.c_double),
+                ("seconds_features", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "FeanormOptions":
+        o = cls()
+        lib().aasr_feanorm_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_feanorm_recipe(cfg_text: str, recipe_path: str, module: Optional[str] = None, pca: Optional[str] = None,
+                       out: Optional[str] = None, speakers: Optional[str] = None, utt: Optional[str] = None,
+                       opts: Optional[FeanormOptions] = None) -> dict:
+    """-> the run's counts, the global block count and the device times."""
+    opts = opts or FeanormOptions.defaults()
+    enc = lambda s: s.encode() if s else None
+    opts.module, opts.pca, opts.out, opts.speakers, opts.utt = enc(module), enc(pca), enc(out), enc(speakers), enc(utt)
+    st = RunStats()
+    check(lib().aasr_run_feanorm_recipe(cfg_text.encode(), recipe_path.encode(), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total, "blocks": opts.blocks,
+            "seconds_moments": opts.seconds_moments, "seconds_features": opts.seconds_features}

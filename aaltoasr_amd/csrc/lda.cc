@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "feat.h"
+#include "jacobi.h"
 #include "recipe_pass.h"
 #include "scatter.h"
 
@@ -201,7 +202,7 @@ namespace aasr {
 // Cyclic Jacobi on the symmetric n x n row-major matrix a: on return a's diagonal holds the eigenvalues and the
 // COLUMNS of v the eigenvectors.  Every rotation annihilates one off-diagonal pair (Rutishauser's formulas); sweeps
 // until the off-diagonal sum of squares is below eps^2 of the matrix's.
-static void jacobi_eigen(std::vector<double> &a, int n, std::vector<double> &v) {
+void jacobi_eigen(std::vector<double> &a, int n, std::vector<double> &v) {
   v.assign((size_t)n * n, 0.0);
   for (int i = 0; i < n; i++) v[(size_t)i * n + i] = 1;
   double total = 0;

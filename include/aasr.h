@@ -938,6 +938,93 @@ aasr_status aasr_gcluster_arrays(int32_t dim, int32_t n_gauss, const double *mea
  * the tool would have written (its reader's last pair counted twice included). */
 aasr_status aasr_gmm_cluster(aasr_gmm *h, int32_t n_clusters, int32_t info);
 
+/* ---------------------------------------------------------------------------
+ * Feature normalization and PCA: aku/feanorm.cc.
+ *
+ * The blocked moments, on the device (csrc/moments_accum.hip).  A SEGMENT is a contiguous run of rows of a frame
+ * buffer -- feanorm's block of -b frames inside one utterance.  Per segment, in double:
+ *   AASR_MOMENTS_DIAG: the count, sum x and sum x^2 (vector pipe), any dimension >= 1;
+ *   AASR_MOMENTS_FULL: the count, sum x and sum x x^T (FP64 matrix pipe), 1 ... 127 dimensions
+ *                      (AASR_ERR_UNSUPPORTED beyond).
+ * Deterministic: no atomics; a segment's sums depend on its rows alone, not on the calls and launches around it. */
+#define AASR_MOMENTS_DIAG 0
+#define AASR_MOMENTS_FULL 1
+typedef struct aasr_moments aasr_moments;
+aasr_status aasr_moments_create(int32_t dim, int32_t mode, aasr_moments **out);
+void aasr_moments_destroy(aasr_moments *h);
+/* Appends n_segments segments of the double frame rows d_frames (device, [n_frames x dim]) on `stream`, no host
+ * wait.  segments (host): [n_segments x 3] = first row, length (>= 1), utterance (any number, handed back by
+ * aasr_moments_get); a segment outside the buffer is AASR_ERR_INVALID and nothing is added.  Calls on one handle go
+ * to one stream. */
+aasr_status aasr_moments_accumulate_dev(aasr_moments *h, const double *d_frames, int64_t n_frames,
+                                        const int32_t *segments, int32_t n_segments, void *stream);
+/* waits until the sums of every segment given so far are on the host */
+aasr_status aasr_moments_fetch(aasr_moments *h, void *stream);
+int64_t aasr_moments_num_segments(const aasr_moments *h);
+/* after a fetch, per segment in the order given: count [n], utterance [n], sum_x [n x dim] and sum_xx --
+ * DIAG: [n x dim], sum x^2; FULL: [n x dim (dim + 1) / 2], the packed lower triangle of sum x x^T, row-major with
+ * j <= i.  Any pointer may be NULL. */
+aasr_status aasr_moments_get(const aasr_moments *h, double *count, int32_t *utterance, double *sum_x, double *sum_xx);
+/* feanorm.cc:181-242 on the host, after a fetch, over the segments in the order given: sums += segment / block_size
+ * and count += length / block_size in double (the division is by block_size whatever the segment's length).
+ * keep [n] or NULL: a segment with keep == 0 is left out.  count [1], sum_x [dim], sum_xx as in aasr_moments_get
+ * for one segment. */
+aasr_status aasr_moments_blocked(const aasr_moments *h, int32_t block_size, const int32_t *keep, double *count,
+                                 double *sum_x, double *sum_xx);
+/* Diagnostic, read-only: out[0] the full-mode kernel's instance PB (16 PB >= dim + 1; 0 in diagonal mode), out[1]
+ * work items and out[2] launches of the last aasr_moments_accumulate_dev call.  Zeros before the first. */
+void aasr_debug_moments_shape(const aasr_moments *h, int32_t *out);
+/* Diagnostic: at most n segments a launch (default: what csrc/moments.h allows), so that a test reaches several
+ * launches with a few segments. */
+aasr_status aasr_debug_moments_set_launch_segments(aasr_moments *h, int32_t n);
+
+/* feanorm.cc:281-325 in double, without LAPACK (the cyclic Jacobi solver of the lda driver).  cov [dim x dim]
+ * symmetric, row-major; scale [dim], the normalization's scale (NULL: ones).  pca [dim x dim], row-major:
+ * row i = eigenvector i of cov, then
+ *   unit_determinant == 0:  pca(i, j) /= sqrt(eigenvalue i), then pca(i, j) /= scale[j]   (unit variance)
+ *   unit_determinant != 0:  pca(i, j) /= scale[j], then pca /= |det pca|^(1 / dim)        (unit determinant)
+ * Row order and sign, which the reference leaves to LAPACK, are defined here: rows by ASCENDING eigenvalue, as dsyev
+ * returns them (a tie: the solver's lower index), and every row's entry of largest magnitude (the first such) is
+ * POSITIVE.  eigenvalues: NULL or [dim], ascending.  A non-positive (or NaN) eigenvalue is AASR_ERR_INVALID and no
+ * matrix, in both branches.  Host only. */
+aasr_status aasr_feanorm_pca(int32_t dim, const double *cov, const double *scale, int32_t unit_determinant, double *pca,
+                             double *eigenvalues);
+
+typedef struct aasr_feanorm_options {
+  int32_t info;             /* -i                                                                   */
+  int32_t block_size;       /* -b: frames per block (1000)                                          */
+  int32_t cov;              /* --cov: estimate and print the covariance                             */
+  int32_t print;            /* -p: print mean and variance                                          */
+  int32_t unit_determinant; /* -u                                                                   */
+  const char *module;       /* -M: the normalization module, or NULL                                */
+  const char *pca;          /* -P: the lin_transform module that receives the PCA, or NULL          */
+  const char *speakers;     /* -S: path of a speaker configuration, or NULL                         */
+  const char *utt;          /* --utt: the speaker file to write, or NULL                            */
+  const char *out;          /* -w: the feature configuration to write, or NULL                      */
+  double blocks;            /* out: the global count (blocks, the tail of an utterance a fraction)  */
+  double seconds_moments;   /* out: device time of the moment launches (events)                     */
+  double seconds_features;  /* out: device time of the feature chain (events)                       */
+} aasr_feanorm_options;
+void aasr_feanorm_default_options(aasr_feanorm_options *opt);
+
+/* feanorm's main (aku/feanorm.cc:65-386).  feat_cfg_text: the feature configuration; the recipe is read without
+ * batching.  Before the device is opened: the reference's refusals with its messages ("Module %s is not a
+ * normalization module", "--utt requires the normalization module (--module)", "Module %s is not a linear
+ * transformation module", "--utt requires --speakers", "unknown module requested: %s"), its warning for -w without
+ * -M, a -P module whose source's dimension is not the statistics' (the reference asserts), a block size below 1 and,
+ * with --cov or -P, more than 127 dimensions (AASR_ERR_UNSUPPORTED).
+ * Per recipe line: -S's set_speaker / set_utterance, the frames (int)(start-time rate) ... (int)(end-time rate)
+ * (0: to the end) of the -M module's FIRST SOURCE (without -M: of the chain's output) in double on the device, cut
+ * into blocks of block_size; the blocks' moments on the device, the blocked sums on the host in recipe order.  The
+ * trailing partial block of an utterance enters the global sums only when the input's end stopped the loop, not
+ * when end-time did (feanorm.cc:178-195); --utt counts it either way.  With --utt the utterances go to the device
+ * one at a time, since every utterance's normalization is set on the module before the next line's speaker change
+ * reads the module back.  Then mean = sum / count, scale = 1 / sqrtf(sum2 / count - mean^2), aasr_feanorm_pca;
+ * -p / --cov print to stdout ("%f "); --utt writes the speaker file (every speaker and utterance); the
+ * normalization (without --utt) and the PCA are set on their modules and -w writes the configuration. */
+aasr_status aasr_run_feanorm_recipe(const char *feat_cfg_text, const char *recipe_path, aasr_feanorm_options *opt,
+                                    aasr_run_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
