@@ -98,6 +98,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                       ("lda", "aku/main_lda.cc"),
                       ("gcluster", "aku/main_gcluster.cc"),
                       ("feanorm", "aku/main_feanorm.cc"),
+                      ("estimate", "aku/main_estimate.cc"),
                       ("aku_adapter_check", "aku/main_adapter_check.cc"),
                       ("feacat", "aku/main_feacat.cc"),
                       ("plugin_check", "aku/main_plugin_check.cc"),

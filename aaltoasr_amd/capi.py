@@ -199,6 +199,44 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_feanorm_default_options.argtypes = [vp]
     L.aasr_feanorm_default_options.restype = None
     L.aasr_run_feanorm_recipe.argtypes = [cp, cp, vp, vp]
+    L.aasr_estimate_create.argtypes = [cp, cp, cp, pvp]
+    L.aasr_estimate_destroy.argtypes = [vp]
+    L.aasr_estimate_destroy.restype = None
+    L.aasr_estimate_add_dump.argtypes = [vp, cp, i32]
+    L.aasr_estimate_set_gaussian_parameters.argtypes = [vp, d, d]
+    L.aasr_estimate_transitions.argtypes = [vp]
+    L.aasr_estimate_ml.argtypes = [vp, i32, i32]
+    L.aasr_estimate_delete_gaussians.argtypes = [vp, d, vp, vp]
+    L.aasr_estimate_remove_mixture_components.argtypes = [vp, d, vp, vp]
+    L.aasr_estimate_split_gaussians.argtypes = [vp, d, i32, i32, d, vp]
+    L.aasr_estimate_write_gk.argtypes = [vp, cp]
+    L.aasr_estimate_write_mc.argtypes = [vp, cp]
+    L.aasr_estimate_write_ph.argtypes = [vp, cp]
+    L.aasr_estimate_sizes.argtypes = [vp, vp]
+    L.aasr_estimate_sizes.restype = None
+    L.aasr_estimate_get_statistics.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.aasr_estimate_get_mixture_statistics.argtypes = [vp, vp, vp, vp]
+    L.aasr_estimate_get_transition_statistics.argtypes = [vp, vp, vp]
+    L.aasr_estimate_get_gaussians.argtypes = [vp, vp, vp]
+    L.aasr_estimate_get_mixtures.argtypes = [vp, vp, vp, vp]
+    L.aasr_estimate_get_transitions.argtypes = [vp, vp, vp, vp]
+    L.aasr_mllt_create.argtypes = [i32, i64, vp, vp, vp, vp, pvp]
+    L.aasr_mllt_destroy.argtypes = [vp]
+    L.aasr_mllt_destroy.restype = None
+    L.aasr_mllt_get_covariances.argtypes = [vp, vp]
+    L.aasr_mllt_variances.argtypes = [vp, vp, vp]
+    L.aasr_mllt_g_sums.argtypes = [vp, vp, vp]
+    L.aasr_mllt_update_rows.argtypes = [i32, vp, d, i32, vp]
+    L.aasr_mllt_estimate.argtypes = [vp, d, vp, vp, vp]
+    L.aasr_debug_mllt_shape.argtypes = [vp, vp]
+    L.aasr_debug_mllt_shape.restype = None
+    L.aasr_debug_mllt_times.argtypes = [vp, vp]
+    L.aasr_debug_mllt_times.restype = None
+    L.aasr_debug_mllt_set_slab_bytes.argtypes = [vp, i64]
+    L.aasr_estimate_run_mllt.argtypes = [vp, vp, vp, vp]
+    L.aasr_estimate_default_options.argtypes = [vp]
+    L.aasr_estimate_default_options.restype = None
+    L.aasr_run_estimate.argtypes = [vp]
     L.aasr_spkc_write_text.argtypes = [vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(i64)]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
@@ -1596,3 +1634,216 @@ def run_feanorm_recipe(cfg_text: str, recipe_path: str, module: Optional[str] = 
     check(lib().aasr_run_feanorm_recipe(cfg_text.encode(), recipe_path.encode(), C.byref(opts), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total, "blocks": opts.blocks,
             "seconds_moments": opts.seconds_moments, "seconds_features": opts.seconds_features}
+
+
+# ---- model re-estimation from statistics dumps ---------------------------------------------------
+
+
+class Estimate:
+    """Owner of an aasr_estimate handle (host only): a model's files with the accumulators that the dumps of stats are
+    added to, the ML update, the pool edits and the writers of aku/estimate.cc."""
+
+    def __init__(self, gk: str, mc: str, ph: str):
+        h = C.c_void_p()
+        check(lib().aasr_estimate_create(gk.encode(), mc.encode(), ph.encode(), C.byref(h)))
+        self._h = h.value
+
+    @classmethod
+    def from_base(cls, base: str) -> "Estimate":
+        return cls(base + ".gk", base + ".mc", base + ".ph")
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_estimate_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sizes(self) -> dict:
+        out = (C.c_int32 * 7)()
+        lib().aasr_estimate_sizes(self._h, out)
+        return dict(zip(("gaussians", "dim", "mixtures", "components", "states", "transitions", "mode"), map(int, out)))
+
+    def add_dump(self, base: str, transitions: bool = False) -> None:
+        check(lib().aasr_estimate_add_dump(self._h, base.encode(), 1 if transitions else 0))
+
+    def set_gaussian_parameters(self, minvar: float = 0.1, covsmooth: float = 0.0) -> None:
+        check(lib().aasr_estimate_set_gaussian_parameters(self._h, float(minvar), float(covsmooth)))
+
+    def estimate_transitions(self) -> None:
+        check(lib().aasr_estimate_transitions(self._h))
+
+    def estimate_ml(self, pool: bool = True, mixtures: bool = True) -> None:
+        check(lib().aasr_estimate_ml(self._h, 1 if pool else 0, 1 if mixtures else 0))
+
+    def delete_gaussians(self, minocc: float):
+        """-> (index map of the pool before the call, Gaussians deleted)"""
+        m, n = np.zeros(self.sizes()["gaussians"], np.int32), C.c_int32()
+        check(lib().aasr_estimate_delete_gaussians(self._h, float(minocc), _ptr(m), C.byref(n)))
+        return m, n.value
+
+    def remove_mixture_components(self, min_weight: float):
+        """-> (index map of the pool before the call, Gaussians deleted)"""
+        m, n = np.zeros(self.sizes()["gaussians"], np.int32), C.c_int32()
+        check(lib().aasr_estimate_remove_mixture_components(self._h, float(min_weight), _ptr(m), C.byref(n)))
+        return m, n.value
+
+    def split_gaussians(self, minocc: float = 0.0, maxmixgauss: int = 0, numgauss: int = -1, splitalpha: float = 1.0) -> int:
+        n = C.c_int32()
+        check(lib().aasr_estimate_split_gaussians(self._h, float(minocc), maxmixgauss, numgauss, float(splitalpha), C.byref(n)))
+        return n.value
+
+    def write(self, base: str) -> None:
+        L = lib()
+        check(L.aasr_estimate_write_mc(self._h, (base + ".mc").encode()))
+        check(L.aasr_estimate_write_ph(self._h, (base + ".ph").encode()))
+        check(L.aasr_estimate_write_gk(self._h, (base + ".gk").encode()))
+
+    def statistics(self) -> dict:
+        """The accumulated statistics in double (sum_xx: [G x dim], or the packed lower triangles in mode 3)."""
+        z, L = self.sizes(), lib()
+        G, D, M, K, T = z["gaussians"], z["dim"], z["mixtures"], z["components"], z["transitions"]
+        xx = D * (D + 1) // 2 if z["mode"] & 2 else D
+        acc, fc, g = np.zeros(G, np.int32), np.zeros(G, np.int32), np.zeros(G)
+        sx, sxx = np.zeros((G, D)), np.zeros((G, xx))
+        check(L.aasr_estimate_get_statistics(self._h, _ptr(acc), _ptr(fc), _ptr(g), _ptr(sx), _ptr(sxx)))
+        macc, moff, mg = np.zeros(M, np.int32), np.zeros(M + 1, np.int32), np.zeros(K)
+        check(L.aasr_estimate_get_mixture_statistics(self._h, _ptr(macc), _ptr(moff), _ptr(mg)))
+        tacc, tocc = np.zeros(T, np.int32), np.zeros(T)
+        check(L.aasr_estimate_get_transition_statistics(self._h, _ptr(tacc), _ptr(tocc)))
+        return {"mode": z["mode"], "accumulated": acc, "feacount": fc, "gamma": g, "sum_x": sx, "sum_xx": sxx,
+                "mix_accumulated": macc, "mix_offsets": moff, "mix_gamma": mg, "trans_accumulated": tacc, "trans_occ": tocc}
+
+    def parameters(self) -> dict:
+        """The current parameters in double."""
+        z, L = self.sizes(), lib()
+        G, D, M, K, T = z["gaussians"], z["dim"], z["mixtures"], z["components"], z["transitions"]
+        mean, var = np.zeros((G, D)), np.zeros((G, D))
+        check(L.aasr_estimate_get_gaussians(self._h, _ptr(mean), _ptr(var)))
+        off, idx, w = np.zeros(M + 1, np.int32), np.zeros(K, np.int32), np.zeros(K)
+        check(L.aasr_estimate_get_mixtures(self._h, _ptr(off), _ptr(idx), _ptr(w)))
+        src, tgt, prob = np.zeros(T, np.int32), np.zeros(T, np.int32), np.zeros(T)
+        check(L.aasr_estimate_get_transitions(self._h, _ptr(src), _ptr(tgt), _ptr(prob)))
+        return {"mean": mean, "var": var, "mix_offsets": off, "mix_index": idx, "mix_weight": w, "trans_source": src,
+                "trans_target": tgt, "trans_prob": prob}
+
+    def run_mllt(self, old_matrix=None):
+        """estimate --mllt over the handle's mode-3 statistics (device) -> A old_matrix in float32 [dim x dim]."""
+        D = self.sizes()["dim"]
+        old = None if old_matrix is None else np.ascontiguousarray(old_matrix, np.float32)
+        out = np.zeros((D, D), np.float32)
+        check(lib().aasr_estimate_run_mllt(self._h, _ptr(old), _ptr(out), None))
+        return out
+
+
+class Mllt:
+    """Owner of an aasr_mllt handle: the Gaussians' covariances resident on the device, the variance and G passes of
+    HmmSet::estimate_mllt over them."""
+
+    def __init__(self, gamma, sum_x, sum_xx, accumulated=None):
+        g = np.ascontiguousarray(gamma, np.float64)
+        sx = np.ascontiguousarray(sum_x, np.float64).reshape(len(g), -1)
+        self.G, self.D = sx.shape
+        self.E = self.D * (self.D + 1) // 2
+        sxx = np.ascontiguousarray(sum_xx, np.float64).reshape(self.G, -1)
+        if sxx.shape[1] != self.E:
+            raise ValueError("sum_xx must hold packed lower triangles [G x dim (dim + 1) / 2]")
+        acc = None if accumulated is None else np.ascontiguousarray(accumulated, np.int32)
+        h = C.c_void_p()
+        check(lib().aasr_mllt_create(self.D, self.G, _ptr(g), _ptr(sx), _ptr(sxx), _ptr(acc), C.byref(h)))
+        self._h = h.value
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_mllt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def covariances(self):
+        out = np.zeros((self.G, self.E))
+        check(lib().aasr_mllt_get_covariances(self._h, _ptr(out)))
+        return out
+
+    def variances(self, A):
+        A = np.ascontiguousarray(A, np.float64)
+        out = np.zeros((self.G, self.D))
+        check(lib().aasr_mllt_variances(self._h, _ptr(A), _ptr(out)))
+        return out
+
+    def g_sums(self, var):
+        """-> [dim x dim (dim + 1) / 2]: the packed lower triangle of sum_g (gamma_g / var_gi) S_g per dimension i."""
+        v = np.ascontiguousarray(var, np.float64)
+        out = np.zeros((self.D, self.E))
+        check(lib().aasr_mllt_g_sums(self._h, _ptr(v), _ptr(out)))
+        return out
+
+    def estimate(self, minvar: float = 0.1):
+        """The whole loop -> (A [dim x dim], mean [G x dim], var [G x dim]); rows of skipped Gaussians are zero."""
+        A, mean, var = np.zeros((self.D, self.D)), np.zeros((self.G, self.D)), np.zeros((self.G, self.D))
+        check(lib().aasr_mllt_estimate(self._h, float(minvar), _ptr(A), _ptr(mean), _ptr(var)))
+        return A, mean, var
+
+    def set_slab_bytes(self, nbytes: int) -> None:
+        """Diagnostic: the bound on a launch's slab memory."""
+        check(lib().aasr_debug_mllt_set_slab_bytes(self._h, nbytes))
+
+    def launch_shape(self) -> dict:
+        out = (C.c_int32 * 3)()
+        lib().aasr_debug_mllt_shape(self._h, out)
+        return {"pb": int(out[0]), "items": int(out[1]), "launches": int(out[2])}
+
+    def times(self) -> dict:
+        out = (C.c_double * 4)()
+        lib().aasr_debug_mllt_times(self._h, out)
+        return dict(zip(("cov_build", "variances", "g_sums", "host_solve"), map(float, out)))
+
+
+def mllt_update_rows(A, g_inv, beta: float, iterations: int = 1):
+    """aku/HmmSet.cc:955-980 (host only): `iterations` inner updates of A from the inverted G_i [dim x dim x dim]."""
+    A = np.array(A, np.float64, order="C")
+    gi = np.ascontiguousarray(g_inv, np.float64)
+    check(lib().aasr_mllt_update_rows(A.shape[0], _ptr(gi), float(beta), iterations, _ptr(A)))
+    return A
+
+
+class EstimateOptions(C.Structure):
+    """aasr_estimate_options: estimate's options (aku/estimate.cc:115-155) for --ml."""
+    _fields_ = [("gk", C.c_char_p), ("mc", C.c_char_p), ("ph", C.c_char_p), ("base_name", C.c_char_p),
+                ("config", C.c_char_p), ("list", C.c_char_p), ("out", C.c_char_p), ("mllt", C.c_char_p),
+                ("savesum", C.c_char_p), ("transitions", C.c_int32), ("info", C.c_int32), ("minvar", C.c_double),
+                ("covsmooth", C.c_double), ("delete_set", C.c_int32), ("delete_minocc", C.c_double),
+                ("mremove_set", C.c_int32), ("mremove", C.c_double), ("split", C.c_int32), ("minocc_set", C.c_int32),
+                ("minocc", C.c_double), ("maxmixgauss", C.c_int32), ("numgauss_set", C.c_int32), ("numgauss", C.c_int32),
+                ("splitalpha", C.c_double), ("no_mixture_update", C.c_int32), ("no_write", C.c_int32),
+                ("n_deleted", C.c_int32), ("n_removed", C.c_int32), ("n_splits", C.c_int32), ("seconds_read", C.c_double),
+                ("seconds_mllt", C.c_double), ("seconds_mllt_parts", C.c_double * 4)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "EstimateOptions":
+        o = cls()
+        lib().aasr_estimate_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_estimate(base: str, list_path: str, out: str, config: Optional[str] = None, mllt: Optional[str] = None,
+                 savesum: Optional[str] = None, opts: Optional[EstimateOptions] = None) -> dict:
+    """estimate --ml -b base -L list_path -o out [-c config] [--mllt MODULE] [-s savesum] -> the run's counts and times."""
+    opts = opts or EstimateOptions.defaults()
+    enc = lambda s: s.encode() if s else None
+    opts.gk, opts.mc, opts.ph, opts.base_name = enc(base + ".gk"), enc(base + ".mc"), enc(base + ".ph"), enc(base)
+    opts.config, opts.list, opts.out, opts.mllt, opts.savesum = enc(config), enc(list_path), enc(out), enc(mllt), enc(savesum)
+    check(lib().aasr_run_estimate(C.byref(opts)))
+    return {"n_deleted": opts.n_deleted, "n_removed": opts.n_removed, "n_splits": opts.n_splits,
+            "seconds_read": opts.seconds_read, "seconds_mllt": opts.seconds_mllt,
+            "seconds_mllt_parts": list(opts.seconds_mllt_parts)}

@@ -19,6 +19,7 @@
 #include "feat.h"
 #include "gmm.h"
 #include "mllr.h"
+#include "mllt.h"
 #include "recipe_pass.h"
 
 using namespace aasr;
@@ -200,7 +201,7 @@ namespace aasr {
 // entry of largest magnitude at or below the diagonal, the first such), the inverse from the factors (dgetri's
 // result); *det: the product of U's diagonal WITHOUT the permutation's sign, which is what the reference multiplies
 // up after LUFactorizeIP (MllrTrainer.cc:207-211).  false: a zero pivot.
-static bool lu_inverse(std::vector<double> &a, int n, double *det) {
+bool lu_inverse(std::vector<double> &a, int n, double *det) {  // shared with estimate.cc (mllt.h)
   std::vector<int> piv((size_t)n);
   for (int c = 0; c < n; c++) {
     int p = c;

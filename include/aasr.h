@@ -1025,6 +1025,145 @@ void aasr_feanorm_default_options(aasr_feanorm_options *opt);
 aasr_status aasr_run_feanorm_recipe(const char *feat_cfg_text, const char *recipe_path, aasr_feanorm_options *opt,
                                     aasr_run_stats *stats);
 
+/* ---------------------------------------------------------------------------
+ * Model re-estimation from statistics dumps: aku/estimate.cc --ml over diagonal pools.
+ *
+ * The estimation handle, host only: a model's .gk / .mc / .ph files with the accumulators that the dumps of stats
+ * (.gks, .mcs, .phs, .lls) are added to.  Pools with full-covariance or subspace Gaussians are
+ * AASR_ERR_UNSUPPORTED.  State s emits mixture s; the transitions are numbered in state order, as HmmSet numbers
+ * them. */
+typedef struct aasr_estimate aasr_estimate;
+aasr_status aasr_estimate_create(const char *gk, const char *mc, const char *ph, aasr_estimate **out);
+void aasr_estimate_destroy(aasr_estimate *h);
+/* Adds base.gks and base.mcs, base.phs when transitions != 0, and the lines of base.lls, in double
+ * (HmmSet::accumulate_{gk,mc,ph}_from_dump, aku/HmmSet.cc:655-765).  The first dump's mode word fixes the accumulator
+ * kind for the handle's life: 1 diagonal second moments, 3 the packed lower triangle (PDF_ML_FULL_STATS); a mode with
+ * discriminative bits is AASR_ERR_UNSUPPORTED.  The reference's errors, with its messages: a wrong pool size,
+ * dimension, pdf count or transition count, a negative feacount, a pdf index outside the pool, a transition that
+ * cannot be found.  A missing .phs is only a message on stderr; a .phs that ends before its first line is allowed,
+ * and one that ends later repeats its last line up to the announced count, as the reference's reader does. */
+aasr_status aasr_estimate_add_dump(aasr_estimate *h, const char *base, int32_t transitions);
+/* --minvar (0.1) and --covsmooth (0; without effect on diagonal Gaussians) */
+aasr_status aasr_estimate_set_gaussian_parameters(aasr_estimate *h, double minvar, double covsmooth);
+/* HmmSet::estimate_transition_parameters (aku/HmmSet.cc:782-815): per state the counts over their FLOAT running sum,
+ * floored at 0.001; a state without counts keeps its probabilities.  Nothing happens before the first .phs. */
+aasr_status aasr_estimate_transitions(aasr_estimate *h);
+/* The ML update.  pool != 0: per Gaussian mean = sum_x (1 / gamma), variance = sum_xx_i / gamma - mean_i mean_i
+ * (mode 3: the diagonal of sum_xx (1 / gamma) - mean mean^T), floored at minvar; mixtures != 0: per state's mixture
+ * weight_k = gamma_k / sum gamma.  A Gaussian or mixture without statistics keeps its parameters and gets the
+ * reference's warning on stderr. */
+aasr_status aasr_estimate_ml(aasr_estimate *h, int32_t pool, int32_t mixtures);
+/* The pool edits (aku/HmmSet.cc:1058-1350).  index_map: NULL or [pool size before the call], the Gaussian's new index
+ * or -1.  Where the reference's std::sort leaves Gaussians of equal occupancy in any order, the lower index goes
+ * first. */
+aasr_status aasr_estimate_delete_gaussians(aasr_estimate *h, double minocc, int32_t *index_map, int32_t *n_deleted);
+aasr_status aasr_estimate_remove_mixture_components(aasr_estimate *h, double min_weight, int32_t *index_map,
+                                                    int32_t *n_deleted);
+aasr_status aasr_estimate_split_gaussians(aasr_estimate *h, double minocc, int32_t maxmixgauss, int32_t numgauss,
+                                          double splitalpha, int32_t *n_splits);
+/* PDFPool::write_gk, HmmSet::write_mc, HmmSet::write_legacy_ph: six significant digits ("%g") */
+aasr_status aasr_estimate_write_gk(const aasr_estimate *h, const char *path);
+aasr_status aasr_estimate_write_mc(const aasr_estimate *h, const char *path);
+aasr_status aasr_estimate_write_ph(const aasr_estimate *h, const char *path);
+/* out[7]: Gaussians, dimension, mixtures, mixture components, states, transitions, statistics mode (0: no dump yet) */
+void aasr_estimate_sizes(const aasr_estimate *h, int32_t *out);
+/* The accumulated statistics.  Per Gaussian: accumulated [G] (0 / 1), feacount [G], gamma [G], sum_x [G x dim],
+ * sum_xx [G x dim] (mode 1) or [G x dim (dim + 1) / 2] (mode 3, row-major with j <= i).  Per mixture: accumulated [M],
+ * offsets [M + 1] into gamma [components].  Per transition: accumulated [T], occupancy [T].  Any pointer may be NULL. */
+aasr_status aasr_estimate_get_statistics(const aasr_estimate *h, int32_t *accumulated, int32_t *feacount, double *gamma,
+                                         double *sum_x, double *sum_xx);
+aasr_status aasr_estimate_get_mixture_statistics(const aasr_estimate *h, int32_t *accumulated, int32_t *offsets,
+                                                 double *gamma);
+aasr_status aasr_estimate_get_transition_statistics(const aasr_estimate *h, int32_t *accumulated, double *occupancy);
+/* The current parameters: mean, var [G x dim]; offsets [M + 1], index and weight [components]; source, target (offset
+ * relative to the source's place in its HMM) and prob [T].  Any pointer may be NULL. */
+aasr_status aasr_estimate_get_gaussians(const aasr_estimate *h, double *mean, double *var);
+aasr_status aasr_estimate_get_mixtures(const aasr_estimate *h, int32_t *offsets, int32_t *index, double *weight);
+aasr_status aasr_estimate_get_transitions(const aasr_estimate *h, int32_t *source, int32_t *target, double *prob);
+
+/* MLLT (HmmSet::estimate_mllt, aku/HmmSet.cc:841-1056) on the device (csrc/mllt.hip).  The handle builds the
+ * covariances S_g = sum_xx_g (1 / gamma_g) - mean_g mean_g^T once and keeps them resident in double.  gamma [G],
+ * sum_x [G x dim], sum_xx [G x dim (dim + 1) / 2] packed lower triangles; accumulated [G] or NULL (all): a Gaussian
+ * with 0 is skipped everywhere (zero covariance, zero weight).  1 ... 63 dimensions (AASR_ERR_UNSUPPORTED beyond).
+ * Deterministic: no atomics; the same input gives the same bytes, whatever the slab bound cuts a call into. */
+typedef struct aasr_mllt aasr_mllt;
+aasr_status aasr_mllt_create(int32_t dim, int64_t n_gauss, const double *gamma, const double *sum_x, const double *sum_xx,
+                             const int32_t *accumulated, aasr_mllt **out);
+void aasr_mllt_destroy(aasr_mllt *h);
+/* the resident covariances, [G x dim (dim + 1) / 2] packed lower triangles */
+aasr_status aasr_mllt_get_covariances(aasr_mllt *h, double *cov);
+/* var [G x dim]: var_gi = a_i S_g a_i^T for the rows a_i of A [dim x dim], not floored */
+aasr_status aasr_mllt_variances(aasr_mllt *h, const double *A, double *var);
+/* g_sums [dim x dim (dim + 1) / 2]: the packed lower triangle of sum_g (gamma_g / var_gi) S_g for every i, on the FP64
+ * matrix pipe */
+aasr_status aasr_mllt_g_sums(aasr_mllt *h, const double *var, double *g_sums);
+/* Host only: `iterations` inner updates of A [dim x dim] (aku/HmmSet.cc:955-980).  Each takes the cofactors
+ * C = |det A| (A^T)^-1 of the current A once and then replaces EVERY row from them: row_i = G_i^T c_i, scaled by
+ * sqrt(beta / c_i . row_i).  g_inv [dim x dim x dim]: the inverted G_i, row-major. */
+aasr_status aasr_mllt_update_rows(int32_t dim, const double *g_inv, double beta, int32_t iterations, double *A);
+/* The whole loop from A = I: 7 times (variances floored at minvar, G sums, their inverses, 80 inner updates,
+ * A / |det A|^(1 / dim)), then mean [G x dim] = A mean_g and var [G x dim] = the floored variances under the final A;
+ * rows of skipped Gaussians are left as they are.  mean and var may be NULL. */
+aasr_status aasr_mllt_estimate(aasr_mllt *h, double minvar, double *A, double *mean, double *var);
+/* Diagnostic, read-only: out[0] the kernels' instance PB (16 PB >= dim), out[1] work items and out[2] launches of the
+ * last aasr_mllt_g_sums pass.  Zeros before the first. */
+void aasr_debug_mllt_shape(const aasr_mllt *h, int32_t *out);
+/* Diagnostic: out[4] = seconds (host clock, transfers included) of the covariance build, of all variance passes, of
+ * all G passes and of the host solves so far. */
+void aasr_debug_mllt_times(const aasr_mllt *h, double *out);
+/* Diagnostic: the bound on a launch's slab memory in bytes (default 64 MiB, csrc/mllt.h; at least one item's slab is
+ * always allowed). */
+aasr_status aasr_debug_mllt_set_slab_bytes(aasr_mllt *h, int64_t bytes);
+/* estimate --mllt on a handle whose dumps are mode 3 (AASR_ERR_INVALID otherwise, naming stats --mllt): the loop
+ * above over the handle's statistics, the new means and variances into the pool, the mixtures as in the ML update.
+ * old_matrix [dim x dim] or NULL (identity); new_matrix [dim x dim] = A old_matrix in float.  seconds: NULL or [4],
+ * as aasr_debug_mllt_times. */
+aasr_status aasr_estimate_run_mllt(aasr_estimate *h, const float *old_matrix, float *new_matrix, double *seconds);
+
+typedef struct aasr_estimate_options {
+  const char *gk, *mc, *ph;     /* the previous model (-b, or -g / -m / -p)                            */
+  const char *base_name;        /* what --savesum prints: -b's value, or the .gk path (NULL)           */
+  const char *config;           /* -c: path of the feature configuration, or NULL                      */
+  const char *list;             /* -L: file with one dump base name per line                           */
+  const char *out;              /* -o: base name of the output model                                   */
+  const char *mllt;             /* --mllt: the lin_transform module, or NULL                           */
+  const char *savesum;          /* -s: the summary file to append to, or NULL                          */
+  int32_t transitions;          /* -t                                                                  */
+  int32_t info;                 /* -i                                                                  */
+  double minvar;                /* --minvar (0.1)                                                      */
+  double covsmooth;             /* --covsmooth (0)                                                     */
+  int32_t delete_set;           /* --delete given                                                      */
+  double delete_minocc;         /* --delete                                                            */
+  int32_t mremove_set;          /* --mremove given                                                     */
+  double mremove;               /* --mremove                                                           */
+  int32_t split;                /* --split                                                             */
+  int32_t minocc_set;           /* --minocc given                                                      */
+  double minocc;                /* --minocc (0)                                                        */
+  int32_t maxmixgauss;          /* --maxmixgauss (0)                                                   */
+  int32_t numgauss_set;         /* --numgauss given                                                    */
+  int32_t numgauss;             /* --numgauss (-1)                                                     */
+  double splitalpha;            /* --splitalpha (1)                                                    */
+  int32_t no_mixture_update;    /* --no-mixture-update                                                 */
+  int32_t no_write;             /* --no-write                                                          */
+  int32_t n_deleted;            /* out: Gaussians deleted by --delete                                  */
+  int32_t n_removed;            /* out: Gaussians deleted by --mremove                                 */
+  int32_t n_splits;             /* out: Gaussians split                                                */
+  double seconds_read;          /* out: reading and adding the dumps                                   */
+  double seconds_mllt;          /* out: the MLLT estimation, configuration load included               */
+  double seconds_mllt_parts[4]; /* out: as aasr_debug_mllt_times                                       */
+} aasr_estimate_options;
+void aasr_estimate_default_options(aasr_estimate_options *opt);
+
+/* estimate's main (aku/estimate.cc:158-425) for --ml.  In this order: "Either --minocc or --numgauss is required with
+ * --split"; "Must specify configuration file with MLLT"; the model; with --mllt, before any dump is read and before
+ * the device is opened: "Module %s is not a transform module", a module whose matrix is not dim x dim, more than 63
+ * dimensions (AASR_ERR_UNSUPPORTED); the dumps of the list in order; with --mllt, dumps that are not mode 3 are
+ * refused (the reference would invert a zero matrix).  Then the transitions (-t), the ML update or MLLT, --delete,
+ * --mremove, --split, the writers (out.mc, out.ph, out.gk; out.cfg with -c) and the summary, appended with 12 digits.
+ * --no-write writes nothing.  The device is opened only for --mllt and for writing out.cfg (the configuration writer
+ * belongs to the feature handle); --ml without -c runs on a machine without one. */
+aasr_status aasr_run_estimate(aasr_estimate_options *opt);
+
 #ifdef __cplusplus
 }
 #endif
