@@ -99,6 +99,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                       ("gcluster", "aku/main_gcluster.cc"),
                       ("feanorm", "aku/main_feanorm.cc"),
                       ("estimate", "aku/main_estimate.cc"),
+                      ("tie", "aku/main_tie.cc"),
                       ("aku_adapter_check", "aku/main_adapter_check.cc"),
                       ("feacat", "aku/main_feacat.cc"),
                       ("plugin_check", "aku/main_plugin_check.cc"),

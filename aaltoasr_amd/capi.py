@@ -59,6 +59,8 @@ class RecipeTiming(C.Structure):
 
 
 _lib: Optional[C.CDLL] = None
+# aasr_tie_gain_fn: (user, n_members, members, n_set, set) -> gain
+TIE_GAIN_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32))
 
 
 def declared_symbols() -> list:
@@ -237,6 +239,31 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_estimate_default_options.argtypes = [vp]
     L.aasr_estimate_default_options.restype = None
     L.aasr_run_estimate.argtypes = [vp]
+    # state tying
+    ptext = [C.POINTER(vp), C.POINTER(i64)]
+    L.aasr_tie_parse_label.argtypes = [cp] + ptext
+    L.aasr_tie_create.argtypes = [i32, cp, pvp]
+    L.aasr_tie_destroy.argtypes = [vp]
+    L.aasr_tie_destroy.restype = None
+    L.aasr_tie_num_rules.argtypes = [vp]
+    L.aasr_tie_num_classes.argtypes = [vp]
+    L.aasr_tie_rules_text.argtypes = [vp] + ptext
+    L.aasr_tie_context_phone.argtypes = [vp, cp, i32, C.POINTER(i32)]
+    L.aasr_tie_set_stats.argtypes = [vp, vp, vp, vp]
+    L.aasr_tie_evaluate.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.aasr_tie_split.argtypes = [vp, i32, d, i32, i32, i32]
+    L.aasr_tie_merge.argtypes = [vp, d, i32]
+    L.aasr_tie_clusters_text.argtypes = [vp] + ptext
+    L.aasr_tie_basebind_text.argtypes = [vp, i32] + ptext
+    L.aasr_tie_write_basebind.argtypes = [vp, cp, i32]
+    L.aasr_tie_write_model.argtypes = [vp, cp, i32]
+    L.aasr_debug_tie_set_occupancy.argtypes = [vp, vp]
+    L.aasr_debug_tie_split_given.argtypes = [vp, i32, d, i32, TIE_GAIN_FN, vp]
+    L.aasr_debug_tie_shape.argtypes = [vp, vp]
+    L.aasr_debug_tie_shape.restype = None
+    L.aasr_tie_default_options.argtypes = [vp]
+    L.aasr_tie_default_options.restype = None
+    L.aasr_run_tie_recipe.argtypes = [cp, cp, vp, vp]
     L.aasr_spkc_write_text.argtypes = [vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(i64)]
     L.aasr_version.restype = cp
     L.aasr_device_count.restype = C.c_int
@@ -1847,3 +1874,169 @@ def run_estimate(base: str, list_path: str, out: str, config: Optional[str] = No
     return {"n_deleted": opts.n_deleted, "n_removed": opts.n_removed, "n_splits": opts.n_splits,
             "seconds_read": opts.seconds_read, "seconds_mllt": opts.seconds_mllt,
             "seconds_mllt_parts": list(opts.seconds_mllt_parts)}
+
+
+# ---- decision-tree state tying ------------------------------------------------------------------
+
+def _take_text(call) -> bytes:
+    out, n = C.c_void_p(), C.c_int64()
+    check(call(C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out, n.value)
+    finally:
+        lib().aasr_free(out)
+
+
+def tie_parse_label(label: str):
+    """PhonePool's label functions (host only): -> (centre, left contexts, right contexts), nearest first."""
+    c, l, r = _take_text(lambda o, n: lib().aasr_tie_parse_label(label.encode("latin-1"), o, n)).decode("latin-1").split("\n")
+    return c, (l.split("\x1f") if l else []), (r.split("\x1f") if r else [])
+
+
+class TieOptions(C.Structure):
+    """aasr_tie_options: tie's options (aku/tie.cc:115-136) over .phn files."""
+    _fields_ = [("ophn", C.c_int32), ("hmmnet", C.c_int32), ("info", C.c_int32), ("count", C.c_int32),
+                ("context", C.c_int32), ("mloss_given", C.c_int32), ("hops", C.c_int32), ("clusters", C.c_int32),
+                ("sgain", C.c_double), ("mloss", C.c_double), ("rule", C.c_char_p), ("speakers", C.c_char_p),
+                ("out", C.c_char_p), ("basebind", C.c_char_p), ("seconds_scatter", C.c_double),
+                ("seconds_features", C.c_double), ("seconds_split", C.c_double), ("seconds_merge", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "TieOptions":
+        o = cls()
+        lib().aasr_tie_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+class Tie:
+    """Owner of an aasr_tie handle: rules, context phones, their statistics on the device, the trees."""
+
+    def __init__(self, dim: int, rule_path: str):
+        h = C.c_void_p()
+        check(lib().aasr_tie_create(dim, rule_path.encode(), C.byref(h)))
+        self._h = h.value
+        self.D = dim
+        self.E = 1 + dim + dim * (dim + 1) // 2
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_tie_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rules(self):
+        """[(name, [phones in set order])]"""
+        t = _take_text(lambda o, n: lib().aasr_tie_rules_text(self._h, o, n)).decode("latin-1")
+        return [(f[0], f[1:]) for f in (line.split("\x1f") for line in t.split("\n")[:-1])]
+
+    def context_phone(self, label: str, state: int) -> int:
+        c = C.c_int32()
+        check(lib().aasr_tie_context_phone(self._h, label.encode("latin-1"), state, C.byref(c)))
+        return c.value
+
+    def num_classes(self) -> int:
+        return int(lib().aasr_tie_num_classes(self._h))
+
+    def set_stats(self, gamma, sum_x, sum_xx) -> None:
+        """aasr_scatter_get's layout: gamma [C], sum_x [C x dim], sum_xx [C x dim (dim + 1) / 2]."""
+        g, sx = np.ascontiguousarray(gamma, np.float64), np.ascontiguousarray(sum_x, np.float64)
+        sxx = np.ascontiguousarray(sum_xx, np.float64)
+        n = self.num_classes()
+        if g.shape != (n,) or sx.shape != (n, self.D) or sxx.shape != (n, self.D * (self.D + 1) // 2):
+            raise ValueError("statistics do not match %d classes of %d dimensions" % (n, self.D))
+        check(lib().aasr_tie_set_stats(self._h, _ptr(g), _ptr(sx), _ptr(sxx)))
+
+    def set_occupancy(self, gamma) -> None:
+        """Diagnostic, host only: the frame counts alone."""
+        g = np.ascontiguousarray(gamma, np.float64)
+        if g.shape != (self.num_classes(),):
+            raise ValueError("one occupancy per class")
+        check(lib().aasr_debug_tie_set_occupancy(self._h, _ptr(g)))
+
+    def evaluate(self, jobs, cands=(), want_sums: bool = True):
+        """jobs: [(members, masks)] with masks a 0/1 array [rows x len(members)]; cands: [(parent row, child 1 row,
+        child 2 row or -1)] over the jobs' rows numbered through.  -> (sums [rows x E] or None, gains)."""
+        job_k, job_rows, idx, words = [], [], [], []
+        for members, masks in jobs:
+            members = np.asarray(members, np.int32).reshape(-1)
+            masks = np.asarray(masks, np.uint8).reshape(-1, len(members)) if len(members) else \
+                np.zeros((np.asarray(masks).shape[0], 0), np.uint8)
+            k, wpr = len(members), (len(members) + 31) // 32
+            w = np.zeros((masks.shape[0], wpr), np.uint32)
+            for b in range(k):
+                w[:, b >> 5] |= (masks[:, b].astype(np.uint32) & 1) << np.uint32(b & 31)
+            job_k.append(k)
+            job_rows.append(masks.shape[0])
+            idx.append(members)
+            words.append(w.reshape(-1))
+        job_k, job_rows = np.asarray(job_k, np.int32), np.asarray(job_rows, np.int32)
+        idx = np.ascontiguousarray(np.concatenate(idx) if idx else np.zeros(0), np.int32)
+        words = np.ascontiguousarray(np.concatenate(words) if words else np.zeros(0), np.uint32)
+        cd = np.ascontiguousarray(np.asarray(cands, np.int32).reshape(-1, 3))
+        rows = int(job_rows.sum())
+        sums = np.zeros((rows, self.E)) if want_sums else None
+        gain = np.zeros(len(cd))
+        check(lib().aasr_tie_evaluate(self._h, len(job_k), _ptr(job_k), _ptr(job_rows), _ptr(idx) if len(idx) else None,
+                                      _ptr(words) if len(words) else None, _ptr(sums), len(cd),
+                                      _ptr(cd) if len(cd) else None, _ptr(gain) if len(cd) else None))
+        return sums, gain
+
+    def split(self, count: int = 100, sgain: float = 0.0, context: int = 1, hops: int = 1, info: int = 0) -> None:
+        check(lib().aasr_tie_split(self._h, count, float(sgain), context, hops, info))
+
+    def split_given(self, gain_of, count: int = 100, sgain: float = 0.0, context: int = 1) -> None:
+        """Diagnostic, host only: the split loop with gain_of(members, new_set) -> gain in place of the device."""
+        def fn(_user, nm, mem, ns, st):
+            return float(gain_of([mem[i] for i in range(nm)], [st[i] for i in range(ns)]))
+        check(lib().aasr_debug_tie_split_given(self._h, count, float(sgain), context, TIE_GAIN_FN(fn), None))
+
+    def merge(self, mloss: float, info: int = 0) -> None:
+        check(lib().aasr_tie_merge(self._h, float(mloss), info))
+
+    def clusters(self):
+        """The clusters in final order: [{"phone", "state", "index", "occ", "members", "rules"}]; rules: a list of
+        rule sets, each [(rule name, context index, answer)]."""
+        t = _take_text(lambda o, n: lib().aasr_tie_clusters_text(self._h, o, n)).decode("latin-1")
+        out = []
+        for line in t.split("\n")[:-1]:
+            ph, st, si, occ, mem, rules = line.split("\x1f")
+            sets = [[(r.rsplit(":", 2)[0], int(r.rsplit(":", 2)[1]), r.rsplit(":", 2)[2] == "1") for r in s.split(",")]
+                    for s in rules.split("|")] if rules else []
+            out.append({"phone": ph, "state": int(st), "index": int(si), "occ": float(occ),
+                        "members": [int(m) for m in mem.split(",")] if mem else [], "rules": sets})
+        return out
+
+    def basebind(self, context: int = 1) -> bytes:
+        return _take_text(lambda o, n: lib().aasr_tie_basebind_text(self._h, context, o, n))
+
+    def write_basebind(self, path: str, context: int = 1) -> None:
+        check(lib().aasr_tie_write_basebind(self._h, path.encode(), context))
+
+    def write_model(self, base: str, context: int = 1) -> None:
+        check(lib().aasr_tie_write_model(self._h, base.encode(), context))
+
+    def shape(self) -> dict:
+        """Diagnostic: the last batch's work items per hop, its sides and candidates; the rounds of the last runs."""
+        out = (C.c_int32 * 6)()
+        lib().aasr_debug_tie_shape(self._h, out)
+        return dict(zip(("items_hop1", "items_hop2", "sides", "candidates", "rounds_split", "rounds_merge"), map(int, out)))
+
+
+def run_tie_recipe(cfg_text: str, recipe_path: str, rule: str, out: Optional[str] = None, basebind: Optional[str] = None,
+                   speakers: Optional[str] = None, opts: Optional[TieOptions] = None) -> dict:
+    """The tie tool's run -> its counts and times."""
+    opts = opts or TieOptions.defaults()
+    opts.rule, opts.out = rule.encode(), (out.encode() if out else None)
+    opts.basebind, opts.speakers = (basebind.encode() if basebind else None), (speakers.encode() if speakers else None)
+    st = RunStats()
+    check(lib().aasr_run_tie_recipe(cfg_text.encode(), recipe_path.encode(), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "clusters": opts.clusters, "seconds_total": st.seconds_total,
+            "seconds_features": opts.seconds_features, "seconds_scatter": opts.seconds_scatter,
+            "seconds_split": opts.seconds_split, "seconds_merge": opts.seconds_merge}

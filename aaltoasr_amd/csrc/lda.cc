@@ -199,6 +199,8 @@ aasr_status aasr_debug_scatter_set_slab_bytes(aasr_scatter *h, int64_t bytes) {
 
 namespace aasr {
 
+const double *scatter_device_accumulator(const aasr_scatter *h) { return h->acc.p; }
+
 // Cyclic Jacobi on the symmetric n x n row-major matrix a: on return a's diagonal holds the eigenvalues and the
 // COLUMNS of v the eigenvectors.  Every rotation annihilates one off-diagonal pair (Rutishauser's formulas); sweeps
 // until the off-diagonal sum of squares is below eps^2 of the matrix's.

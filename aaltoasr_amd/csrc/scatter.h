@@ -66,3 +66,10 @@ void scatter_launch(const ScatterParams &p, int item0, int n_items, const Scatte
                     double *acc, hipStream_t stream);
 
 }  // namespace aasr
+
+struct aasr_scatter;
+namespace aasr {
+// a handle's accumulator on the device, [classes x scatter_class_doubles(dim)] in the tile layout above (lda.cc), for
+// a driver that goes on working with the sums where they are (tie.cc)
+const double *scatter_device_accumulator(const aasr_scatter *h);
+}  // namespace aasr

@@ -1164,6 +1164,100 @@ void aasr_estimate_default_options(aasr_estimate_options *opt);
  * belongs to the feature handle); --ml without -c runs on a machine without one. */
 aasr_status aasr_run_estimate(aasr_estimate_options *opt);
 
+/* ---------------------------------------------------------------------------
+ * Decision-tree state tying: aku/tie.cc over aku/PhonePool.cc.
+ *
+ * A CONTEXT PHONE is a label ("a-b+c", "x-a-b+c+y", "b") with a state number; its class index is the order of its
+ * first mention.  Per class the handle keeps the raw sums gamma, sum x, sum x x^T as one row on the device; a
+ * cluster's statistic is the sum of its members' rows (csrc/tie.h).  One tree per centre phone and state is grown by
+ * the rules of the rule file; candidates are chosen on the host (frame counts are integers), their sums and
+ * likelihood gains come from the device (csrc/tie_split.hip), the winner is picked on the host with the reference's
+ * strict comparisons in the reference's order (rule outer, context index inner).  A covariance that is not positive
+ * definite is no special case: the plain column Cholesky yields NaN or an infinity and the comparisons do what they do.
+ *
+ * 1 ... 63 dimensions (AASR_ERR_UNSUPPORTED beyond: one d x d matrix of doubles has to fit 32 KiB of LDS).
+ * Parity with the reference binary is not pinned: no reference tie is built (it needs LAPACK++). */
+typedef struct aasr_tie aasr_tie;
+/* PhonePool::center_phone / fill_left_contexts / fill_right_contexts: text (aasr_free) = "centre\nleft\nright", the
+ * contexts nearest first and separated by \x1f.  Host only. */
+aasr_status aasr_tie_parse_label(const char *label, char **text, int64_t *len);
+/* Reads the rule file ("NAME context p1,p2,..." per line, the type in any letter case); the reference's messages for
+ * a short line, an unknown type and a rule without phones.  Host only. */
+aasr_status aasr_tie_create(int32_t dim, const char *rule_path, aasr_tie **out);
+void aasr_tie_destroy(aasr_tie *h);
+int32_t aasr_tie_num_rules(const aasr_tie *h);
+int32_t aasr_tie_num_classes(const aasr_tie *h);
+/* text (aasr_free): per rule "NAME\x1fphone\x1fphone...\n", the phones in set order */
+aasr_status aasr_tie_rules_text(const aasr_tie *h, char **text, int64_t *len);
+/* PhonePool::get_context_phone: the class of (label, state), new or known.  Refused once statistics are set.  Host only. */
+aasr_status aasr_tie_context_phone(aasr_tie *h, const char *label, int32_t state, int32_t *cls);
+/* The classes' statistics from host arrays in aasr_scatter_get's layout (gamma [C], sum_x [C x dim], sum_xx
+ * [C x dim (dim + 1) / 2]), uploaded as rows.  They must be finite. */
+aasr_status aasr_tie_set_stats(aasr_tie *h, const double *gamma, const double *sum_x, const double *sum_xx);
+/* The kernel pair on caller-given lists.  Job j: job_k[j] classes (its slice of idx, any order) and job_rows[j] masks
+ * over that list, (job_k[j] + 31) / 32 words each, bit k % 32 of word k / 32 for list position k; the jobs' lists and
+ * masks follow each other in idx and mask.  Output row = sum of the listed classes' rows whose bit is set; the jobs'
+ * rows are numbered through.  sums (or NULL): [rows x E], E = 1 + dim + dim (dim + 1) / 2 = [gamma, sum x, packed
+ * lower triangle].  Candidate c = cands[3 c ...] = (parent row, child 1 row, child 2 row or -1 for parent - child 1);
+ * gain [n_cands] = (gamma_p ld_p - gamma_1 ld_1 - gamma_2 ld_2) / 2 with ld = 2 sum log L_ii of the side's
+ * covariance.  Same input, same bytes. */
+aasr_status aasr_tie_evaluate(aasr_tie *h, int32_t n_jobs, const int32_t *job_k, const int32_t *job_rows, const int32_t *idx,
+                              const uint32_t *mask, double *sums, int32_t n_cands, const int32_t *cands, double *gain);
+/* PhonePool::decision_tree_cluster_context_phones: min_count --count, sgain --sgain, max_context --context (<= 0: every
+ * context index the phone has).  hops 2: members -> sums per (context index, label) -> candidates; hops 1: members ->
+ * candidates.  One launch sequence per round of all trees. */
+aasr_status aasr_tie_split(aasr_tie *h, int32_t min_count, double sgain, int32_t max_context, int32_t hops, int32_t info);
+/* PhonePool::merge_context_phones with --mloss. */
+aasr_status aasr_tie_merge(aasr_tie *h, double mloss, int32_t info);
+/* The clusters in their final order (the state numbering), text (aasr_free): per cluster
+ * "phone\x1fstate\x1fstate index\x1foccupancy\x1fclass,class,...\x1frule:context:answer,...|rule:context:answer,...\n"
+ * -- the rule sets a merge has joined are separated by '|'. */
+aasr_status aasr_tie_clusters_text(aasr_tie *h, char **text, int64_t *len);
+/* PhonePool::save_to_basebind, byte for byte: phones whose label starts with '_' (and every phone with max_context <=
+ * 0) plain, the others as the full product of the context set, "label n s1 ... sn\n".  Host only. */
+aasr_status aasr_tie_basebind_text(aasr_tie *h, int32_t max_context, char **text, int64_t *len);
+aasr_status aasr_tie_write_basebind(aasr_tie *h, const char *path, int32_t max_context);
+/* PhonePool::save_model: base.mc, base.ph, base.gk in HmmSet::write_all's text formats -- one full-covariance Gaussian
+ * per tied state (mu = sum x / gamma, Sigma = sum x x^T / gamma - mu mu^T of the cluster's summed row), mixture
+ * "1 s 1", transitions 0: 0.8 and 1: 0.2. */
+aasr_status aasr_tie_write_model(aasr_tie *h, const char *base, int32_t max_context);
+/* Diagnostics.  The occupancies alone (no device), and the split loop with gains from the caller: fn is called per
+ * candidate with the cluster's classes and the new set's classes, both ascending.  out[6] of the shape: work items of
+ * the first and second hop, sides and candidates of the last batch, rounds of the last split and merge. */
+typedef double (*aasr_tie_gain_fn)(void *user, int32_t n_members, const int32_t *members, int32_t n_set, const int32_t *set);
+aasr_status aasr_debug_tie_set_occupancy(aasr_tie *h, const double *gamma);
+aasr_status aasr_debug_tie_split_given(aasr_tie *h, int32_t min_count, double sgain, int32_t max_context, aasr_tie_gain_fn fn,
+                                       void *user);
+void aasr_debug_tie_shape(const aasr_tie *h, int32_t *out);
+
+typedef struct aasr_tie_options {
+  int32_t ophn;        /* -O: the recipe's alignment field names the .phn                       */
+  int32_t hmmnet;      /* -H given: "This feature is currently broken. Fix it?", as the reference */
+  int32_t info;        /* -i                                                                    */
+  int32_t count;       /* --count (100)                                                         */
+  int32_t context;     /* --context (1)                                                         */
+  int32_t mloss_given; /* --mloss given: merge after the split                                  */
+  int32_t hops;        /* 2 (default) or 1, as aasr_tie_split                                   */
+  int32_t clusters;    /* out: tied states                                                      */
+  double sgain;        /* --sgain (0)                                                           */
+  double mloss;        /* --mloss (0)                                                           */
+  const char *rule;    /* -u                                                                    */
+  const char *speakers; /* -S, or NULL                                                          */
+  const char *out;      /* -o, or NULL                                                          */
+  const char *basebind; /* -B, or NULL: exactly one of out and basebind                         */
+  double seconds_scatter, seconds_features, seconds_split, seconds_merge; /* out */
+} aasr_tie_options;
+void aasr_tie_default_options(aasr_tie_options *opt);
+/* tie's main (aku/tie.cc:137-280) over .phn files.  Host only and in this order: -H's message; the recipe; "Specify
+ * either --out or --basebind for output"; recipe line limits (AASR_ERR_UNSUPPORTED); the rule file; a text pass over
+ * the .phn files that numbers every (label, state) ("Context phone tying requires phn files with state numbers!", here
+ * also for a line past the feature end, which the reference never reads).  Then the device: more than 63 dimensions is
+ * AASR_ERR_UNSUPPORTED before any frame is read; per line the context phone (first label, state) comes to exist and the
+ * frames start ... end - 1 go to its class through aasr_scatter_accumulate_dev; the line that meets the feature end is
+ * the file's last, with the frames it has before the end or none; the sums stay on the device for the split, the merge (with mloss_given) and the
+ * writer.  A frame that two lines of one file claim is AASR_ERR_UNSUPPORTED. */
+aasr_status aasr_run_tie_recipe(const char *feat_cfg_text, const char *recipe_path, aasr_tie_options *opt, aasr_run_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
