@@ -134,6 +134,14 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_stats_write_phs.argtypes = [cp, i32, vp, vp, vp]
     L.aasr_stats_write_lls.argtypes = [cp, d, i64]
     L.aasr_stats_create.argtypes = [vp, vp, pvp]
+    L.aasr_stats_create_full.argtypes = [vp, vp, pvp]
+    L.aasr_stats_mode.argtypes = [vp]
+    L.aasr_stats_mode.restype = i32
+    L.aasr_stats_full_moments.argtypes = [vp, vp]
+    L.aasr_stats_write_gks_full.argtypes = [cp, i32, i32, vp, vp, vp, vp, vp]
+    L.aasr_debug_stats_full_shape.argtypes = [vp, C.POINTER(i32)]
+    L.aasr_debug_stats_full_shape.restype = None
+    L.aasr_debug_stats_set_slab_bytes.argtypes = [vp, i64]
     L.aasr_stats_destroy.argtypes = [vp]
     L.aasr_stats_destroy.restype = None
     L.aasr_stats_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp]
@@ -1167,7 +1175,7 @@ class StatsOptions(C.Structure):
     """aasr_stats_options: stats' options (aku/stats.cc:321-356) for --ml over .phn files."""
     _fields_ = [("transitions", C.c_int32), ("ophn", C.c_int32), ("no_train", C.c_int32), ("uttadap", C.c_int32),
                 ("info", C.c_int32), ("num_batches", C.c_int32), ("batch_index", C.c_int32),
-                ("speakers", C.c_void_p), ("out", C.c_char_p)]
+                ("speakers", C.c_void_p), ("out", C.c_char_p), ("full_stats", C.c_int32)]
 
     @classmethod
     def defaults(cls, **kw) -> "StatsOptions":
@@ -1206,6 +1214,17 @@ def stats_write_gks(path: str, feacount, gamma, aux_gamma, sum_x, sum_xx, mode: 
     check(lib().aasr_stats_write_gks(path.encode(), G, D, mode, _ptr(fc), _ptr(g), _ptr(a), _ptr(sx), _ptr(sxx)))
 
 
+def stats_write_gks_full(path: str, feacount, gamma, aux_gamma, sum_x, sum_xx_packed) -> None:
+    """The mode-3 .gks: sum_xx_packed [G x D (D + 1) / 2], the lower triangles row by row (j <= i)."""
+    fc = np.ascontiguousarray(feacount, np.int64)
+    g, a = np.ascontiguousarray(gamma, np.float64), np.ascontiguousarray(aux_gamma, np.float64)
+    sx, sxx = np.ascontiguousarray(sum_x, np.float64), np.ascontiguousarray(sum_xx_packed, np.float64)
+    G, D = sx.shape
+    if sxx.shape != (G, D * (D + 1) // 2):
+        raise ValueError("sum_xx_packed must be [%d x %d]" % (G, D * (D + 1) // 2))
+    check(lib().aasr_stats_write_gks_full(path.encode(), G, D, _ptr(fc), _ptr(g), _ptr(a), _ptr(sx), _ptr(sxx)))
+
+
 def stats_write_mcs(path: str, mix_off, mix_idx, count, gamma, aux_gamma, mixture_ll, mode: int = 1) -> None:
     off, idx = np.ascontiguousarray(mix_off, np.int32), np.ascontiguousarray(mix_idx, np.int32)
     cnt, g = np.ascontiguousarray(count, np.int64), np.ascontiguousarray(gamma, np.float64)
@@ -1227,11 +1246,14 @@ def stats_write_lls(path: str, loglik: float, frames: int) -> None:
 class Stats:
     """Owner of an aasr_stats handle: ML statistics of one model and topology, accumulated on the device."""
 
-    def __init__(self, gmm: "Gmm", topo: Topology, n_components: int = 0):
-        """n_components: the model's mixture components in all (for the per-component gammas of fetch)"""
+    def __init__(self, gmm: "Gmm", topo: Topology, n_components: int = 0, full: bool = False):
+        """n_components: the model's mixture components in all (for the per-component gammas of fetch); full: collect
+        the full second moments as well (mode-3 dumps)"""
         h = C.c_void_p()
-        check(lib().aasr_stats_create(gmm._h, topo.handle, C.byref(h)))
+        L = lib()
+        check((L.aasr_stats_create_full if full else L.aasr_stats_create)(gmm._h, topo.handle, C.byref(h)))
         self._h = h.value
+        self.full = bool(full)
         self.G, self.D, self.S, self.K = gmm.num_gaussians, gmm.dim, gmm.num_states, n_components
 
     def close(self) -> None:
@@ -1263,6 +1285,20 @@ class Stats:
         return {"dimp": int(out[0]), "block": int(out[1]), "lds_recs": int(out[2]), "max_comps": int(out[3]),
                 "items": int(out[4])}
 
+    def mode(self) -> int:
+        return int(lib().aasr_stats_mode(self._h))
+
+    def full_launch_shape(self) -> dict:
+        """Diagnostic: the full pass of the last accumulate_dev call that reached it (zeros before, and on a plain
+        handle): PB, work items, launches and units (item x component)."""
+        out = (C.c_int32 * 4)()
+        lib().aasr_debug_stats_full_shape(self._h, out)
+        return {"pb": int(out[0]), "items": int(out[1]), "launches": int(out[2]), "units": int(out[3])}
+
+    def set_slab_bytes(self, nbytes: int) -> None:
+        """Diagnostic: the bound on a launch's slab memory in the full pass (the result does not depend on it)."""
+        check(lib().aasr_debug_stats_set_slab_bytes(self._h, int(nbytes)))
+
     def add_transitions(self, transition) -> None:
         t = np.ascontiguousarray(transition, np.int32)
         check(lib().aasr_stats_add_transitions(self._h, _ptr(t), len(t)))
@@ -1279,8 +1315,12 @@ class Stats:
         check(L.aasr_stats_gaussians(self._h, _ptr(fc), _ptr(g), _ptr(a), _ptr(sx), _ptr(sxx)))
         cnt, mll, mg = np.zeros(S, np.int64), np.zeros(S), np.zeros(max(1, self.K))
         check(L.aasr_stats_mixtures(self._h, _ptr(cnt), _ptr(mg), _ptr(mll)))
-        return {"feacount": fc, "gamma": g, "aux_gamma": a, "sum_x": sx, "sum_xx": sxx, "count": cnt,
-                "mixture_ll": mll, "mix_gamma": mg[:self.K]}
+        out = {"feacount": fc, "gamma": g, "aux_gamma": a, "sum_x": sx, "sum_xx": sxx, "count": cnt,
+               "mixture_ll": mll, "mix_gamma": mg[:self.K]}
+        if self.full:   # the packed lower triangles of sum gamma x x^T, row-major with j <= i
+            out["sum_xx_full"] = np.zeros((G, D * (D + 1) // 2))
+            check(L.aasr_stats_full_moments(self._h, _ptr(out["sum_xx_full"])))
+        return out
 
     def transitions(self):
         n = lib().aasr_stats_num_transitions(self._h)

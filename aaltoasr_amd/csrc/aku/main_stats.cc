@@ -2,9 +2,11 @@
 // the engine: features per utterance on the device, .phn segmentations on the host, the accumulation
 // for many utterances per launch (aasr_run_stats_recipe), dumps as HmmSet::dump_statistics writes them.
 //
-//   stats (-b BASE | -g GK -m MC -p PH) -c CFG -r RECIPE -o OUT --ml [-t] [-O] [-S SPKC [-U]] [-n]
+//   stats (-b BASE | -g GK -m MC -p PH) -c CFG -r RECIPE -o OUT --ml [--full-stats] [-t] [-O] [-S SPKC [-U]] [-n]
 //         [-B n -I k] [-i level] [-F f -W f -A f]
 //
+// --full-stats (an extension of this tool, like --device) collects the full second moments sum gamma x x^T and writes
+// mode-3 dumps, what estimate --mllt reads; pools of more than 127 dimensions are refused with it.
 // Only --ml over .phn files is built: -H (hmmnets), --mmi / --mpe / --grad, --mllt, -P, --savelat,
 // -a and --nseggk / --nsegmc are refused before the device is opened, and so are full-covariance or
 // subspace pools and speaker files with model transforms.
@@ -20,7 +22,7 @@
 
 int main(int argc, char *argv[]) {
   aku::conf::Config config;
-  config("usage: stats [OPTION...]\n")
+  config("usage: stats [OPTION...] --ml [--full-stats]\n")
     ('h', "help", "", "", "display help")
     ('b', "base=BASENAME", "arg", "", "base filename for model files")
     ('g', "gk=FILE", "arg", "", "Mixture base distributions")
@@ -56,7 +58,8 @@ int main(int argc, char *argv[]) {
     ('B', "batch=INT", "arg", "0", "number of batch processes with the same recipe")
     ('I', "bindex=INT", "arg", "0", "batch process index")
     ('i', "info=INT", "arg", "0", "info level")
-    ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)");
+    ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)")
+    ('\0', "full-stats", "", "", "collect full second moments (mode-3 dumps, what estimate --mllt reads)");
   config.default_parse(argc, argv);
 
   // what this build does not do, refused before anything is read
@@ -78,6 +81,14 @@ int main(int argc, char *argv[]) {
   if (config["batch"].specified ^ config["bindex"].specified) die("Must give both --batch and --bindex");
   if (!config["ml"].specified) die("At least one mode (--ml, --mmi, --mpe) must be given!");
   check_pool(gk, "stats");
+  if (config["full-stats"].specified) {  // the full-statistics kernel's limit, known from the pool's header
+    std::ifstream in(gk);
+    int size = 0, dim = 0;
+    in >> size >> dim;
+    if (in && dim > 127)
+      die("stats: --full-stats collects full second moments for at most 127 dimensions (" + gk + " has " +
+          std::to_string(dim) + ")");
+  }
   if (config["speakers"].specified) check_speakers(config["speakers"].get_str(), "stats");
   check_recipe_line_limits(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int(), false,
                            "stats");
@@ -106,6 +117,7 @@ int main(int argc, char *argv[]) {
   opt.info = config["info"].get_int();
   opt.num_batches = config["batch"].get_int();
   opt.batch_index = config["bindex"].get_int();
+  opt.full_stats = config["full-stats"].specified;
   const std::string out = config["out"].get_str();
   opt.out = out.c_str();
   aasr_spkc *spk = nullptr;

@@ -1,7 +1,8 @@
 // stats.cc -- ML statistics collection (aku/stats.cc with --ml over .phn segmentations): the statistics
 // handle that drives the device accumulation (stats_accum.hip), the dump writers of
 // HmmSet::dump_statistics and the stats main loop over a recipe (aasr_run_stats_recipe,
-// stats.cc:73-170, 540-620, 740-795).  The segmentation reader is recipe_pass.cc's.
+// stats.cc:73-170, 540-620, 740-795).  The segmentation reader is recipe_pass.cc's.  A handle made by
+// aasr_stats_create_full also collects the full second moments (stats_full_accum.hip) and dumps mode 3.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include "gmm.h"
 #include "recipe_pass.h"
 #include "stats.h"
+#include "stats_full.h"
 
 using namespace aasr;
 
@@ -48,6 +50,21 @@ struct aasr_stats {
   // host copies after aasr_stats_fetch
   bool fetched = false;
   std::vector<double> h_racc, h_pacc, h_gacc;
+  // full second moments (aasr_stats_create_full): per pool Gaussian the tiles of sum gamma xi xi^T (stats_full.h)
+  bool full = false;
+  int64_t TS = 0;  // doubles of a Gaussian's accumulator and of a unit's slab
+  int64_t full_slab_bytes = STATS_FULL_SLAB_BYTES;
+  DevBuf<double> facc, fslab, fgam, fpacked;
+  DevBuf<FullItem> d_fitems;
+  DevBuf<FullUnit> d_funits;
+  DevBuf<FullGroup> d_fgroups;
+  DevBuf<int32_t> d_fentries;
+  std::vector<FullItem> h_fitems;
+  std::vector<FullUnit> h_funits;
+  std::vector<FullGroup> h_fgroups;
+  std::vector<int32_t> h_fentries;
+  int32_t full_shape[4] = {0, 0, 0, 0};  // PB, work items, launches, units of the last call (aasr_debug_stats_full_shape)
+  std::vector<double> h_full;            // after a fetch: [G x dim (dim + 1) / 2]
   ~aasr_stats() {
     if (staged) (void)hipEventDestroy(staged);
   }
@@ -76,15 +93,113 @@ static void stats_launch_shape(int max_comps, int rec, int32_t *block, int32_t *
   *lds_recs = (size_t)(b * (max_comps + 2) + max_comps * rec) * 8 + (size_t)b * 8 <= 64 * 1024 ? 1 : 0;
 }
 
+// The full second moments of a call whose row list (grouped by pdf, cnt[s] the first entry of pdf s) is on its way to
+// h->d_rows: items of at most SCATTER_ITEM rows, a unit per (item, component), launches of whole items within the
+// slab bound, and per launch the units of every pool Gaussian in unit order (stats_full.h).
+struct FullLaunch {
+  int item0, n_items, unit0, n_units, group0, n_groups;
+};
+
+// Host side and device buffers of the pass: everything that can fail for want of memory, done before the call's
+// mode-1 kernels are queued, so that an error leaves both accumulators where they were.
+static std::vector<FullLaunch> stats_full_prepare(aasr_stats *h, const std::vector<int64_t> &cnt) {
+  h->h_fitems.clear();
+  h->h_funits.clear();
+  h->h_fgroups.clear();
+  h->h_fentries.clear();
+  const int64_t max_units = std::max<int64_t>(
+      1, std::min<int64_t>(SCATTER_MAX_ITEMS, h->full_slab_bytes / (h->TS * (int64_t)sizeof(double))));
+  typedef FullLaunch Launch;
+  std::vector<Launch> launches;
+  int64_t gam = 0, max_gam = 0, most_units = 0;
+  for (int s = 0; s < h->S; s++) {
+    const int M = h->mix_off[(size_t)s + 1] - h->mix_off[(size_t)s];
+    if (M == 0) continue;  // (nothing to weigh the frames with)
+    for (int64_t b = cnt[(size_t)s]; b < cnt[(size_t)s + 1]; b += SCATTER_ITEM) {
+      const int32_t len = (int32_t)std::min<int64_t>(SCATTER_ITEM, cnt[(size_t)s + 1] - b);
+      if (launches.empty() || launches.back().n_units + M > max_units) {
+        launches.push_back(Launch{(int)h->h_fitems.size(), 0, (int)h->h_funits.size(), 0, 0, 0});
+        gam = 0;
+      }
+      Launch &L = launches.back();
+      for (int k = 0; k < M; k++) h->h_funits.push_back(FullUnit{(int32_t)h->h_fitems.size(), k});
+      h->h_fitems.push_back(FullItem{(int32_t)b, len, s, 0, gam});
+      gam += (int64_t)M * len;
+      max_gam = std::max(max_gam, gam);
+      L.n_items++;
+      L.n_units += M;
+      most_units = std::max<int64_t>(most_units, L.n_units);
+    }
+  }
+  h->full_shape[0] = scatter_pb(h->D);
+  h->full_shape[1] = (int32_t)h->h_fitems.size();
+  h->full_shape[2] = (int32_t)launches.size();
+  h->full_shape[3] = (int32_t)h->h_funits.size();
+  if (launches.empty()) return launches;
+  // per launch: its units sorted by pool Gaussian, unit order kept within a Gaussian
+  std::vector<std::pair<int32_t, int32_t>> order;
+  for (Launch &L : launches) {
+    order.clear();
+    for (int u = 0; u < L.n_units; u++) {
+      const FullUnit &fu = h->h_funits[(size_t)(L.unit0 + u)];
+      order.emplace_back(h->mix_idx[(size_t)(h->mix_off[(size_t)h->h_fitems[(size_t)fu.item].pdf] + fu.comp)], u);
+    }
+    std::sort(order.begin(), order.end());  // (pairs: by Gaussian, then by unit)
+    L.group0 = (int)h->h_fgroups.size();
+    for (const auto &o : order) {
+      if (L.n_groups > 0 && h->h_fgroups.back().g == o.first) h->h_fgroups.back().count++;
+      else {
+        h->h_fgroups.push_back(FullGroup{o.first, (int32_t)h->h_fentries.size(), 1, 0});
+        L.n_groups++;
+      }
+      h->h_fentries.push_back(o.second);
+    }
+  }
+  h->d_fitems.ensure(h->h_fitems.size());
+  h->d_funits.ensure(h->h_funits.size());
+  h->d_fgroups.ensure(h->h_fgroups.size());
+  h->d_fentries.ensure(h->h_fentries.size());
+  h->fslab.ensure((size_t)most_units * h->TS);
+  h->fgam.ensure((size_t)max_gam);
+  return launches;
+}
+
+// the uploads and the launches of a prepared pass, after the mode-1 kernels on the same stream
+static void stats_full_pass(aasr_stats *h, const double *d_frames, const std::vector<FullLaunch> &launches, hipStream_t st) {
+  if (launches.empty()) return;
+  AASR_HIP(hipMemcpyAsync(h->d_fitems.p, h->h_fitems.data(), h->h_fitems.size() * sizeof(FullItem), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipMemcpyAsync(h->d_funits.p, h->h_funits.data(), h->h_funits.size() * sizeof(FullUnit), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipMemcpyAsync(h->d_fgroups.p, h->h_fgroups.data(), h->h_fgroups.size() * sizeof(FullGroup), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipMemcpyAsync(h->d_fentries.p, h->h_fentries.data(), h->h_fentries.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipEventRecord(h->staged, st));  // (now after these uploads as well)
+  FullParams p{};
+  p.x = d_frames;
+  p.dim = h->D;
+  p.rows = h->d_rows.p;
+  p.items = h->d_fitems.p;
+  p.units = h->d_funits.p;
+  p.recs = h->gmm->f64_recs.p;
+  p.rec = h->rec;
+  p.state_off = h->gmm->f64_state_off.p;
+  p.gam = h->fgam.p;
+  p.slab = h->fslab.p;
+  for (const FullLaunch &L : launches)  // (the launches of a call follow each other on the stream and share the buffers)
+    stats_full_launch(p, L.item0, L.n_items, L.unit0, L.n_units, h->d_fgroups.p + L.group0, L.n_groups, h->d_fentries.p,
+                      h->facc.p, st);
+}
+
 }  // namespace aasr
 
 extern "C" {
 
-aasr_status aasr_stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats **out) {
+static aasr_status stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats **out, bool full) {
   return guarded([&] {
-    if (!gmm || !topo || !out) raise(AASR_ERR_INVALID, "aasr_stats_create: null argument");
+    if (!gmm || !topo || !out) raise(AASR_ERR_INVALID, "%s: null argument", full ? "aasr_stats_create_full" : "aasr_stats_create");
     *out = nullptr;
     check_stats_model(gmm);
+    if (full && gmm->host.dim > SCATTER_MAX_DIM)  // (before the device is asked for anything)
+      raise(AASR_ERR_UNSUPPORTED, "stats: full statistics are collected for at most %d dimensions, the model has %d",
+            SCATTER_MAX_DIM, gmm->host.dim);
     {
       const aasr_status st = aasr_topo_validate(topo, gmm);
       if (st != AASR_OK) raise(st, "%s", last_error().c_str());
@@ -134,10 +249,26 @@ aasr_status aasr_stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats *
     h->g_off.upload(goff.data(), goff.size());
     h->g_rec.upload(grec.data(), grec.size());
     h->rec_pdf.upload(rpdf.data(), rpdf.size());
+    if (full) {
+      h->full = true;
+      h->TS = scatter_class_doubles(h->D);
+      h->facc.alloc((size_t)std::max(1, h->G) * h->TS);
+      AASR_HIP(hipMemset(h->facc.p, 0, h->facc.n * sizeof(double)));
+    }
     AASR_HIP(hipEventCreateWithFlags(&h->staged, hipEventDisableTiming));
     *out = h.release();
   });
 }
+
+aasr_status aasr_stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats **out) {
+  return stats_create(gmm, topo, out, false);
+}
+
+aasr_status aasr_stats_create_full(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats **out) {
+  return stats_create(gmm, topo, out, true);
+}
+
+int32_t aasr_stats_mode(const aasr_stats *h) { return h ? (h->full ? 3 : 1) : -1; }
 
 void aasr_stats_destroy(aasr_stats *h) { delete h; }
 
@@ -197,6 +328,8 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
       h->h_item_begin.push_back((int32_t)h->h_items.size());
     }
     if (h->h_items.empty()) return;
+    std::vector<FullLaunch> full_launches;
+    if (h->full) full_launches = stats_full_prepare(h, cnt);
     StatsParams p{};
     p.max_comps = h->max_comps;
     p.rec = h->rec;
@@ -227,6 +360,7 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
     stats_items_launch(p, h->dimp, (int)h->h_items.size(), st);
     stats_pdf_reduce_launch(h->d_pdfs.p, h->d_item_begin.p, (int)h->h_pdfs.size(), h->d_items.p, h->slab.p,
                             h->gmm->f64_state_off.p, h->D, h->racc.p, h->pacc.p, st);
+    if (h->full) stats_full_pass(h, d_frames, full_launches, st);
     h->fetched = false;
   });
 }
@@ -254,6 +388,13 @@ aasr_status aasr_stats_fetch(aasr_stats *h, void *stream) {
     AASR_HIP(hipMemcpyAsync(h->h_racc.data(), h->racc.p, h->racc.n * sizeof(double), hipMemcpyDeviceToHost, st));
     AASR_HIP(hipMemcpyAsync(h->h_pacc.data(), h->pacc.p, h->pacc.n * sizeof(double), hipMemcpyDeviceToHost, st));
     AASR_HIP(hipMemcpyAsync(h->h_gacc.data(), h->gacc.p, h->gacc.n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (h->full) {
+      h->h_full.resize((size_t)std::max(1, h->G) * h->D * (h->D + 1) / 2);
+      h->fpacked.ensure(h->h_full.size());
+      stats_full_pack_launch(h->facc.p, h->G, h->D, h->fpacked.p, st);
+      if (h->G > 0)
+        AASR_HIP(hipMemcpyAsync(h->h_full.data(), h->fpacked.p, h->h_full.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
     AASR_HIP(hipStreamSynchronize(st));
     h->staged_pending = false;
     h->fetched = true;
@@ -280,6 +421,28 @@ aasr_status aasr_stats_gaussians(const aasr_stats *h, int64_t *feacount, double 
         if (sum_xx) sum_xx[(size_t)g * D + d] = a[3 + D + d];
       }
     }
+  });
+}
+
+aasr_status aasr_stats_full_moments(const aasr_stats *h, double *sum_xx) {
+  return guarded([&] {
+    require_fetched(h, "aasr_stats_full_moments");
+    if (!h->full) raise(AASR_ERR_INVALID, "aasr_stats_full_moments: the handle collects no full statistics (aasr_stats_create_full)");
+    if (!sum_xx) raise(AASR_ERR_INVALID, "aasr_stats_full_moments: null argument");
+    std::copy(h->h_full.begin(), h->h_full.begin() + (size_t)h->G * h->D * (h->D + 1) / 2, sum_xx);
+  });
+}
+
+void aasr_debug_stats_full_shape(const aasr_stats *h, int32_t *out) {
+  if (!out) return;
+  for (int i = 0; i < 4; i++) out[i] = h ? h->full_shape[i] : 0;
+}
+
+aasr_status aasr_debug_stats_set_slab_bytes(aasr_stats *h, int64_t bytes) {
+  return guarded([&] {
+    if (!h || bytes < 1) raise(AASR_ERR_INVALID, "aasr_debug_stats_set_slab_bytes: bad argument");
+    if (!h->full) raise(AASR_ERR_INVALID, "aasr_debug_stats_set_slab_bytes: the handle collects no full statistics");
+    h->full_slab_bytes = bytes;
   });
 }
 
@@ -335,6 +498,40 @@ aasr_status aasr_stats_write_gks(const char *path, int32_t pool_size, int32_t di
           const float t = (float)sum_xx[(size_t)g * dim + d];
           gks.write((const char *)&t, sizeof(float));
         }
+      }
+      gks.write((const char *)&end, sizeof(int));
+    }
+    if (!gks) raise(AASR_ERR_IO, "write error on %s", path);
+  });
+}
+
+// FullStatisticsAccumulator::dump_statistics (Distributions.cc:42-60) under HmmSet::dump_gk_statistics
+aasr_status aasr_stats_write_gks_full(const char *path, int32_t pool_size, int32_t dim, const int64_t *feacount,
+                                      const double *gamma, const double *aux_gamma, const double *sum_x,
+                                      const double *sum_xx_packed) {
+  return guarded([&] {
+    if (!path || pool_size < 0 || dim < 0 || (pool_size > 0 && (!feacount || !gamma || !aux_gamma || !sum_x || !sum_xx_packed)))
+      raise(AASR_ERR_INVALID, "aasr_stats_write_gks_full: bad argument");
+    std::ofstream gks(path, std::ofstream::binary);
+    if (!gks) raise(AASR_ERR_IO, "HmmSet::dump_gk_statistics(): could not open %s", path);
+    const int mode = 3;  // PDF_ML_STATS | PDF_ML_FULL_STATS
+    gks.write((const char *)&pool_size, sizeof(int));
+    gks.write((const char *)&dim, sizeof(int));
+    gks.write((const char *)&mode, sizeof(int));
+    const int zero = 0, end = -1;
+    const size_t tri = (size_t)dim * (dim + 1) / 2;
+    std::vector<float> t((size_t)dim + tri);
+    for (int g = 0; gks && g < pool_size; g++) {
+      gks.write((const char *)&g, sizeof(int));
+      if (feacount[g] > 0) {
+        gks.write((const char *)&zero, sizeof(int));
+        const int fc = (int)feacount[g];
+        gks.write((const char *)&fc, sizeof(int));
+        gks.write((const char *)&gamma[g], sizeof(double));
+        gks.write((const char *)&aux_gamma[g], sizeof(double));
+        for (int d = 0; d < dim; d++) t[(size_t)d] = (float)sum_x[(size_t)g * dim + d];
+        for (size_t e = 0; e < tri; e++) t[(size_t)dim + e] = (float)sum_xx_packed[(size_t)g * tri + e];  // row by row, j <= i
+        gks.write((const char *)t.data(), (std::streamsize)(t.size() * sizeof(float)));
       }
       gks.write((const char *)&end, sizeof(int));
     }
@@ -412,13 +609,16 @@ aasr_status aasr_stats_write(const aasr_stats *h, const char *base) {
     std::vector<int64_t> count((size_t)std::max(1, h->S));
     std::vector<double> gamma((size_t)std::max(1, h->K)), mll((size_t)std::max(1, h->S)), aux((size_t)std::max(1, h->S), 0.0);
     ok(aasr_stats_mixtures(h, count.data(), gamma.data(), mll.data()));
-    ok(aasr_stats_write_mcs((b + ".mcs").c_str(), h->S, 1, h->mix_off.data(), h->mix_idx.data(), count.data(),
+    ok(aasr_stats_write_mcs((b + ".mcs").c_str(), h->S, h->full ? 3 : 1, h->mix_off.data(), h->mix_idx.data(), count.data(),
                             gamma.data(), aux.data(), mll.data()));
     const size_t G1 = (size_t)std::max(1, h->G);
     std::vector<int64_t> fc(G1);
     std::vector<double> gg(G1), ga(G1), sx(G1 * h->D + 1), sxx(G1 * h->D + 1);
     ok(aasr_stats_gaussians(h, fc.data(), gg.data(), ga.data(), sx.data(), sxx.data()));
-    ok(aasr_stats_write_gks((b + ".gks").c_str(), h->G, h->D, 1, fc.data(), gg.data(), ga.data(), sx.data(), sxx.data()));
+    if (h->full)
+      ok(aasr_stats_write_gks_full((b + ".gks").c_str(), h->G, h->D, fc.data(), gg.data(), ga.data(), sx.data(), h->h_full.data()));
+    else
+      ok(aasr_stats_write_gks((b + ".gks").c_str(), h->G, h->D, 1, fc.data(), gg.data(), ga.data(), sx.data(), sxx.data()));
   });
 }
 
@@ -472,7 +672,7 @@ extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, con
     refuse_line_limits(infos, "stats");
     aasr_stats *h = nullptr;
     {  // (a model the accumulation kernel has no shape for keeps its AASR_ERR_UNSUPPORTED)
-      const aasr_status cs = aasr_stats_create(gmm, topo, &h);
+      const aasr_status cs = opt->full_stats && !opt->no_train ? aasr_stats_create_full(gmm, topo, &h) : aasr_stats_create(gmm, topo, &h);
       if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
     }
     std::unique_ptr<aasr_stats, void (*)(aasr_stats *)> hguard(h, aasr_stats_destroy);

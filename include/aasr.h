@@ -676,7 +676,10 @@ aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_top
  * Maximum-likelihood statistics: aku/stats.cc with --ml over state-segmented .phn files (PhnReader),
  * accumulated on the device (csrc/stats_accum.hip) and dumped as HmmSet::dump_statistics writes
  * them (.gks, .mcs, .phs) with the .lls summary, for the reference's estimate / combine_stats.
- * Diagonal pools without model-side transforms only; -H (hmmnets), MMI / MPE and MLLT are not built.
+ * Diagonal pools without model-side transforms only; -H (hmmnets) and MMI / MPE are not built.  With
+ * full statistics (aasr_stats_create_full, the tool's --full-stats) the second moment of every Gaussian is
+ * the whole matrix sum gamma x x^T (csrc/stats_full_accum.hip) and the dumps are mode 3
+ * (PDF_ML_STATS | PDF_ML_FULL_STATS): what estimate --mllt reads, what the reference's stats --mllt writes.
  *
  * Segmentation: PhnReader::next_frame (aku/PhnReader.cc:138-292) as stats configures it -- the emission
  * pdf of every frame from the first line's start on, and with `transitions` the global index of the
@@ -696,6 +699,12 @@ aasr_status aasr_stats_read_segmentation(const aasr_topo *topo, const char *path
 aasr_status aasr_stats_write_gks(const char *path, int32_t pool_size, int32_t dim, int32_t mode,
                                  const int64_t *feacount, const double *gamma, const double *aux_gamma,
                                  const double *sum_x, const double *sum_xx);
+/* The mode-3 .gks (FullStatisticsAccumulator::dump_statistics, Distributions.cc:42-60): per accumulated Gaussian the
+ * means as floats, then sum_xx_packed [pool_size x dim (dim + 1) / 2], the lower triangle row by row (j <= i), as
+ * floats.  Host only. */
+aasr_status aasr_stats_write_gks_full(const char *path, int32_t pool_size, int32_t dim, const int64_t *feacount,
+                                      const double *gamma, const double *aux_gamma, const double *sum_x,
+                                      const double *sum_xx_packed);
 aasr_status aasr_stats_write_mcs(const char *path, int32_t num_pdfs, int32_t mode, const int32_t *mix_off,
                                  const int32_t *mix_idx, const int64_t *count, const double *gamma,
                                  const double *aux_gamma, const double *mixture_ll);
@@ -708,6 +717,14 @@ aasr_status aasr_stats_write_lls(const char *path, double loglik, int64_t frames
  * its count (host).  Deterministic: no atomics, fixed summation order. */
 typedef struct aasr_stats aasr_stats;
 aasr_status aasr_stats_create(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats **out);
+/* The same handle with full statistics: every aasr_stats_accumulate_dev call also adds, on the same stream, per pool
+ * Gaussian sum gamma xi xi^T with xi = [1, x] over the frames of every mixture that holds it (on the FP64 matrix
+ * pipe; per Gaussian: pdfs ascending, work items in order, components in record order; no atomics).  Everything else
+ * behaves, byte for byte, as on a handle of aasr_stats_create.  At most 127 dimensions (AASR_ERR_UNSUPPORTED above,
+ * before anything is allocated); the accumulator takes 12 KiB per Gaussian at 39 dimensions, 72 KiB at 127. */
+aasr_status aasr_stats_create_full(aasr_gmm *gmm, const aasr_topo *topo, aasr_stats **out);
+/* the statistics mode of the handle's dumps: 1, or 3 with full statistics */
+int32_t aasr_stats_mode(const aasr_stats *h);
 void aasr_stats_destroy(aasr_stats *h);
 /* Adds n_frames double frame rows (device, [n_frames x dim]) whose pdfs are pdf[] (host; -1: skip)
  * on `stream`, no host wait.  d_frame_ll (device, n_frames doubles, or NULL) receives every frame's
@@ -723,6 +740,10 @@ aasr_status aasr_stats_fetch(aasr_stats *h, void *stream);
 aasr_status aasr_stats_gaussians(const aasr_stats *h, int64_t *feacount, double *gamma, double *aux_gamma,
                                  double *sum_x, double *sum_xx);
 aasr_status aasr_stats_mixtures(const aasr_stats *h, int64_t *count, double *gamma, double *mixture_ll);
+/* after a fetch, full handles only (AASR_ERR_INVALID on others): sum_xx [pool x dim (dim + 1) / 2], the packed lower
+ * triangles of sum gamma x x^T, row-major with j <= i (the layout of aasr_estimate_get_statistics in mode 3 and of
+ * aasr_mllt_create); zeros for a Gaussian without frames */
+aasr_status aasr_stats_full_moments(const aasr_stats *h, double *sum_xx);
 int32_t aasr_stats_num_transitions(const aasr_stats *h);
 aasr_status aasr_stats_transitions(const aasr_stats *h, int32_t *source, int32_t *target_offset, double *count);
 /* Diagnostic, read-only: the launch shape of the last aasr_stats_accumulate_dev call that reached the
@@ -730,7 +751,14 @@ aasr_status aasr_stats_transitions(const aasr_stats *h, int32_t *source, int32_t
  * 128 or 64), out[2] 1 when the mixture records were staged in LDS, out[3] the model's largest mixture,
  * out[4] work items launched.  Five zeros before the first such call. */
 void aasr_debug_stats_shape(const aasr_stats *h, int32_t *out);
-/* after a fetch: base.phs, base.mcs, base.gks */
+/* Diagnostic, read-only: the full pass of the last aasr_stats_accumulate_dev call that reached it -- out[0] PB (the
+ * blocks of 16 that dim + 1 is padded to), out[1] work items, out[2] launches, out[3] units (item x component).
+ * Four zeros before the first such call and on a handle without full statistics. */
+void aasr_debug_stats_full_shape(const aasr_stats *h, int32_t *out);
+/* Diagnostic: the bound on a launch's slab memory in the full pass (default 64 MiB; one work item at least).  The
+ * result's bytes do not depend on it.  Full handles only. */
+aasr_status aasr_debug_stats_set_slab_bytes(aasr_stats *h, int64_t bytes);
+/* after a fetch: base.phs, base.mcs, base.gks (mode 3 on a full handle) */
 aasr_status aasr_stats_write(const aasr_stats *h, const char *base);
 
 typedef struct aasr_stats_options {
@@ -743,6 +771,7 @@ typedef struct aasr_stats_options {
   int32_t batch_index;  /* -I                                                */
   struct aasr_spkc *speakers; /* -S: speaker configuration or NULL          */
   const char *out;      /* -o: base name of the output files                 */
+  int32_t full_stats;   /* --full-stats: full second moments, mode-3 dumps   */
 } aasr_stats_options;
 void aasr_stats_default_options(aasr_stats_options *opt);
 
