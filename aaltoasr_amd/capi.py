@@ -155,6 +155,22 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_stats_default_options.argtypes = [vp]
     L.aasr_stats_default_options.restype = None
     L.aasr_run_stats_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
+    L.aasr_segll_create.argtypes = [vp, pvp]
+    L.aasr_segll_destroy.argtypes = [vp]
+    L.aasr_segll_destroy.restype = None
+    L.aasr_segll_score_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.aasr_debug_segll_shape.argtypes = [vp, C.POINTER(i32)]
+    L.aasr_debug_segll_shape.restype = None
+    L.aasr_phn_read_segmentation.argtypes = [vp, cp, f, i32, i32, i32, i32, i32, C.POINTER(i32),
+                                             C.POINTER(C.POINTER(i32)), C.POINTER(C.POINTER(i32)), C.POINTER(i32)]
+    L.aasr_vtln_default_options.argtypes = [vp]
+    L.aasr_vtln_default_options.restype = None
+    L.aasr_vtln_grid.argtypes = [vp, C.POINTER(f), C.POINTER(f), C.POINTER(i32)]
+    L.aasr_vtln_grid.restype = None
+    L.aasr_vtln_summary_text.argtypes = [C.POINTER(cp), i32, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
+    L.aasr_debug_vtln_set_group_frames.argtypes = [i64]
+    L.aasr_debug_vtln_set_group_frames.restype = None
+    L.aasr_run_vtln_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
     # CMLLR estimation
     L.aasr_mllr_create.argtypes = [vp, pvp]
     L.aasr_mllr_destroy.argtypes = [vp]
@@ -1339,6 +1355,125 @@ def run_stats_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str,
     opts.out = ob
     st = RunStats()
     check(lib().aasr_run_stats_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}
+
+
+# ---- the log-likelihood of a state segmentation, VTLN estimation ---------------------------------
+
+AASR_PHN_STATE_NUM_LABELS, AASR_PHN_RELATIVE_SAMPLES = 1, 2
+
+
+class SegLL:
+    """Owner of an aasr_segll handle: per frame safe_log(likelihood) of the one pdf its segmentation gives it -- the
+    frame_ll of Stats.accumulate_dev from a kernel that sums nothing (any dimension, any mixture size)."""
+
+    def __init__(self, gmm: "Gmm"):
+        h = C.c_void_p()
+        check(lib().aasr_segll_create(gmm._h, C.byref(h)))
+        self._h = h.value
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_segll_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def score_dev(self, d_frames, pdf, d_frame_ll, stream=None) -> None:
+        """d_frames: a float64 device tensor [n x dim]; pdf: host int32 per frame (-1: skip, its entry of d_frame_ll is
+        left as it is); d_frame_ll: a float64 device tensor [n]."""
+        p = np.ascontiguousarray(pdf, np.int32)
+        check(lib().aasr_segll_score_dev(self._h, _ptr(d_frames), len(p), _ptr(p), _ptr(d_frame_ll),
+                                         _stream_handle(stream)))
+
+    def launch_shape(self) -> dict:
+        """Diagnostic: the last score_dev call that launched the kernel (zeros before the first): work items, rows per LDS
+        sub-block, a workgroup's LDS bytes, the doubles between two rows in LDS, the rows of the largest item."""
+        out = (C.c_int32 * 5)()
+        lib().aasr_debug_segll_shape(self._h, out)
+        return {"items": int(out[0]), "sub": int(out[1]), "lds_bytes": int(out[2]), "stride": int(out[3]),
+                "item_rows": int(out[4])}
+
+
+def phn_read_segmentation(topo: Topology, path: str, frame_rate: float = 125.0, first_frame: int = 0,
+                          last_frame: int = 0, eof_frame: int = -1, snl: bool = False, rsamp: bool = False,
+                          transitions: bool = False):
+    """stats_read_segmentation with PhnReader's two modes: state-number labels (snl) and sample numbers relative to the
+    start time (rsamp).  Host only."""
+    L = lib()
+    sf, n = C.c_int32(), C.c_int32()
+    pp, tp = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+    flags = (AASR_PHN_STATE_NUM_LABELS if snl else 0) | (AASR_PHN_RELATIVE_SAMPLES if rsamp else 0)
+    check(L.aasr_phn_read_segmentation(topo.handle, path.encode(), frame_rate, first_frame, last_frame, eof_frame, flags,
+                                       1 if transitions else 0, C.byref(sf), C.byref(pp), C.byref(tp), C.byref(n)))
+    try:
+        if n.value < 0:
+            return None
+        pdf = np.array([pp[k] for k in range(n.value)], np.int32)
+        tr = np.array([tp[k] for k in range(n.value)], np.int32)
+        return sf.value, pdf, tr
+    finally:
+        L.aasr_free(pp)
+        L.aasr_free(tp)
+
+
+class VtlnOptions(C.Structure):
+    """aasr_vtln_options: vtln's options (aku/vtln.cc:158-178)."""
+    _fields_ = [("ophn", C.c_int32), ("snl", C.c_int32), ("rsamp", C.c_int32), ("info", C.c_int32),
+                ("num_batches", C.c_int32), ("batch_index", C.c_int32), ("grid_size", C.c_int32),
+                ("grid_size_given", C.c_int32), ("grid_rad", C.c_float), ("grid_rad_given", C.c_int32),
+                ("relative", C.c_int32), ("module", C.c_char_p), ("speakers", C.c_void_p), ("out", C.c_char_p),
+                ("savesum", C.c_char_p)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "VtlnOptions":
+        o = cls()
+        lib().aasr_vtln_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def vtln_grid(opts: VtlnOptions):
+    """(grid_start, grid_step, grid_size) of aku/vtln.cc:214-225 as float32 / int: the warp factor of grid point i is
+    float32(centre + grid_start + i * grid_step)."""
+    a, b, n = C.c_float(), C.c_float(), C.c_int32()
+    lib().aasr_vtln_grid(C.byref(opts), C.byref(a), C.byref(b), C.byref(n))
+    return np.float32(a.value), np.float32(b.value), int(n.value)
+
+
+def vtln_summary_text(speakers, warps, logliks) -> str:
+    """save_vtln_stats: speakers [ids], warps / logliks [per speaker a sequence] -> the summary file's text"""
+    ids = [x.encode() for x in speakers]
+    arr = (C.c_char_p * max(1, len(ids)))(*ids)
+    counts = np.array([len(w) for w in warps], np.int32)
+    w = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32) for x in warps] + [np.zeros(0, np.float32)]))
+    ll = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64) for x in logliks] + [np.zeros(0)]))
+    text, n = C.c_void_p(), C.c_int64()
+    check(lib().aasr_vtln_summary_text(arr, len(ids), _ptr(counts), _ptr(w), _ptr(ll), C.byref(text), C.byref(n)))
+    try:
+        return C.string_at(text.value, n.value).decode()
+    finally:
+        lib().aasr_free(text)
+
+
+def vtln_set_group_frames(frames: int) -> None:
+    """Diagnostic: the bound on a group's frames in run_vtln_recipe (<= 0: the default)."""
+    lib().aasr_debug_vtln_set_group_frames(int(frames))
+
+
+def run_vtln_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str, speakers: "SpeakerConfig", module: str,
+                    out: Optional[str] = None, savesum: Optional[str] = None,
+                    opts: Optional[VtlnOptions] = None) -> dict:
+    opts = opts or VtlnOptions.defaults()
+    ob, sb, mb = (out.encode() if out else None), (savesum.encode() if savesum else None), module.encode()
+    opts.out, opts.savesum, opts.module, opts.speakers = ob, sb, mb, speakers._h
+    st = RunStats()
+    check(lib().aasr_run_vtln_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}
 
 

@@ -169,7 +169,8 @@ static bool phn_next_text(FILE *f, std::string *text) {
 // One transcript entry; false at the end of the file or at a timed line that starts at or after
 // last_frame (> 0).  Times are clipped to [first_frame, last_frame] as PhnReader::set_frame_limits
 // leaves them.
-bool next_phn_line(FILE *f, float samples_per_frame, int first_frame, int last_frame, int *line_no, PhnLine *phn) {
+bool next_phn_line(FILE *f, float samples_per_frame, int first_frame, int last_frame, int *line_no, PhnLine *phn,
+                   int flags) {
   std::string text;
   if (!phn_next_text(f, &text)) {
     if (ferror(f)) raise(AASR_ERR_IO, "transcript: read error on line %d", *line_no);
@@ -200,19 +201,25 @@ bool next_phn_line(FILE *f, float samples_per_frame, int first_frame, int last_f
     head = fl[0];
     if (fl.size() == 2) e.comment = fl[1];
   }
+  if ((flags & PHN_RELATIVE_SAMPLES) && e.start >= 0) {  // PhnReader.cc:360-364
+    e.start += first_frame;
+    e.end += first_frame;
+  }
   if (last_frame > 0 && e.start >= last_frame) return false;
   if (last_frame > 0 && e.end >= last_frame) e.end = last_frame;
   if (first_frame > 0 && e.start >= 0 && e.start < first_frame) e.start = first_frame;
-  e.label = head.substr(0, std::min(head.find(','), head.size()));
+  if (flags & PHN_STATE_NUM_LABELS) e.state = atoi(head.c_str());  // :383-386, a state number instead of a label
+  else e.label = head.substr(0, std::min(head.find(','), head.size()));
   *phn = e;
   (*line_no)++;
   return true;
 }
 
-void phn_skip_to_first_frame(FILE *f, float samples_per_frame, int first_frame, int last_frame, int *line_no) {
+void phn_skip_to_first_frame(FILE *f, float samples_per_frame, int first_frame, int last_frame, int *line_no, int flags) {
+  if (flags & PHN_RELATIVE_SAMPLES) return;  // PhnReader.cc:108
   PhnLine phn;
   long curpos = ftell(f), oldpos = curpos;
-  while (next_phn_line(f, samples_per_frame, first_frame, last_frame, line_no, &phn)) {
+  while (next_phn_line(f, samples_per_frame, first_frame, last_frame, line_no, &phn, flags)) {
     oldpos = curpos;
     curpos = ftell(f);
     if (phn.end < 0 || phn.end > first_frame) {

@@ -464,7 +464,8 @@ void gmm_dim_split_score(aasr_gmm *g, const float *d_frames, int64_t F, float *d
                          const unsigned long long *maskw = nullptr, int c1 = 0, const int32_t *gclus = nullptr,
                          bool frames_adapted = false);
 void gmm_build_pool_centred(aasr_gmm *g);
-void gmm_build_f64(aasr_gmm *g);
+// any_dim: also beyond the 192 dimensions of the kernels with dimension instances (records padded to whole 8s)
+void gmm_build_f64(aasr_gmm *g, bool any_dim = false);
 void gmm_cluster_score_f64_launch(aasr_gmm *g, const double *d_frames, const double *d_members, int64_t F,
                                   double *d_out, int linear, double det, hipStream_t stream);
 void gmm_f64_masked_launch(aasr_gmm *g, const double *d_members, int64_t F, double *d_out, int linear, double det,

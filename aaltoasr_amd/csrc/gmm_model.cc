@@ -444,16 +444,18 @@ void gmm_set_transforms(aasr_gmm *g, int32_t n_transforms, const int32_t *gauss_
 // mean, precision (1 / variance, 0 for a non-positive variance), the constant log sqrt(prod
 // precision) (0 when the product is not positive: the "invalid" Gaussian,
 // aku/Distributions.cc:1117-1135) and the normalised mixture weight.
-void gmm_build_f64(aasr_gmm *g) {
-  if (g->f64_built) return;
+void gmm_build_f64(aasr_gmm *g, bool any_dim) {
   const HostModel &m = g->host;
   const int D = m.dim;
+  // (asked again on records that a caller with any_dim built: the kernels with dimension instances still refuse)
+  if (D > 192 && !any_dim) raise(AASR_ERR_UNSUPPORTED, "no f64 kernel instance for dimension %d", D);
+  if (g->f64_built) return;
   // the frame vector is a per-lane array of doubles, instances up to 192 dimensions.  What the compiler makes of it in
   // k_stats_items (code object notes, tests/test_kernel_notes.py): in registers without scratch up to <128> (255 VGPRs
   // at <96>, 256 + 82 AGPRs at <128>); <192> would need 384 for the frame alone, takes all 512 (256 + 256 AGPRs) and
   // still spills 97 VGPRs, 248 bytes of scratch per lane
-  const int dimp = D <= 64 ? centred_dimp_for(D) : D <= 96 ? 96 : D <= 128 ? 128 : D <= 192 ? 192 : 0;
-  if (!dimp) raise(AASR_ERR_UNSUPPORTED, "no f64 kernel instance for dimension %d", D);
+  // beyond them (any_dim: a kernel whose loops run over the dimension from memory) the records are padded to whole 8s
+  const int dimp = D <= 64 ? centred_dimp_for(D) : D <= 96 ? 96 : D <= 128 ? 128 : D <= 192 ? 192 : (D + 7) / 8 * 8;
   const int rec = 2 * dimp + 2;
   const size_t K = m.mix_idx.size();
   std::vector<double> recs(std::max<size_t>(K, 1) * rec, 0.0);

@@ -498,22 +498,7 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
     if (have_trainer) finish_speaker();
 
     // the new speaker configuration (aku/mllr.cc:318-332)
-    if (opt->out) {
-      std::vector<const char *> sp;
-      int32_t n_sp = -1, n_ut = -1;
-      if (opt->num_batches > 1) {
-        if (opt->batch_index == 1) updated.insert("default");
-        for (const std::string &s : updated) sp.push_back(s.c_str());
-        n_sp = (int32_t)sp.size();
-        n_ut = 0;
-      }
-      char *text = nullptr;
-      int64_t len = 0;
-      if (aasr_spkc_write_text(spk, sp.data(), n_sp, nullptr, n_ut, &text, &len) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      std::unique_ptr<char, void (*)(void *)> tguard(text, free);
-      write_text_file(opt->out, text, (size_t)len);
-    }
+    if (opt->out) write_speaker_file_for_batch(spk, updated, opt->num_batches, opt->batch_index, opt->out);
     fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
   });
 }

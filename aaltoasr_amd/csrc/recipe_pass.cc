@@ -87,32 +87,42 @@ TopoTables::TopoTables(const aasr_topo *topo) {
 }
 
 Segmentation read_segmentation(const aasr_topo *topo, const TopoTables &tt, const char *path, float frame_rate,
-                               int first_frame, int last_frame, int eof_frame, bool want_transitions) {
+                               int first_frame, int last_frame, int eof_frame, bool want_transitions, int phn_flags) {
+  const bool snl = (phn_flags & PHN_STATE_NUM_LABELS) != 0;
+  if (snl && want_transitions)
+    raise(AASR_ERR_UNSUPPORTED, "PhnReader: transitions are not collected from phn files with state number labels");
   FILE *f = fopen(path, "r");
   if (!f) raise(AASR_ERR_IO, "PhnReader::open(): could not open %s", path);
   std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
   const float spf = 16000 / frame_rate;
   int line_no = 0;
-  if (first_frame > 0 || last_frame > 0) phn_skip_to_first_frame(f, spf, first_frame, last_frame, &line_no);
+  if (first_frame > 0 || last_frame > 0) phn_skip_to_first_frame(f, spf, first_frame, last_frame, &line_no, phn_flags);
   Segmentation seg;
   PhnLine cur;
-  if (!next_phn_line(f, spf, first_frame, last_frame, &line_no, &cur)) return seg;
+  if (!next_phn_line(f, spf, first_frame, last_frame, &line_no, &cur, phn_flags)) return seg;
   seg.initialized = true;
   int frame = -1;
   bool eof_flag = false;
   while (!eof_flag) {
     frame = frame == -1 ? cur.start : frame + 1;
-    if (cur.state < 0) raise(AASR_ERR_INVALID, "PhnReader::next_frame(): A state segmented phn file is required");
-    const int h = aasr_topo_hmm_index(topo, cur.label.c_str());
-    if (h < 0) raise(AASR_ERR_INVALID, "Unknown HMM in transcription: '%s' in %s", cur.label.c_str(), path);
-    const std::vector<int32_t> &states = tt.hmm_states[(size_t)h];
-    if (cur.state >= (int)states.size())
-      raise(AASR_ERR_INVALID, "%s: state %d of HMM %s does not exist", path, cur.state, cur.label.c_str());
-    const int state = states[(size_t)cur.state];
+    int state;
+    if (snl) {  // PhnReader.cc:164-167: the number is the state's index (the reference does not look whether it exists)
+      state = cur.state;
+      if (state < 0 || state >= (int)tt.offsets.size())
+        raise(AASR_ERR_INVALID, "%s: state %d does not exist", path, state);
+    } else {
+      if (cur.state < 0) raise(AASR_ERR_INVALID, "PhnReader::next_frame(): A state segmented phn file is required");
+      const int h = aasr_topo_hmm_index(topo, cur.label.c_str());
+      if (h < 0) raise(AASR_ERR_INVALID, "Unknown HMM in transcription: '%s' in %s", cur.label.c_str(), path);
+      const std::vector<int32_t> &states = tt.hmm_states[(size_t)h];
+      if (cur.state >= (int)states.size())
+        raise(AASR_ERR_INVALID, "%s: state %d of HMM %s does not exist", path, cur.state, cur.label.c_str());
+      state = states[(size_t)cur.state];
+    }
     bool new_phn_loaded = false;
     const PhnLine prev = cur;
     while (frame + 1 >= cur.end) {
-      if (!next_phn_line(f, spf, first_frame, last_frame, &line_no, &cur)) {
+      if (!next_phn_line(f, spf, first_frame, last_frame, &line_no, &cur, phn_flags)) {
         eof_flag = true;
         break;
       }
@@ -223,6 +233,24 @@ int64_t GroupStager::stage(const std::vector<std::vector<int16_t>> &audio, const
     row += n;
   }
   return rows_total;
+}
+
+void write_speaker_file_for_batch(aasr_spkc *speakers, std::set<std::string> seen, int num_batches, int batch_index,
+                                  const char *path) {
+  std::vector<const char *> sp;
+  int32_t n_sp = -1, n_ut = -1;
+  if (num_batches > 1) {
+    if (batch_index == 1) seen.insert("default");
+    for (const std::string &s : seen) sp.push_back(s.c_str());
+    n_sp = (int32_t)sp.size();
+    n_ut = 0;
+  }
+  char *text = nullptr;
+  int64_t len = 0;
+  if (aasr_spkc_write_text(speakers, sp.data(), n_sp, nullptr, n_ut, &text, &len) != AASR_OK)
+    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  std::unique_ptr<char, void (*)(void *)> tguard(text, free);
+  write_text_file(path, text, (size_t)len);
 }
 
 void fill_run_stats(aasr_run_stats *stats, int64_t utterances, int64_t frames,

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -48,11 +49,13 @@ struct Segmentation {
   std::vector<int32_t> tr;   // per frame: global transition index, -1: none; empty unless transitions were asked for
 };
 
-// PhnReader::next_frame (aku/PhnReader.cc:138-292) with state_num_labels = false and relative_sample_numbers = false,
-// driven as stats.cc:simple_train drives it: frames until the reader's end, the frame loop leaving at eof_frame
-// (< 0: no limit) after next_frame has run for it.
+// PhnReader::next_frame (aku/PhnReader.cc:138-292), driven as stats.cc:simple_train drives it: frames until the
+// reader's end, the frame loop leaving at eof_frame (< 0: no limit) after next_frame has run for it.  phn_flags: the
+// reader's state_num_labels and relative_sample_numbers (phn_line.h), neither by default.  With state-number labels
+// the line's number is the state (and pdf) index itself; transitions are refused with them (the reader's "first out
+// transition" guess, PhnReader.cc:234-243, is not built).
 Segmentation read_segmentation(const aasr_topo *topo, const TopoTables &tt, const char *path, float frame_rate,
-                               int first_frame, int last_frame, int eof_frame, bool want_transitions);
+                               int first_frame, int last_frame, int eof_frame, bool want_transitions, int phn_flags = 0);
 // The state sequence of a recipe line as mllr and lda take it (aku/mllr.cc:111-115, lda.cc:212-218): the line's frame
 // range, no transitions; a segmentation that cannot be initialised is reported on stderr and has no frames.
 Segmentation read_state_sequence(const aasr_topo *topo, const TopoTables &tt, const RecipeInfo &info, bool ophn,
@@ -78,6 +81,11 @@ struct GroupStager {
   int64_t stage(const std::vector<std::vector<int16_t>> &audio, const std::vector<int32_t> &start,
                 const std::vector<int32_t> &rows, const std::function<void(size_t)> &before_utterance);
 };
+
+// The speaker file an adaptation tool writes (aku/mllr.cc:318-332, vtln.cc:269-286): every entry of the configuration,
+// or with batches (num_batches > 1) the speakers the batch has seen, "default" from batch 1 only, and no utterances.
+void write_speaker_file_for_batch(aasr_spkc *speakers, std::set<std::string> seen, int num_batches, int batch_index,
+                                  const char *path);
 
 void fill_run_stats(aasr_run_stats *stats, int64_t utterances, int64_t frames,
                     std::chrono::steady_clock::time_point t0, double seconds_device);

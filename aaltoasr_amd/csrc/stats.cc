@@ -72,13 +72,28 @@ struct aasr_stats {
 
 namespace aasr {
 
-static void check_stats_model(const aasr_gmm *g) {
+void rows_by_pdf(const char *what, int S, const int32_t *pdf, int64_t n_frames, std::vector<int64_t> *cnt_out,
+                 std::vector<int32_t> *rows) {
+  std::vector<int64_t> &cnt = *cnt_out;
+  cnt.assign((size_t)S + 1, 0);
+  for (int64_t f = 0; f < n_frames; f++) {
+    if (pdf[f] >= S) raise(AASR_ERR_INVALID, "%s: pdf %d of frame %ld out of range", what, pdf[f], (long)f);
+    if (pdf[f] >= 0) cnt[(size_t)pdf[f] + 1]++;
+  }
+  for (int s = 0; s < S; s++) cnt[(size_t)s + 1] += cnt[(size_t)s];
+  rows->resize((size_t)std::max<int64_t>(1, cnt[(size_t)S]));
+  std::vector<int64_t> fill(cnt.begin(), cnt.end() - 1);
+  for (int64_t f = 0; f < n_frames; f++)
+    if (pdf[f] >= 0) (*rows)[(size_t)fill[(size_t)pdf[f]]++] = (int32_t)f;
+}
+
+void check_stats_model(const aasr_gmm *g, const char *tool) {
   if (g->host.any_full())
-    raise(AASR_ERR_UNSUPPORTED, "stats: full-covariance and subspace Gaussians are not supported (diagonal pools only)");
+    raise(AASR_ERR_UNSUPPORTED, "%s: full-covariance and subspace Gaussians are not supported (diagonal pools only)", tool);
   if (!g->host.gauss_bias.empty())
-    raise(AASR_ERR_UNSUPPORTED, "stats: subspace Gaussians are not supported (diagonal pools only)");
+    raise(AASR_ERR_UNSUPPORTED, "%s: subspace Gaussians are not supported (diagonal pools only)", tool);
   if (g->host.n_transforms > 0)
-    raise(AASR_ERR_UNSUPPORTED, "stats: model-side transforms (cmllr) are not supported");
+    raise(AASR_ERR_UNSUPPORTED, "%s: model-side transforms (cmllr) are not supported", tool);
 }
 
 // The item kernel's shape for a model whose largest mixture has max_comps components of rec doubles a record.
@@ -294,18 +309,8 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
     if (h->staged_pending) AASR_HIP(hipEventSynchronize(h->staged));
     h->staged_pending = false;
     // frames grouped by pdf (frame order within a pdf), cut into items of at most STATS_CHUNK frames
-    std::vector<int64_t> cnt((size_t)h->S + 1, 0);
-    for (int64_t f = 0; f < n_frames; f++) {
-      if (pdf[f] >= h->S) raise(AASR_ERR_INVALID, "aasr_stats_accumulate_dev: pdf %d of frame %ld out of range", pdf[f], (long)f);
-      if (pdf[f] >= 0) cnt[(size_t)pdf[f] + 1]++;
-    }
-    for (int s = 0; s < h->S; s++) cnt[(size_t)s + 1] += cnt[(size_t)s];
-    h->h_rows.resize((size_t)std::max<int64_t>(1, cnt[(size_t)h->S]));
-    {
-      std::vector<int64_t> fill(cnt.begin(), cnt.end() - 1);
-      for (int64_t f = 0; f < n_frames; f++)
-        if (pdf[f] >= 0) h->h_rows[(size_t)fill[(size_t)pdf[f]]++] = (int32_t)f;
-    }
+    std::vector<int64_t> cnt;
+    rows_by_pdf("aasr_stats_accumulate_dev", h->S, pdf, n_frames, &cnt, &h->h_rows);
     h->h_items.clear();
     h->h_pdfs.clear();
     h->h_item_begin.assign(1, 0);
@@ -624,16 +629,17 @@ aasr_status aasr_stats_write(const aasr_stats *h, const char *base) {
 
 // ---- host-only segmentation reader ---------------------------------------------------------------
 
-aasr_status aasr_stats_read_segmentation(const aasr_topo *topo, const char *path, float frame_rate, int32_t first_frame,
-                                         int32_t last_frame, int32_t eof_frame, int32_t transitions,
-                                         int32_t *start_frame, int32_t **pdf, int32_t **transition, int32_t *n_frames) {
+static aasr_status read_segmentation_call(const char *what, const aasr_topo *topo, const char *path, float frame_rate,
+                                          int32_t first_frame, int32_t last_frame, int32_t eof_frame, int32_t flags,
+                                          int32_t transitions, int32_t *start_frame, int32_t **pdf, int32_t **transition,
+                                          int32_t *n_frames) {
   return guarded([&] {
-    if (!topo || !path || !start_frame || !pdf || !transition || !n_frames)
-      raise(AASR_ERR_INVALID, "aasr_stats_read_segmentation: null argument");
+    if (!topo || !path || !start_frame || !pdf || !transition || !n_frames) raise(AASR_ERR_INVALID, "%s: null argument", what);
     *pdf = nullptr;
     *transition = nullptr;
+    if (flags & ~(AASR_PHN_STATE_NUM_LABELS | AASR_PHN_RELATIVE_SAMPLES)) raise(AASR_ERR_INVALID, "%s: unknown flags %d", what, flags);
     TopoTables tt(topo);
-    Segmentation seg = read_segmentation(topo, tt, path, frame_rate, first_frame, last_frame, eof_frame, transitions != 0);
+    Segmentation seg = read_segmentation(topo, tt, path, frame_rate, first_frame, last_frame, eof_frame, transitions != 0, flags);
     const size_t n = seg.pdf.size();
     *pdf = (int32_t *)malloc(std::max<size_t>(1, n) * sizeof(int32_t));
     *transition = (int32_t *)malloc(std::max<size_t>(1, n) * sizeof(int32_t));
@@ -649,6 +655,20 @@ aasr_status aasr_stats_read_segmentation(const aasr_topo *topo, const char *path
     *start_frame = seg.start_frame;
     *n_frames = seg.initialized ? (int32_t)n : -1;
   });
+}
+
+aasr_status aasr_stats_read_segmentation(const aasr_topo *topo, const char *path, float frame_rate, int32_t first_frame,
+                                         int32_t last_frame, int32_t eof_frame, int32_t transitions,
+                                         int32_t *start_frame, int32_t **pdf, int32_t **transition, int32_t *n_frames) {
+  return read_segmentation_call("aasr_stats_read_segmentation", topo, path, frame_rate, first_frame, last_frame, eof_frame, 0,
+                                transitions, start_frame, pdf, transition, n_frames);
+}
+
+aasr_status aasr_phn_read_segmentation(const aasr_topo *topo, const char *path, float frame_rate, int32_t first_frame,
+                                       int32_t last_frame, int32_t eof_frame, int32_t flags, int32_t transitions,
+                                       int32_t *start_frame, int32_t **pdf, int32_t **transition, int32_t *n_frames) {
+  return read_segmentation_call("aasr_phn_read_segmentation", topo, path, frame_rate, first_frame, last_frame, eof_frame,
+                                flags, transitions, start_frame, pdf, transition, n_frames);
 }
 
 void aasr_stats_default_options(aasr_stats_options *o) {

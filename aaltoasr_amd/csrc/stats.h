@@ -11,6 +11,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
+
+struct aasr_gmm;
 
 namespace aasr {
 
@@ -37,6 +40,16 @@ struct StatsParams {
   int32_t lds_recs;          // 1: the mixture's records are staged in LDS
   int32_t max_comps;         // largest mixture of the launch
 };
+
+// Host: the row list of a call, shared by the handles that take frames with a pdf each (stats.cc, seg_loglik.cc).
+// rows: the frames with a pdf >= 0 grouped by pdf, frame order within a pdf; cnt[s] the first entry of pdf s
+// (S + 1 entries).  A pdf >= S raises "<what>: pdf %d of frame %ld out of range" (AASR_ERR_INVALID) before anything
+// is written; frames with a negative pdf are left out.
+void rows_by_pdf(const char *what, int S, const int32_t *pdf, int64_t n_frames, std::vector<int64_t> *cnt,
+                 std::vector<int32_t> *rows);
+// Host: the models these handles refuse (AASR_ERR_UNSUPPORTED, "<tool>: ..."): full-covariance and subspace
+// Gaussians, model-side transforms.  Asks the device for nothing.
+void check_stats_model(const aasr_gmm *g, const char *tool = "stats");
 
 // per-item partial sums (one workgroup per item)
 void stats_items_launch(const StatsParams &p, int dimp, int n_items, hipStream_t stream);

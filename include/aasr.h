@@ -783,6 +783,79 @@ aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_top
                                   aasr_run_stats *stats);
 
 /* ---------------------------------------------------------------------------
+ * The log-likelihood of a state segmentation, per frame: what aku/vtln.cc:99-114 asks of the model for every frame,
+ * safe_log(Mixture::compute_likelihood(frame)) of the one pdf the segmentation gives it -- the d_frame_ll of
+ * aasr_stats_accumulate_dev, byte for byte, from a kernel of its own (csrc/seg_loglik.hip) that sums nothing: any
+ * dimension and any mixture size.  Refused at create with AASR_ERR_UNSUPPORTED, before the device is asked for
+ * anything: full-covariance Gaussians, subspace Gaussians, model-side transforms.  Deterministic: no atomics. */
+typedef struct aasr_segll aasr_segll;
+aasr_status aasr_segll_create(aasr_gmm *gmm, aasr_segll **out);
+void aasr_segll_destroy(aasr_segll *h);
+/* n_frames double frame rows (device, [n_frames x dim]) whose pdfs are pdf[] (host) -> d_frame_ll (device, n_frames
+ * doubles) on `stream`, no host wait.  A frame with pdf -1 (any negative pdf) is skipped: its entry of d_frame_ll is
+ * not written.  A pdf >= the number of states is AASR_ERR_INVALID and nothing is queued.  Calls on one handle go to
+ * one stream. */
+aasr_status aasr_segll_score_dev(aasr_segll *h, const double *d_frames, int64_t n_frames,
+                                 const int32_t *pdf, double *d_frame_ll, void *stream);
+/* Diagnostic, read-only: the last aasr_segll_score_dev call that launched the kernel -- out[0] work items (one pdf,
+ * at most 256 rows each), out[1] rows per LDS sub-block (no more than the largest item has), out[2] LDS bytes of a
+ * workgroup (at most 65536), out[3] doubles between two rows in LDS, out[4] rows of the largest item.  Five zeros
+ * before the first such call. */
+void aasr_debug_segll_shape(const aasr_segll *h, int32_t *out);
+
+/* PhnReader::next_frame (aku/PhnReader.cc:138-292) with the reader's two modes: aasr_stats_read_segmentation with
+ * `flags`, a sum of
+ *   AASR_PHN_STATE_NUM_LABELS  --snl: the first field after the times is the state's index (atoi; no HMM label is
+ *                              looked up).  With `transitions` the call is refused (AASR_ERR_UNSUPPORTED).
+ *   AASR_PHN_RELATIVE_SAMPLES  --rsamp: the file's times count from first_frame (start and end are shifted by it) and
+ *                              no line is skipped for first_frame.
+ * flags = 0 is aasr_stats_read_segmentation.  Host only. */
+#define AASR_PHN_STATE_NUM_LABELS 1
+#define AASR_PHN_RELATIVE_SAMPLES 2
+aasr_status aasr_phn_read_segmentation(const aasr_topo *topo, const char *path, float frame_rate,
+                                       int32_t first_frame, int32_t last_frame, int32_t eof_frame, int32_t flags,
+                                       int32_t transitions, int32_t *start_frame, int32_t **pdf,
+                                       int32_t **transition, int32_t *n_frames);
+
+/* ---------------------------------------------------------------------------
+ * VTLN warp-factor estimation: aku/vtln.cc over state-segmented .phn files.  Per speaker a grid of warp factors
+ * around a centre (1, or with `relative` the speaker's current factor); per grid point the utterances' features under
+ * that factor and the log-likelihood of their segmentations (aasr_segll), summed per speaker in recipe order and
+ * frame order; the best factor of every speaker is set on the module and the speaker configuration. */
+typedef struct aasr_vtln_options {
+  int32_t ophn;            /* -O: read the recipe's alignment= files              */
+  int32_t snl;             /* --snl: state-number labels                          */
+  int32_t rsamp;           /* --rsamp: sample numbers relative to the start time  */
+  int32_t info;            /* -i                                                  */
+  int32_t num_batches;     /* -B                                                  */
+  int32_t batch_index;     /* -I                                                  */
+  int32_t grid_size;       /* --grid-size (21)                                    */
+  int32_t grid_size_given; /* 1: --grid-size was on the command line              */
+  float grid_rad;          /* --grid-rad (0.1)                                    */
+  int32_t grid_rad_given;  /* 1: --grid-rad was on the command line               */
+  int32_t relative;        /* --relative                                          */
+  const char *module;      /* -v: the vtln module                                 */
+  struct aasr_spkc *speakers; /* -S: the speaker configuration (required)         */
+  const char *out;         /* -o: the speaker file to write, or NULL              */
+  const char *savesum;     /* -s: the summary file to write, or NULL              */
+} aasr_vtln_options;
+void aasr_vtln_default_options(aasr_vtln_options *opt);
+/* The grid of aku/vtln.cc:214-225 in float: grid_start (negated, as the loop uses it), grid_step, grid_size.  Host only. */
+void aasr_vtln_grid(const aasr_vtln_options *opt, float *grid_start, float *grid_step, int32_t *grid_size);
+/* save_vtln_stats (aku/vtln.cc:118-129): per speaker, in the order of the ids' bytes, "[id]", a "%.3f: %.3f" line per
+ * warp factor and an empty line.  counts[i] factors of speaker i follow each other in warps / logliks.  *text is
+ * malloc'ed (aasr_free).  Host only. */
+aasr_status aasr_vtln_summary_text(const char *const *speakers, int32_t n_speakers, const int32_t *counts,
+                                   const float *warps, const double *logliks, char **text, int64_t *len);
+/* Diagnostic: the bound on a group's frames in aasr_run_vtln_recipe (default 2^20; a group holds one utterance at
+ * least).  The files written do not depend on it.  <= 0: the default again. */
+void aasr_debug_vtln_set_group_frames(int64_t frames);
+/* vtln main loop (aku/vtln.cc:234-286) over one recipe slice (read with cluster_speakers). */
+aasr_status aasr_run_vtln_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
+                                 const char *recipe_path, const aasr_vtln_options *opt,
+                                 aasr_run_stats *stats);
+
+/* ---------------------------------------------------------------------------
  * Constrained MLLR estimation: aku/mllr.cc over state-segmented .phn files, one global transform per
  * speaker -- for a lin_transform feature module (-M) or as a model-side cmllr block (unitmode UNIT_NO).
  *
