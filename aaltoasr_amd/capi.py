@@ -163,6 +163,29 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_debug_segll_shape.restype = None
     L.aasr_phn_read_segmentation.argtypes = [vp, cp, f, i32, i32, i32, i32, i32, C.POINTER(i32),
                                              C.POINTER(C.POINTER(i32)), C.POINTER(C.POINTER(i32)), C.POINTER(i32)]
+    # HMM networks and the forward-backward pass
+    L.aasr_hmmnet_read.argtypes = [vp, cp, pvp]
+    L.aasr_hmmnet_destroy.argtypes = [vp]
+    L.aasr_hmmnet_destroy.restype = None
+    L.aasr_hmmnet_counts.argtypes = [vp, vp]
+    L.aasr_hmmnet_array.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
+    L.aasr_hmmnet_arc_label.argtypes = [vp, i32]
+    L.aasr_hmmnet_arc_label.restype = cp
+    L.aasr_fb_default_options.argtypes = [vp]
+    L.aasr_fb_default_options.restype = None
+    L.aasr_fb_batch_create.argtypes = [vp, i32, vp, vp, pvp]
+    L.aasr_fb_batch_destroy.argtypes = [vp]
+    L.aasr_fb_batch_destroy.restype = None
+    L.aasr_fb_batch_device_bytes.argtypes = [vp]
+    L.aasr_fb_batch_device_bytes.restype = i64
+    L.aasr_fb_batch_dev.argtypes = [vp, vp, i64, i64, i32, vp, i32, vp]
+    L.aasr_fb_batch_sync.argtypes = [vp, vp, C.POINTER(i32)]
+    L.aasr_fb_batch_result.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(d), C.POINTER(d), C.POINTER(i32), vp, vp]
+    L.aasr_debug_fb_shape.argtypes = [vp, C.POINTER(i32)]
+    L.aasr_debug_fb_shape.restype = None
+    L.aasr_logl_default_options.argtypes = [vp]
+    L.aasr_logl_default_options.restype = None
+    L.aasr_run_logl_recipe.argtypes = [vp, vp, vp, cp, vp, C.POINTER(d), vp]
     L.aasr_vtln_default_options.argtypes = [vp]
     L.aasr_vtln_default_options.restype = None
     L.aasr_vtln_grid.argtypes = [vp, C.POINTER(f), C.POINTER(f), C.POINTER(i32)]
@@ -1419,6 +1442,147 @@ def phn_read_segmentation(topo: Topology, path: str, frame_rate: float = 125.0, 
     finally:
         L.aasr_free(pp)
         L.aasr_free(tp)
+
+
+# ---- HMM networks and the forward-backward pass ------------------------------------------------
+
+FB_BAUM_WELCH, FB_VITERBI = 0, 1
+FB_OK, FB_FAILED_BACKWARD, FB_FAILED_FORWARD = 1, 2, 3
+
+_HMMNET_INT_ARRAYS = ("em_begin", "em_src", "em_tgt", "em_pdf", "em_tr", "em_self", "in_begin", "in_arcs", "pdfs",
+                      "pdf_begin", "pdf_arcs", "trs", "tr_begin", "tr_arcs", "eo_begin", "ep_src", "ep_tgt", "ei_begin",
+                      "ei_arcs", "bl_begin", "bl_nodes", "fl_begin", "fl_nodes")
+_HMMNET_DOUBLE_ARRAYS = ("em_logp", "em_static", "ep_score")
+
+
+class HmmNet:
+    """Owner of an aasr_hmmnet handle: an HMM network file (HmmNetBaumWelch::read_fst) as the flat arrays the
+    forward-backward kernel reads.  Host only."""
+
+    def __init__(self, topo: Topology, path: str):
+        h = C.c_void_p()
+        check(lib().aasr_hmmnet_read(topo.handle, path.encode(), C.byref(h)))
+        self._h = h.value
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_hmmnet_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self) -> int:
+        return self._h
+
+    def counts(self) -> dict:
+        out = np.zeros(9, np.int32)
+        check(lib().aasr_hmmnet_counts(self._h, _ptr(out)))
+        names = ("nodes", "emitting", "epsilon", "backward_levels", "forward_levels", "pdfs", "transitions", "initial",
+                 "final")
+        return {k: int(v) for k, v in zip(names, out)}
+
+    def array(self, name: str) -> np.ndarray:
+        """One of the reader's arrays by its name in csrc/hmmnet.h."""
+        if name in _HMMNET_INT_ARRAYS:
+            which, dtype = _HMMNET_INT_ARRAYS.index(name), np.int32
+        else:
+            which, dtype = 100 + _HMMNET_DOUBLE_ARRAYS.index(name), np.float64
+        n = C.c_int64()
+        check(lib().aasr_hmmnet_array(self._h, which, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype)
+        check(lib().aasr_hmmnet_array(self._h, which, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def arc_label(self, arc: int) -> Optional[str]:
+        s = lib().aasr_hmmnet_arc_label(self._h, arc)
+        return None if s is None else s.decode()
+
+
+class FbOptions(C.Structure):
+    """aasr_fb_options"""
+    _fields_ = [("fw_beam", C.c_double), ("bw_beam", C.c_double), ("ac_scale", C.c_double), ("mode", C.c_int32),
+                ("max_attempts", C.c_int32), ("want_pdf_occ", C.c_int32), ("want_tr_occ", C.c_int32),
+                ("force_global", C.c_int32)]
+
+    @classmethod
+    def defaults(cls) -> "FbOptions":
+        o = cls()
+        lib().aasr_fb_default_options(C.byref(o))
+        return o
+
+
+def fb_batch(nets: list, n_frames: list, scores, row0: list, opts: Optional[FbOptions] = None, stream: int = 0) -> list:
+    """Forward-backward over HMM networks on the device.  nets[u]: the HmmNet of utterance u; scores: a device tensor
+    of state log-likelihood rows (float32 or float64), row0[u] the row of utterance u's first frame.  Utterances whose
+    backward pass misses the initial node are launched again with backward beam 2x, 3x, ... up to max_attempts.
+    Returns per utterance a dict: status, backward_total, forward_total, attempts, pdf_occ, tr_occ (the last two None
+    unless the options ask for them), and `shape`, the launch shape of the first attempt."""
+    L = lib()
+    opts = opts or FbOptions.defaults()
+    n = len(nets)
+    handles = (C.c_void_p * max(n, 1))(*[h.handle for h in nets])
+    T = np.ascontiguousarray(n_frames, np.int32)
+    r0 = np.ascontiguousarray(row0, np.int64)
+    b = C.c_void_p()
+    check(L.aasr_fb_batch_create(C.byref(opts), n, handles, _ptr(T), C.byref(b)))
+    try:
+        f64 = 1 if str(scores.dtype) == "torch.float64" else 0
+        failed = C.c_int32(0)
+        shape = None
+        for attempt in range(1, opts.max_attempts + 1):
+            check(L.aasr_fb_batch_dev(b, _ptr(scores), scores.shape[1], scores.shape[0], f64, _ptr(r0), attempt, stream))
+            check(L.aasr_fb_batch_sync(b, stream, C.byref(failed)))
+            if shape is None:
+                sh = (C.c_int32 * 4)()
+                L.aasr_debug_fb_shape(b, sh)
+                shape = {"utterances": int(sh[0]), "lds_form": int(sh[1]), "lds_bytes": int(sh[2]), "attempt": int(sh[3])}
+            if failed.value == 0:
+                break
+        out = []
+        for u in range(n):
+            c = nets[u].counts()
+            st, at = C.c_int32(), C.c_int32()
+            bt, ft = C.c_double(), C.c_double()
+            occ = np.zeros((int(T[u]), c["pdfs"]), np.float64) if opts.want_pdf_occ else None
+            trocc = np.zeros(c["transitions"], np.float64) if opts.want_tr_occ else None
+            check(L.aasr_fb_batch_result(b, u, C.byref(st), C.byref(bt), C.byref(ft), C.byref(at), _ptr(occ), _ptr(trocc)))
+            out.append({"status": st.value, "backward_total": bt.value, "forward_total": ft.value, "attempts": at.value,
+                        "pdf_occ": occ, "tr_occ": trocc, "shape": shape, "device_bytes": L.aasr_fb_batch_device_bytes(b)})
+        return out
+    finally:
+        L.aasr_fb_batch_destroy(b)
+
+
+class LoglOptions(C.Structure):
+    """aasr_logl_options: logl's options (aku/logl.cc:91-112)."""
+    _fields_ = [("ophn", C.c_int32), ("snl", C.c_int32), ("hmmnet", C.c_int32), ("den_hmmnet", C.c_int32),
+                ("mpv", C.c_int32), ("vit", C.c_int32), ("ac_scale_given", C.c_int32), ("info", C.c_int32),
+                ("num_batches", C.c_int32), ("batch_index", C.c_int32), ("fw_beam", C.c_double), ("bw_beam", C.c_double),
+                ("ac_scale", C.c_double), ("speakers", C.c_void_p)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "LoglOptions":
+        o = cls()
+        lib().aasr_logl_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_logl_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str, opts: Optional[LoglOptions] = None,
+                    speakers: Optional["SpeakerConfig"] = None) -> dict:
+    """logl over a recipe -> the total log-likelihood (the per-file lines of info > 0 go to the process's stdout)"""
+    opts = opts or LoglOptions.defaults()
+    opts.speakers = speakers._h if speakers is not None else None
+    st, total = RunStats(), C.c_double()
+    check(lib().aasr_run_logl_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(total),
+                                     C.byref(st)))
+    return {"total": total.value, "utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}
 
 
 class VtlnOptions(C.Structure):

@@ -1,0 +1,272 @@
+// hmmnet_fb.cc -- the handle of the forward-backward pass over HMM networks (aasr_fb_batch_*): packs the
+// utterances' networks (hmmnet.h) into the blobs of hmmnet_fb.h, launches k_hmmnet_fb over the batch, and
+// relaunches the utterances whose backward pass missed the initial node with a wider backward beam
+// (aku/logl.cc:183-199: 2x, 3x, ... the original, the forward beam unchanged).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <map>
+#include <memory>
+#include <vector>
+
+#include "common.h"
+#include "hmmnet.h"
+#include "hmmnet_fb.h"
+
+using namespace aasr;
+
+struct aasr_fb_batch {
+  aasr_fb_options opt{};
+  int32_t n = 0;
+  bool lds_form = true;
+  std::vector<const aasr_hmmnet *> nets;
+  std::vector<FbUttDev> utt;
+  std::vector<FbResult> result;
+  std::vector<int32_t> list;
+  std::vector<double> occ, trocc;  // host copies after a sync
+  DevBuf<int32_t> d_ints, d_list;
+  DevBuf<double> d_doubles, d_work, d_occ, d_trocc;
+  DevBuf<FbUttDev> d_utt;
+  DevBuf<FbResult> d_result;
+  int64_t bytes = 0;
+  // the last launch (aasr_debug_fb_shape): utterances, 1 = LDS node vectors / 0 = global, LDS bytes, attempt
+  int32_t last_shape[4] = {0, 0, 0, 0};
+};
+
+extern "C" {
+
+void aasr_fb_default_options(aasr_fb_options *o) {
+  if (!o) return;
+  *o = aasr_fb_options();
+  o->fw_beam = 15;   // HmmNetBaumWelch's constructor
+  o->bw_beam = 200;
+  o->ac_scale = 1;
+  o->mode = AASR_FB_BAUM_WELCH;
+  o->max_attempts = 5;
+}
+
+aasr_status aasr_fb_batch_create(const aasr_fb_options *opt, int32_t n_utt, const aasr_hmmnet *const *nets,
+                                 const int32_t *n_frames, aasr_fb_batch **out) {
+  return guarded([&] {
+    if (!opt || n_utt < 0 || !out || (n_utt > 0 && (!nets || !n_frames)))
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_create: null argument");
+    *out = nullptr;
+    if (!(opt->fw_beam > 0) || !(opt->bw_beam > 0) || !std::isfinite(opt->fw_beam) || !std::isfinite(opt->bw_beam))
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_create: beams must be positive and finite");
+    if (!std::isfinite(opt->ac_scale)) raise(AASR_ERR_INVALID, "aasr_fb_batch_create: acoustic scale must be finite");
+    if (opt->mode != AASR_FB_BAUM_WELCH && opt->mode != AASR_FB_VITERBI)
+      raise(AASR_ERR_UNSUPPORTED, "aasr_fb_batch_create: mode %d (multipath Viterbi is not built)", opt->mode);
+    if (opt->max_attempts < 1) raise(AASR_ERR_INVALID, "aasr_fb_batch_create: max_attempts must be at least 1");
+    for (int u = 0; u < n_utt; u++) {
+      if (!nets[u]) raise(AASR_ERR_INVALID, "aasr_fb_batch_create: utterance %d has no network", u);
+      if (n_frames[u] < 1) raise(AASR_ERR_INVALID, "aasr_fb_batch_create: utterance %d has %d frames", u, n_frames[u]);
+    }
+    require_device();
+    std::unique_ptr<aasr_fb_batch> b(new aasr_fb_batch());
+    b->opt = *opt;
+    b->n = n_utt;
+    b->nets.assign(nets, nets + n_utt);
+    // each distinct network once in the blobs
+    std::vector<int32_t> ints;
+    std::vector<double> doubles;
+    std::map<const aasr_hmmnet *, FbNetDev> packed;
+    auto put_i = [&](const std::vector<int32_t> &v) {
+      const int32_t at = (int32_t)ints.size();
+      ints.insert(ints.end(), v.begin(), v.end());
+      return at;
+    };
+    auto put_d = [&](const std::vector<double> &v) {
+      const int32_t at = (int32_t)doubles.size();
+      doubles.insert(doubles.end(), v.begin(), v.end());
+      return at;
+    };
+    int32_t max_nodes = 0;
+    int64_t work = 0, occ = 0, trocc = 0;
+    b->utt.resize((size_t)n_utt);
+    for (int u = 0; u < n_utt; u++) {
+      const aasr_hmmnet &h = *nets[u];
+      if (ints.size() + 8 * (h.em_src.size() + h.ep_src.size() + (size_t)h.n_nodes) > (size_t)INT32_MAX)
+        raise(AASR_ERR_UNSUPPORTED, "aasr_fb_batch_create: the batch's networks exceed 2^31 table entries");
+      if (!packed.count(&h)) {
+        FbNetDev d{};
+        d.n_nodes = h.n_nodes;
+        d.n_em = (int32_t)h.em_src.size();
+        d.n_ep = (int32_t)h.ep_src.size();
+        d.n_bl = (int32_t)h.bl_begin.size() - 1;
+        d.n_fl = (int32_t)h.fl_begin.size() - 1;
+        d.n_pdf = (int32_t)h.pdfs.size();
+        d.n_tr = (int32_t)h.trs.size();
+        d.initial = h.initial;
+        d.final_node = h.final_node;
+        d.em_begin = put_i(h.em_begin);
+        d.em_src = put_i(h.em_src);
+        d.em_tgt = put_i(h.em_tgt);
+        d.em_pdf = put_i(h.em_pdf);
+        d.em_slot = put_i(h.em_slot);
+        d.em_trslot = put_i(h.em_trslot);
+        d.in_begin = put_i(h.in_begin);
+        d.in_arcs = put_i(h.in_arcs);
+        d.pdf_begin = put_i(h.pdf_begin);
+        d.pdf_arcs = put_i(h.pdf_arcs);
+        d.tr_begin = put_i(h.tr_begin);
+        d.tr_arcs = put_i(h.tr_arcs);
+        d.eo_begin = put_i(h.eo_begin);
+        d.ep_src = put_i(h.ep_src);
+        d.ep_tgt = put_i(h.ep_tgt);
+        d.ei_begin = put_i(h.ei_begin);
+        d.ei_arcs = put_i(h.ei_arcs);
+        d.bl_begin = put_i(h.bl_begin);
+        d.bl_nodes = put_i(h.bl_nodes);
+        d.fl_begin = put_i(h.fl_begin);
+        d.fl_nodes = put_i(h.fl_nodes);
+        d.em_logp = put_d(h.em_logp);
+        d.em_static = put_d(h.em_static);
+        d.ep_score = put_d(h.ep_score);
+        packed[&h] = d;
+      }
+      FbUttDev &d = b->utt[(size_t)u];
+      d.net = packed[&h];
+      d.row0 = 0;
+      d.T = n_frames[u];
+      d.beta = work;
+      work += ((int64_t)d.T + 1) * h.n_nodes;
+      d.best = work;
+      work += d.T;
+      d.arcs = work;
+      work += 2 * (int64_t)d.net.n_em;
+      d.nodes = work;
+      work += 2 * (int64_t)h.n_nodes;
+      d.occ = occ;
+      occ += (int64_t)d.T * d.net.n_pdf;
+      d.trocc = trocc;
+      trocc += d.net.n_tr;
+      max_nodes = std::max(max_nodes, h.n_nodes);
+    }
+    b->lds_form = max_nodes <= FB_LDS_NODES && !opt->force_global;
+    if (ints.empty()) ints.push_back(0);
+    if (doubles.empty()) doubles.push_back(0);
+    b->d_ints.upload(ints.data(), ints.size());
+    b->d_doubles.upload(doubles.data(), doubles.size());
+    const size_t nu = (size_t)std::max(1, n_utt);
+    b->d_utt.alloc(nu);
+    b->d_result.alloc(nu);
+    b->d_list.alloc(nu);
+    b->d_work.alloc((size_t)std::max<int64_t>(1, work));
+    if (opt->want_pdf_occ) b->d_occ.alloc((size_t)std::max<int64_t>(1, occ));
+    if (opt->want_tr_occ) b->d_trocc.alloc((size_t)std::max<int64_t>(1, trocc));
+    b->occ.assign(opt->want_pdf_occ ? (size_t)occ : 0, 0.0);
+    b->trocc.assign(opt->want_tr_occ ? (size_t)trocc : 0, 0.0);
+    b->result.assign((size_t)n_utt, FbResult{FB_ZERO, FB_ZERO, 0, 0});
+    b->bytes = (int64_t)(ints.size() * 4 + doubles.size() * 8 + (size_t)work * 8 + b->occ.size() * 8 + b->trocc.size() * 8 +
+                         nu * (sizeof(FbUttDev) + sizeof(FbResult) + 4));
+    *out = b.release();
+  });
+}
+
+void aasr_fb_batch_destroy(aasr_fb_batch *b) { delete b; }
+
+int64_t aasr_fb_batch_device_bytes(const aasr_fb_batch *b) { return b ? b->bytes : -1; }
+
+void aasr_debug_fb_shape(const aasr_fb_batch *b, int32_t *out) {
+  if (!b || !out) return;
+  std::copy(b->last_shape, b->last_shape + 4, out);
+}
+
+aasr_status aasr_fb_batch_dev(aasr_fb_batch *b, const void *d_state_loglik, int64_t pitch, int64_t n_rows, int32_t f64,
+                              const int64_t *row0, int32_t attempt, void *stream) {
+  return guarded([&] {
+    if (!b || (b->n > 0 && (!d_state_loglik || !row0)) || pitch < 1)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_dev: bad argument");
+    if (attempt < 1 || attempt > b->opt.max_attempts)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_dev: attempt %d outside 1 .. %d", attempt, b->opt.max_attempts);
+    const hipStream_t st = (hipStream_t)stream;
+    b->list.clear();
+    for (int u = 0; u < b->n; u++) {
+      const aasr_hmmnet &h = *b->nets[(size_t)u];
+      for (int32_t pdf : h.pdfs)
+        if (pdf >= pitch) raise(AASR_ERR_INVALID, "aasr_fb_batch_dev: utterance %d uses pdf %d, rows have %lld columns", u, pdf, (long long)pitch);
+      if (row0[u] < 0 || row0[u] + b->utt[(size_t)u].T > n_rows)
+        raise(AASR_ERR_INVALID, "aasr_fb_batch_dev: utterance %d reads rows %lld .. %lld of %lld", u, (long long)row0[u],
+              (long long)(row0[u] + b->utt[(size_t)u].T), (long long)n_rows);
+      b->utt[(size_t)u].row0 = row0[u];
+      // the first attempt runs every utterance, a later one those whose backward pass failed (results of a sync)
+      if (attempt == 1 || b->result[(size_t)u].status == FB_FAILED_BACKWARD) b->list.push_back(u);
+    }
+    if (attempt == 1) {
+      for (FbResult &r : b->result) r = FbResult{FB_ZERO, FB_ZERO, 0, 0};
+      if (b->n) AASR_HIP(hipMemcpyAsync(b->d_result.p, b->result.data(), b->result.size() * sizeof(FbResult), hipMemcpyHostToDevice, st));
+    }
+    b->last_shape[0] = (int32_t)b->list.size();
+    b->last_shape[1] = b->lds_form ? 1 : 0;
+    b->last_shape[2] = (int32_t)((b->lds_form ? 2 * FB_LDS_NODES : 1) * sizeof(double) + FB_THREADS * sizeof(double));
+    b->last_shape[3] = attempt;
+    if (b->list.empty()) return;
+    AASR_HIP(hipMemcpyAsync(b->d_utt.p, b->utt.data(), b->utt.size() * sizeof(FbUttDev), hipMemcpyHostToDevice, st));
+    AASR_HIP(hipMemcpyAsync(b->d_list.p, b->list.data(), b->list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    FbParams p{};
+    p.ints = b->d_ints.p;
+    p.doubles = b->d_doubles.p;
+    p.utt = b->d_utt.p;
+    p.list = b->d_list.p;
+    p.scores = d_state_loglik;
+    p.pitch = pitch;
+    p.f64 = f64 ? 1 : 0;
+    p.mode = b->opt.mode == AASR_FB_VITERBI ? FB_MODE_VITERBI : FB_MODE_BAUM_WELCH;
+    p.want_pdf_occ = b->opt.want_pdf_occ ? 1 : 0;
+    p.want_tr_occ = b->opt.want_tr_occ ? 1 : 0;
+    p.fw_beam = b->opt.fw_beam;
+    p.bw_beam = attempt * b->opt.bw_beam;
+    p.ac_scale = b->opt.ac_scale;
+    p.work = b->d_work.p;
+    p.occ = b->d_occ.p;
+    p.trocc = b->d_trocc.p;
+    p.result = b->d_result.p;
+    hmmnet_fb_launch(p, (int32_t)b->list.size(), b->lds_form, st);
+    AASR_HIP(hipGetLastError());
+    // the host tables of this call are read by the copies above: wait for them before the next call rewrites them
+    AASR_HIP(hipStreamSynchronize(st));
+  });
+}
+
+aasr_status aasr_fb_batch_sync(aasr_fb_batch *b, void *stream, int32_t *n_failed_backward) {
+  return guarded([&] {
+    if (!b) raise(AASR_ERR_INVALID, "aasr_fb_batch_sync: null argument");
+    const hipStream_t st = (hipStream_t)stream;
+    if (b->n > 0) {
+      AASR_HIP(hipMemcpyAsync(b->result.data(), b->d_result.p, b->result.size() * sizeof(FbResult), hipMemcpyDeviceToHost, st));
+      if (!b->occ.empty())
+        AASR_HIP(hipMemcpyAsync(b->occ.data(), b->d_occ.p, b->occ.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (!b->trocc.empty())
+        AASR_HIP(hipMemcpyAsync(b->trocc.data(), b->d_trocc.p, b->trocc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      AASR_HIP(hipStreamSynchronize(st));
+    }
+    int failed = 0;
+    for (const FbResult &r : b->result) failed += r.status == FB_FAILED_BACKWARD;
+    if (n_failed_backward) *n_failed_backward = failed;
+  });
+}
+
+aasr_status aasr_fb_batch_result(const aasr_fb_batch *b, int32_t u, int32_t *status, double *backward_total,
+                                 double *forward_total, int32_t *attempts, double *pdf_occ, double *tr_occ) {
+  return guarded([&] {
+    if (!b || u < 0 || u >= b->n) raise(AASR_ERR_INVALID, "aasr_fb_batch_result: bad argument");
+    const FbResult &r = b->result[(size_t)u];
+    const FbUttDev &d = b->utt[(size_t)u];
+    if (status) *status = r.status;
+    if (backward_total) *backward_total = r.backward_total;
+    if (forward_total) *forward_total = r.forward_total;
+    if (attempts) *attempts = r.attempts;
+    if (pdf_occ) {
+      if (!b->opt.want_pdf_occ) raise(AASR_ERR_INVALID, "aasr_fb_batch_result: the batch was created without pdf occupancies");
+      if (r.status == FB_OK) std::copy(b->occ.begin() + d.occ, b->occ.begin() + d.occ + (int64_t)d.T * d.net.n_pdf, pdf_occ);
+    }
+    if (tr_occ) {
+      if (!b->opt.want_tr_occ) raise(AASR_ERR_INVALID, "aasr_fb_batch_result: the batch was created without transition occupancies");
+      if (r.status == FB_OK) std::copy(b->trocc.begin() + d.trocc, b->trocc.begin() + d.trocc + d.net.n_tr, tr_occ);
+    }
+  });
+}
+
+}  // extern "C"

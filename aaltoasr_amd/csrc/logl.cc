@@ -1,0 +1,271 @@
+// logl.cc -- the log-likelihood of a recipe (aku/logl.cc): per utterance the sum of the frame log-likelihoods along
+// a .phn state segmentation (seg_loglik.hip; logl.cc's transtat is an unset global, so no transition terms enter), or
+// with -H / -D the forward total of the forward-backward pass over the utterance's HMM network (hmmnet_fb.hip) on the
+// state log-likelihood rows of the model's scoring entry.  The recipe pass is the shared one (recipe_pass.h).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "gmm.h"
+#include "hmmnet.h"
+#include "hmmnet_fb.h"
+#include "phn_line.h"
+#include "recipe_pass.h"
+#include "stats.h"
+
+using namespace aasr;
+
+namespace {
+
+constexpr int64_t LOGL_GROUP_FRAMES = (int64_t)1 << 18;
+constexpr int64_t LOGL_GROUP_SCORES = (int64_t)1 << 27;  // rows x states of a group's score buffer
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// logl.cc:71-80
+void print_file_line(const RecipeInfo &u, int info, double ll) {
+  if (info <= 0) return;
+  fprintf(stdout, "Log likelihood for file %s", u.audio_path.c_str());
+  if (u.start_time || u.end_time) fprintf(stdout, " (%.2f-%.2f)", u.start_time, u.end_time);
+  fprintf(stdout, ": %f\n", ll);
+}
+
+void set_speaker(aasr_spkc *spk, const RecipeInfo &u) {
+  if (!spk) return;
+  if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
+    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+}
+
+}  // namespace
+
+extern "C" {
+
+void aasr_logl_default_options(aasr_logl_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->ac_scale = 1;
+}
+
+aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                 const aasr_logl_options *opt, double *total_log_likelihood, aasr_run_stats *stats) {
+  return guarded([&] {
+    if (!feat || !gmm || !topo || !recipe_path || !opt || !total_log_likelihood)
+      raise(AASR_ERR_INVALID, "aasr_run_logl_recipe: null argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    if (opt->mpv) raise(AASR_ERR_UNSUPPORTED, "logl: --mpv (multipath Viterbi) is not supported");
+    aasr_spkc *spk = opt->speakers;
+    const std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, true);
+    refuse_line_limits(infos, "logl");
+    check_feature_dim(gmm, feat);
+    check_stats_model(gmm, "logl");
+    const bool nets = opt->hmmnet || opt->den_hmmnet;
+    const TopoTables tt(topo);
+    const float fr = aasr_feat_frame_rate(feat);
+    const bool timing = getenv("AASR_RECIPE_TIMING") != nullptr;
+    double t_host = 0, t_feat = 0, t_score = 0, t_fb = 0;
+    GroupStager stager(feat, spk);
+    const hipStream_t stream = stager.stream;
+    double total = 0;
+    int64_t num_frames = 0;
+
+    if (!nets) {
+      aasr_segll *h = nullptr;
+      {
+        const aasr_status cs = aasr_segll_create(gmm, &h);
+        if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
+      }
+      std::unique_ptr<aasr_segll, void (*)(aasr_segll *)> hguard(h, aasr_segll_destroy);
+      const int phn_flags = opt->snl ? PHN_STATE_NUM_LABELS : 0;
+      DevBuf<double> d_ll;
+      std::vector<double> ll;
+      size_t next = 0;
+      while (next < infos.size()) {
+        const size_t group_first = next;
+        std::vector<std::vector<int16_t>> audio;
+        std::vector<int32_t> start, rows, pdfs;
+        std::vector<char> ok;
+        int64_t rows_total = 0;
+        while (next < infos.size() && audio.size() < 1024 && (audio.empty() || rows_total < LOGL_GROUP_FRAMES)) {
+          const RecipeInfo &u = infos[next++];
+          audio.push_back(load_utterance_input(feat, u));
+          int first, last;
+          frame_range(u, fr, &first, &last);
+          const Segmentation seg =
+              read_segmentation(topo, tt, (opt->ophn ? u.alignment_path : u.transcript_path).c_str(), fr, first, last,
+                                aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), false, phn_flags);
+          if (!seg.initialized) {  // logl.cc:210-216
+            fprintf(stderr, "Could not initialize the utterance for PhnReader.");
+            fprintf(stderr, "Current file was: %s\n", u.audio_path.c_str());
+            audio.back().clear();
+          }
+          ok.push_back(seg.initialized);
+          start.push_back(seg.start_frame);
+          rows.push_back((int32_t)seg.pdf.size());
+          pdfs.insert(pdfs.end(), seg.pdf.begin(), seg.pdf.end());
+          rows_total += (int64_t)seg.pdf.size();
+        }
+        stager.stage(audio, start, rows, [&](size_t i) { set_speaker(spk, infos[group_first + i]); });
+        if (rows_total > 0) {
+          check_stats_model(gmm, "logl");  // (a speaker's cmllr block would have reached the model by now)
+          d_ll.ensure((size_t)rows_total);
+          if (aasr_segll_score_dev(h, stager.d_x.p, rows_total, pdfs.data(), d_ll.p, stream) != AASR_OK)
+            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+          ll.resize((size_t)rows_total);
+          AASR_HIP(hipMemcpyAsync(ll.data(), d_ll.p, ll.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+          AASR_HIP(hipStreamSynchronize(stream));
+        }
+        size_t row = 0;
+        for (size_t i = 0; i < audio.size(); i++) {
+          if (!ok[i]) continue;
+          double cur = 0;  // the frames in order, safe_log(1 * state_likelihood) each (logl.cc:57-60)
+          for (int32_t f = 0; f < rows[i]; f++) cur += ll[row + (size_t)f];
+          row += (size_t)rows[i];
+          print_file_line(infos[group_first + i], opt->info, cur);
+          total += cur;
+        }
+        num_frames += rows_total;
+      }
+      *total_log_likelihood = total;
+      fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
+      return;
+    }
+
+    // ---- HMM networks ----
+    aasr_fb_options fo;
+    aasr_fb_default_options(&fo);
+    if (opt->fw_beam > 0) fo.fw_beam = opt->fw_beam;  // set_pruning_thresholds: 0 keeps the default
+    if (opt->bw_beam > 0) fo.bw_beam = opt->bw_beam;
+    if (opt->ac_scale_given) fo.ac_scale = opt->ac_scale;
+    fo.mode = opt->vit ? AASR_FB_VITERBI : AASR_FB_BAUM_WELCH;
+    const int S = aasr_gmm_num_states(gmm), D = aasr_gmm_dim(gmm);
+    const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
+    std::map<std::string, std::unique_ptr<aasr_hmmnet, void (*)(aasr_hmmnet *)>> net_cache;
+    DevBuf<double> d_scores64;
+    DevBuf<float> d_scores32, d_x32;
+    std::vector<double> x64;
+    std::vector<float> x32;
+    size_t next = 0;
+    while (next < infos.size()) {
+      double t = now_s();
+      const size_t group_first = next;
+      std::vector<std::vector<int16_t>> audio;
+      std::vector<int32_t> start, rows;
+      std::vector<const aasr_hmmnet *> group_nets;
+      int64_t rows_total = 0;
+      while (next < infos.size() && audio.size() < 1024 &&
+             (audio.empty() || (rows_total < LOGL_GROUP_FRAMES && rows_total * S < LOGL_GROUP_SCORES))) {
+        const RecipeInfo &u = infos[next++];
+        audio.push_back(load_utterance_input(feat, u));
+        // Recipe::Info::init_hmmnet_files (Recipe.cc:198-231)
+        if (!opt->den_hmmnet && u.hmmnet_path.empty())
+          raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
+        const std::string &path = opt->den_hmmnet ? u.den_hmmnet_path : u.hmmnet_path;
+        auto it = net_cache.find(path);
+        if (it == net_cache.end()) {
+          aasr_hmmnet *net = nullptr;
+          const aasr_status rs = aasr_hmmnet_read(topo, path.c_str(), &net);
+          if (rs != AASR_OK) raise(rs, "%s", last_error().c_str());
+          it = net_cache.emplace(path, std::unique_ptr<aasr_hmmnet, void (*)(aasr_hmmnet *)>(net, aasr_hmmnet_destroy)).first;
+        }
+        for (int32_t pdf : it->second->pdfs)
+          if (pdf >= S) raise(AASR_ERR_INVALID, "%s: state %d is not below the model's %d states", path.c_str(), pdf, S);
+        group_nets.push_back(it->second.get());
+        // the frame limits (Recipe.cc:223-228, HmmNetBaumWelch::generate_features): first .. last, or to the last frame
+        // of the audio; a limit past the audio is cut to it
+        int first, last;
+        frame_range(u, fr, &first, &last);
+        const int eof = aasr_feat_eof_frame(feat, (int64_t)audio.back().size());
+        const int end = last > 0 ? std::min(last, eof) : eof;
+        if (end - first < 1)
+          raise(AASR_ERR_INVALID, "HmmNetBaumWelch: no frames for %s (frames %d to %d)", u.audio_path.c_str(), first, end);
+        if (end - first == 1) fprintf(stderr, "HmmNetBaumWelch: Warning: Single frame utterance\n");
+        start.push_back(first);
+        rows.push_back(end - first);
+        rows_total += end - first;
+      }
+      t_host += now_s() - t;
+      t = now_s();
+      stager.stage(audio, start, rows, [&](size_t i) { set_speaker(spk, infos[group_first + i]); });
+      if (timing) AASR_HIP(hipStreamSynchronize(stream));
+      t_feat += now_s() - t;
+      t = now_s();
+      check_stats_model(gmm, "logl");
+      const void *d_rows = nullptr;
+      if (f64) {
+        d_scores64.ensure((size_t)rows_total * S);
+        if (aasr_gmm_score_f64_dev(gmm, stager.d_x.p, rows_total, d_scores64.p, stream) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        d_rows = d_scores64.p;
+      } else {
+        // the scoring entry of the default mode takes float frames
+        x64.resize((size_t)rows_total * D);
+        AASR_HIP(hipMemcpyAsync(x64.data(), stager.d_x.p, x64.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        AASR_HIP(hipStreamSynchronize(stream));
+        x32.assign(x64.begin(), x64.end());
+        d_x32.ensure(x32.size());
+        d_scores32.ensure((size_t)rows_total * S);
+        AASR_HIP(hipMemcpyAsync(d_x32.p, x32.data(), x32.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (aasr_gmm_score_dev(gmm, d_x32.p, rows_total, d_scores32.p, stream) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        d_rows = d_scores32.p;
+      }
+      if (timing) AASR_HIP(hipStreamSynchronize(stream));
+      t_score += now_s() - t;
+      t = now_s();
+      aasr_fb_batch *b = nullptr;
+      if (aasr_fb_batch_create(&fo, (int32_t)group_nets.size(), group_nets.data(), rows.data(), &b) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      std::unique_ptr<aasr_fb_batch, void (*)(aasr_fb_batch *)> bguard(b, aasr_fb_batch_destroy);
+      std::vector<int64_t> row0;
+      int64_t at = 0;
+      for (int32_t r : rows) {
+        row0.push_back(at);
+        at += r;
+      }
+      // logl.cc:183-199: a failed backward pass is run again with 2x, 3x, ... 5x the backward beam -- new launches over
+      // the failed utterances only
+      int32_t failed = 0;
+      for (int attempt = 1; attempt <= fo.max_attempts; attempt++) {
+        if (aasr_fb_batch_dev(b, d_rows, S, rows_total, f64 ? 1 : 0, row0.data(), attempt, stream) != AASR_OK ||
+            aasr_fb_batch_sync(b, stream, &failed) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        if (failed == 0) break;
+      }
+      t_fb += now_s() - t;
+      for (size_t i = 0; i < group_nets.size(); i++) {
+        const RecipeInfo &u = infos[group_first + i];
+        int32_t status = 0, attempts = 0;
+        double fw = 0;
+        if (aasr_fb_batch_result(b, (int32_t)i, &status, nullptr, &fw, &attempts, nullptr, nullptr) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        for (int k = 2; k <= attempts; k++)
+          fprintf(stderr, "Warning: Backward phase failed, increasing beam to %.1f\n", k * fo.bw_beam);
+        if (status == FB_FAILED_BACKWARD) {
+          fprintf(stderr, "Could not run Baum-Welch for file %s\n", u.audio_path.c_str());
+          fprintf(stderr, "The HMM network may be incorrect or initial beam too low.\n");
+          continue;
+        }
+        if (status != FB_OK) raise(AASR_ERR_INVALID, "No paths survived to the end of the network!");
+        print_file_line(u, opt->info, fw);
+        total += fw;
+      }
+      num_frames += rows_total;
+    }
+    if (timing)
+      fprintf(stderr, "logl timing: input and networks %.3f s, features %.3f s, scoring %.3f s, forward-backward %.3f s\n",
+              t_host, t_feat, t_score, t_fb);
+    *total_log_likelihood = total;
+    fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
+  });
+}
+
+}  // extern "C"

@@ -856,6 +856,105 @@ aasr_status aasr_run_vtln_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
                                  aasr_run_stats *stats);
 
 /* ---------------------------------------------------------------------------
+ * HMM networks and the forward-backward pass over them (aku/HmmNetBaumWelch.cc).
+ *
+ * aasr_hmmnet_read: HmmNetBaumWelch::read_fst (aku/HmmNetBaumWelch.cc:65-163) with check_network_structure (:536-617)
+ * and the topological-order check of :165-289, all with the reference's messages (aasr_last_error).  The text FST has
+ * "I node", "F node" and "T src dst [in [out [score]]]" lines; "," is the epsilon string, a "#..." input label an
+ * epsilon arc, any other label starts with the global transition index (HmmSet::read_ph order, the numbering of
+ * aasr_stats_read_segmentation) and may go on with ";..." higher-level labels, which are kept as text only: the
+ * logical-arc hierarchy is not built.  Host only, works without a device. */
+typedef struct aasr_hmmnet aasr_hmmnet;
+aasr_status aasr_hmmnet_read(const aasr_topo *topo, const char *path, aasr_hmmnet **out);
+void aasr_hmmnet_destroy(aasr_hmmnet *net);
+/* counts[AASR_HMMNET_NUM_COUNTS]: nodes, emitting arcs, epsilon arcs, backward epsilon levels, forward epsilon levels,
+ * distinct pdfs, distinct transition indices, initial node, final node */
+#define AASR_HMMNET_NUM_COUNTS 9
+aasr_status aasr_hmmnet_counts(const aasr_hmmnet *net, int32_t *counts);
+/* The reader's flat arrays (csrc/hmmnet.h).  int32 arrays 0..22: em_begin, em_src, em_tgt, em_pdf, em_tr, em_self,
+ * in_begin, in_arcs, pdfs, pdf_begin, pdf_arcs, trs, tr_begin, tr_arcs, eo_begin, ep_src, ep_tgt, ei_begin, ei_arcs,
+ * bl_begin, bl_nodes, fl_begin, fl_nodes; double arrays 100..102: em_logp, em_static, ep_score.  *count receives the
+ * length; the array is copied when out is given and capacity (elements) suffices. */
+aasr_status aasr_hmmnet_array(const aasr_hmmnet *net, int32_t which, void *out, int64_t capacity, int64_t *count);
+/* the ";..." part of emitting arc `arc`'s label ("" without one); NULL out of range */
+const char *aasr_hmmnet_arc_label(const aasr_hmmnet *net, int32_t arc);
+
+/* The batched pass: fill_backward_probabilities (aku/HmmNetBaumWelch.cc:817-1020) with
+ * backward_propagate_epsilon_arcs (:1023-1075), then create_segmented_lattice (:1078-1419), arc scores as
+ * get_arc_score (:1917-1942) with static scores and transition probabilities on, in dense form on the device
+ * (csrc/hmmnet_fb.hip): one workgroup per utterance, double arithmetic, no atomics, fixed summation orders. */
+#define AASR_FB_BAUM_WELCH 0
+#define AASR_FB_VITERBI 1
+#define AASR_FB_OK 1              /* both passes ran                                                    */
+#define AASR_FB_FAILED_BACKWARD 2 /* the backward pass did not reach the initial node (widen the beam) */
+#define AASR_FB_FAILED_FORWARD 3  /* no token survived the forward pass                                 */
+typedef struct aasr_fb_options {
+  double fw_beam;        /* -F (15), set_pruning_thresholds (:526-532)                                        */
+  double bw_beam;        /* -W (200)                                                                          */
+  double ac_scale;       /* -A (1), set_acoustic_scaling                                                      */
+  int32_t mode;          /* AASR_FB_BAUM_WELCH, or AASR_FB_VITERBI (-V)                                       */
+  int32_t max_attempts;  /* attempt k runs with backward beam k x bw_beam (aku/logl.cc:183-199: 5)            */
+  int32_t want_pdf_occ;  /* keep, per frame, the occupancy of every pdf of the network's pdf list             */
+  int32_t want_tr_occ;   /* keep, per transition index of the network, the occupancy summed over the frames   */
+  int32_t force_global;  /* node vectors in global memory whatever the networks' size (csrc/hmmnet_fb.h)      */
+} aasr_fb_options;
+void aasr_fb_default_options(aasr_fb_options *opt);
+typedef struct aasr_fb_batch aasr_fb_batch;
+/* nets[u] (alive as long as the batch) and the number of frames of utterance u (the frame range last - first of
+ * HmmNetBaumWelch::set_frame_limits, at least 1) */
+aasr_status aasr_fb_batch_create(const aasr_fb_options *opt, int32_t n_utt, const aasr_hmmnet *const *nets,
+                                 const int32_t *n_frames, aasr_fb_batch **out);
+void aasr_fb_batch_destroy(aasr_fb_batch *b);
+int64_t aasr_fb_batch_device_bytes(const aasr_fb_batch *b);
+/* State log-likelihood rows already on the device, as aasr_align_batch_dev takes them: float rows, or double rows when
+ * f64, `pitch` elements apart, n_rows of them; row0[u] is the row of utterance u's first frame.  attempt 1 runs every
+ * utterance with the options' backward beam; attempt k > 1 is a new launch over the utterances that the last
+ * aasr_fb_batch_sync found with AASR_FB_FAILED_BACKWARD only, with backward beam k x bw_beam and the forward beam
+ * unchanged (aku/logl.cc:183-199).  Returns when the launch has been queued and its tables copied. */
+aasr_status aasr_fb_batch_dev(aasr_fb_batch *b, const void *d_state_loglik, int64_t pitch, int64_t n_rows, int32_t f64,
+                              const int64_t *row0, int32_t attempt, void *stream);
+/* waits for the stream and fetches the results; *n_failed_backward: utterances a further attempt would run */
+aasr_status aasr_fb_batch_sync(aasr_fb_batch *b, void *stream, int32_t *n_failed_backward);
+/* After a sync.  backward_total: the initial node's score after the first frame (m_total_score); forward_total: the sum
+ * over the tokens alive after the last frame (:1389-1416, trailing epsilon arcs not added), what
+ * get_total_log_likelihood returns.  pdf_occ [n_frames x pdfs] and tr_occ [transitions] follow the network's pdfs / trs
+ * arrays and are written for AASR_FB_OK only; either may be NULL. */
+aasr_status aasr_fb_batch_result(const aasr_fb_batch *b, int32_t u, int32_t *status, double *backward_total,
+                                 double *forward_total, int32_t *attempts, double *pdf_occ, double *tr_occ);
+/* Diagnostic, read-only: the last aasr_fb_batch_dev call -- out[0] utterances launched, out[1] 1: node vectors in LDS,
+ * 0: in global memory, out[2] LDS bytes of a workgroup, out[3] the attempt.  Four zeros before the first call. */
+void aasr_debug_fb_shape(const aasr_fb_batch *b, int32_t *out);
+
+/* logl main loop (aku/logl.cc:145-234) over one recipe slice (read with cluster_speakers): per utterance the sum of the
+ * frame log-likelihoods along its .phn segmentation (aasr_segll; logl.cc's transtat is an unset global, so no
+ * transition terms enter), or with hmmnet / den_hmmnet the forward total of the pass above over the recipe's hmmnet= /
+ * den-hmmnet= network on the state rows of the model's scoring entry in the model's precision mode (AASR_PREC_F64:
+ * double rows), frame limits from the line's start and end times (aku/Recipe.cc:223-228).  A failed backward pass is
+ * run again with 2x ... 5x the backward beam (aku/logl.cc:183-199), new launches over the failed utterances only, with
+ * the reference's warnings on stderr; an utterance that still fails is reported and skipped.  With info > 0 the
+ * reference's "Log likelihood for file ..." line per utterance goes to stdout.  *total_log_likelihood: the sum.
+ * Refused (AASR_ERR_UNSUPPORTED): mpv, recipe start-line / end-line, non-diagonal pools, model-side transforms. */
+typedef struct aasr_logl_options {
+  int32_t ophn;            /* -O: read the recipe's alignment= files                         */
+  int32_t snl;             /* --snl: state-number labels                                     */
+  int32_t hmmnet;          /* -H                                                             */
+  int32_t den_hmmnet;      /* -D: the recipe's den-hmmnet= networks                          */
+  int32_t mpv;             /* -M: refused                                                    */
+  int32_t vit;             /* -V                                                             */
+  int32_t ac_scale_given;  /* 1: -A was on the command line                                  */
+  int32_t info;            /* -i                                                             */
+  int32_t num_batches;     /* -B                                                             */
+  int32_t batch_index;     /* -I                                                             */
+  double fw_beam;          /* -F: 0 keeps the default 15 (set_pruning_thresholds)            */
+  double bw_beam;          /* -W: 0 keeps the default 200                                    */
+  double ac_scale;         /* -A                                                             */
+  struct aasr_spkc *speakers; /* -S: the speaker configuration, or NULL                      */
+} aasr_logl_options;
+void aasr_logl_default_options(aasr_logl_options *opt);
+aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                 const aasr_logl_options *opt, double *total_log_likelihood, aasr_run_stats *stats);
+
+/* ---------------------------------------------------------------------------
  * Constrained MLLR estimation: aku/mllr.cc over state-segmented .phn files, one global transform per
  * speaker -- for a lin_transform feature module (-M) or as a model-side cmllr block (unitmode UNIT_NO).
  *
