@@ -145,6 +145,7 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_stats_destroy.argtypes = [vp]
     L.aasr_stats_destroy.restype = None
     L.aasr_stats_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.aasr_stats_accumulate_weighted_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.aasr_stats_add_transitions.argtypes = [vp, vp, i64]
     L.aasr_stats_fetch.argtypes = [vp, vp]
     L.aasr_stats_gaussians.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -155,6 +156,9 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_stats_default_options.argtypes = [vp]
     L.aasr_stats_default_options.restype = None
     L.aasr_run_stats_recipe.argtypes = [vp, vp, vp, cp, vp, vp]
+    L.aasr_stats_network_default_options.argtypes = [vp]
+    L.aasr_stats_network_default_options.restype = None
+    L.aasr_run_stats_networks_recipe.argtypes = [vp, vp, vp, cp, vp, vp, vp]
     L.aasr_segll_create.argtypes = [vp, pvp]
     L.aasr_segll_destroy.argtypes = [vp]
     L.aasr_segll_destroy.restype = None
@@ -183,6 +187,11 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_fb_batch_result.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(d), C.POINTER(d), C.POINTER(i32), vp, vp]
     L.aasr_debug_fb_shape.argtypes = [vp, C.POINTER(i32)]
     L.aasr_debug_fb_shape.restype = None
+    L.aasr_fb_batch_entries_dev.argtypes = [vp, i32, vp, vp, vp, pvp, pvp]
+    L.aasr_fb_batch_entries_host.argtypes = [vp, vp, vp]
+    L.aasr_fb_batch_frame_sums.argtypes = [vp, i32, vp]
+    L.aasr_debug_fb_entries_shape.argtypes = [vp, C.POINTER(i32)]
+    L.aasr_debug_fb_entries_shape.restype = None
     L.aasr_logl_default_options.argtypes = [vp]
     L.aasr_logl_default_options.restype = None
     L.aasr_run_logl_recipe.argtypes = [vp, vp, vp, cp, vp, C.POINTER(d), vp]
@@ -1312,6 +1321,15 @@ class Stats:
         check(lib().aasr_stats_accumulate_dev(self._h, _ptr(d_frames), len(p), _ptr(p), _ptr(d_frame_ll),
                                               _stream_handle(stream)))
 
+    def accumulate_weighted_dev(self, d_frames, cnt, d_rows, d_weights, stream=None) -> None:
+        """Weighted entries: cnt (host int64, states + 1) the first entry of every pdf in d_rows (int32 device tensor)
+        and d_weights (float64 device tensor); d_frames a float64 device tensor [n x dim]."""
+        c = np.ascontiguousarray(cnt, np.int64)
+        if len(c) != self.S + 1:
+            raise ValueError("cnt must have %d entries" % (self.S + 1))
+        check(lib().aasr_stats_accumulate_weighted_dev(self._h, _ptr(d_frames), int(d_frames.shape[0]), _ptr(c), _ptr(d_rows),
+                                                       _ptr(d_weights), _stream_handle(stream)))
+
     def launch_shape(self) -> dict:
         """Diagnostic: the shape of the accumulation kernel's launch in the last accumulate_dev call that launched it
         (zeros before the first): its dimension instance, frames per sub-block, whether the mixture records were staged
@@ -1371,13 +1389,33 @@ class Stats:
         check(lib().aasr_stats_write(self._h, base.encode()))
 
 
+class StatsNetworkOptions(C.Structure):
+    """aasr_stats_network_options: what stats --networks adds (-M vit, -F, -W, -A)."""
+    _fields_ = [("viterbi", C.c_int32), ("ac_scale_given", C.c_int32), ("fw_beam", C.c_double), ("bw_beam", C.c_double),
+                ("ac_scale", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "StatsNetworkOptions":
+        o = cls()
+        lib().aasr_stats_network_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
 def run_stats_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str, out: str,
-                     opts: Optional[StatsOptions] = None) -> dict:
+                     opts: Optional[StatsOptions] = None, networks: Optional[StatsNetworkOptions] = None) -> dict:
+    """stats over a recipe; with `networks` Baum-Welch over the recipe's hmmnet= networks (stats --networks)"""
     opts = opts or StatsOptions.defaults()
     ob = out.encode()
     opts.out = ob
     st = RunStats()
-    check(lib().aasr_run_stats_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    L = lib()
+    if networks is None:
+        check(L.aasr_run_stats_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    else:
+        check(L.aasr_run_stats_networks_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts),
+                                               C.byref(networks), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}
 
 
@@ -1507,7 +1545,7 @@ class FbOptions(C.Structure):
     """aasr_fb_options"""
     _fields_ = [("fw_beam", C.c_double), ("bw_beam", C.c_double), ("ac_scale", C.c_double), ("mode", C.c_int32),
                 ("max_attempts", C.c_int32), ("want_pdf_occ", C.c_int32), ("want_tr_occ", C.c_int32),
-                ("force_global", C.c_int32)]
+                ("force_global", C.c_int32), ("device_occ", C.c_int32)]
 
     @classmethod
     def defaults(cls) -> "FbOptions":
@@ -1553,6 +1591,64 @@ def fb_batch(nets: list, n_frames: list, scores, row0: list, opts: Optional[FbOp
             check(L.aasr_fb_batch_result(b, u, C.byref(st), C.byref(bt), C.byref(ft), C.byref(at), _ptr(occ), _ptr(trocc)))
             out.append({"status": st.value, "backward_total": bt.value, "forward_total": ft.value, "attempts": at.value,
                         "pdf_occ": occ, "tr_occ": trocc, "shape": shape, "device_bytes": L.aasr_fb_batch_device_bytes(b)})
+        return out
+    finally:
+        L.aasr_fb_batch_destroy(b)
+
+
+def fb_batch_entries(nets: list, n_frames: list, scores, row0: list, n_states: int, opts: Optional[FbOptions] = None,
+                     frame_row0: Optional[list] = None, stream: int = 0) -> dict:
+    """The forward-backward pass of fb_batch with the occupancies kept on the device (device_occ) and turned into
+    weighted statistics entries there (aasr_fb_batch_entries_dev).  frame_row0[u]: the frame row of utterance u's first
+    frame in the entries (default: row0).  Returns status / forward_total / attempts per utterance, cnt (n_states + 1),
+    rows and weights (copied to the host for the caller to look at), sums (per utterance that ran, its frame sums; None
+    for the others), shape (aasr_debug_fb_entries_shape) and pdf_occ_refused: the message with which
+    aasr_fb_batch_result refused the occupancies."""
+    L = lib()
+    o = FbOptions.defaults() if opts is None else opts
+    o.want_pdf_occ = o.device_occ = 1
+    n = len(nets)
+    handles = (C.c_void_p * max(n, 1))(*[h.handle for h in nets])
+    T = np.ascontiguousarray(n_frames, np.int32)
+    r0 = np.ascontiguousarray(row0, np.int64)
+    fr0 = np.ascontiguousarray(row0 if frame_row0 is None else frame_row0, np.int64)
+    b = C.c_void_p()
+    check(L.aasr_fb_batch_create(C.byref(o), n, handles, _ptr(T), C.byref(b)))
+    try:
+        f64 = 1 if str(scores.dtype) == "torch.float64" else 0
+        failed = C.c_int32(0)
+        for attempt in range(1, o.max_attempts + 1):
+            check(L.aasr_fb_batch_dev(b, _ptr(scores), scores.shape[1], scores.shape[0], f64, _ptr(r0), attempt, stream))
+            check(L.aasr_fb_batch_sync(b, stream, C.byref(failed)))
+            if failed.value == 0:
+                break
+        out = {"status": [], "forward_total": [], "attempts": [], "sums": []}
+        cnt = np.zeros(n_states + 1, np.int64)
+        d_rows, d_w = C.c_void_p(), C.c_void_p()
+        check(L.aasr_fb_batch_entries_dev(b, n_states, _ptr(fr0), stream, _ptr(cnt), C.byref(d_rows), C.byref(d_w)))
+        total = int(cnt[-1])
+        rows, weights = np.zeros(total, np.int32), np.zeros(total, np.float64)
+        check(L.aasr_fb_batch_entries_host(b, _ptr(rows), _ptr(weights)))
+        for u in range(n):
+            st, at, ft = C.c_int32(), C.c_int32(), C.c_double()
+            check(L.aasr_fb_batch_result(b, u, C.byref(st), None, C.byref(ft), C.byref(at), None, None))
+            out["status"].append(st.value)
+            out["forward_total"].append(ft.value)
+            out["attempts"].append(at.value)
+            if st.value == FB_OK:
+                s = np.zeros(int(T[u]), np.float64)
+                check(L.aasr_fb_batch_frame_sums(b, u, _ptr(s)))
+                out["sums"].append(s)
+            else:
+                out["sums"].append(None)
+        occ = np.zeros((int(T[0]), nets[0].counts()["pdfs"]), np.float64)
+        rc = L.aasr_fb_batch_result(b, 0, None, None, None, None, _ptr(occ), None) if n else 0
+        out["pdf_occ_refused"] = (int(rc), L.aasr_last_error().decode()) if rc != 0 else None
+        sh = (C.c_int32 * 5)()
+        L.aasr_debug_fb_entries_shape(b, sh)
+        out["shape"] = {"entries": int(sh[0]), "utterances": int(sh[1]), "sum_groups": int(sh[2]), "count_groups": int(sh[3]),
+                        "fill_groups": int(sh[4])}
+        out.update(cnt=cnt, rows=rows, weights=weights)
         return out
     finally:
         L.aasr_fb_batch_destroy(b)

@@ -3,11 +3,14 @@
 // for many utterances per launch (aasr_run_stats_recipe), dumps as HmmSet::dump_statistics writes them.
 //
 //   stats (-b BASE | -g GK -m MC -p PH) -c CFG -r RECIPE -o OUT --ml [--full-stats] [-t] [-O] [-S SPKC [-U]] [-n]
-//         [-B n -I k] [-i level] [-F f -W f -A f]
+//         [-B n -I k] [-i level] [--networks [-F fw] [-W bw] [-A scale] [-M bw|vit]]
 //
 // --full-stats (an extension of this tool, like --device) collects the full second moments sum gamma x x^T and writes
 // mode-3 dumps, what estimate --mllt reads; pools of more than 127 dimensions are refused with it.
-// Only --ml over .phn files is built: -H (hmmnets), --mmi / --mpe / --grad, --mllt, -P, --savelat,
+// --networks is the reference's -H under a spelling of its own: Baum-Welch (or with -M vit Viterbi) over the recipe's
+// hmmnet= networks on the device, with -F / -W / -A honoured; -M mpv, --full-stats and -O are refused with it, and a
+// recipe line without hmmnet= is the reference's error.  Without it -F / -W / -A / -M are read and ignored, as before.
+// Built: --ml over .phn files or networks.  -H itself (use --networks), --mmi / --mpe / --grad, --mllt, -P, --savelat,
 // -a and --nseggk / --nsegmc are refused before the device is opened, and so are full-covariance or
 // subspace pools and speaker files with model transforms.
 #include <cstdio>
@@ -22,7 +25,7 @@
 
 int main(int argc, char *argv[]) {
   aku::conf::Config config;
-  config("usage: stats [OPTION...] --ml [--full-stats]\n")
+  config("usage: stats [OPTION...] --ml [--full-stats | --networks]\n")
     ('h', "help", "", "", "display help")
     ('b', "base=BASENAME", "arg", "", "base filename for model files")
     ('g', "gk=FILE", "arg", "", "Mixture base distributions")
@@ -59,7 +62,8 @@ int main(int argc, char *argv[]) {
     ('I', "bindex=INT", "arg", "0", "batch process index")
     ('i', "info=INT", "arg", "0", "info level")
     ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)")
-    ('\0', "full-stats", "", "", "collect full second moments (mode-3 dumps, what estimate --mllt reads)");
+    ('\0', "full-stats", "", "", "collect full second moments (mode-3 dumps, what estimate --mllt reads)")
+    ('\0', "networks", "", "", "Baum-Welch over the recipe's hmmnet= networks; the reference's -H");
   config.default_parse(argc, argv);
 
   // what this build does not do, refused before anything is read
@@ -74,7 +78,17 @@ int main(int argc, char *argv[]) {
                               {"nseggk", "--nseggk (numerator segmentation model)"},
                               {"nsegmc", "--nsegmc (numerator segmentation model)"}};
   for (const auto &r : refused)
-    if (config[r[0]].specified) die(std::string("stats: ") + r[1] + " is not supported; only --ml over .phn files is");
+    if (config[r[0]].specified)
+      die(std::string("stats: ") + r[1] + " is not supported; only --ml over .phn files is" +
+          (std::string(r[0]) == "hmmnet" ? ", and over HMM networks with --networks" : ""));
+  const bool networks = config["networks"].specified;
+  const std::string segmode = config["segmode"].get_str();
+  if (networks) {
+    if (segmode == "mpv") die("stats: -M mpv (multipath Viterbi) is not supported with --networks; use -M bw or -M vit");
+    if (segmode != "bw" && segmode != "vit") die("stats: -M " + segmode + ": invalid segmentation mode (bw, vit)");
+    if (config["full-stats"].specified) die("stats: --full-stats is not supported with --networks");
+    if (config["ophn"].specified) die("stats: -O (output phns) is not supported with --networks");
+  }
 
   std::string gk, mc, ph;
   resolve_model_files(config, &gk, &mc, &ph);
@@ -92,6 +106,8 @@ int main(int argc, char *argv[]) {
   if (config["speakers"].specified) check_speakers(config["speakers"].get_str(), "stats");
   check_recipe_line_limits(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int(), false,
                            "stats");
+  if (networks)
+    check_recipe_hmmnets(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int(), false);
 
   const int device = config["device"].get_int();
   if (device >= 0 && aasr_set_device(device) != AASR_OK) die(aasr_last_error());
@@ -118,6 +134,13 @@ int main(int argc, char *argv[]) {
   opt.num_batches = config["batch"].get_int();
   opt.batch_index = config["bindex"].get_int();
   opt.full_stats = config["full-stats"].specified;
+  aasr_stats_network_options nopt;
+  aasr_stats_network_default_options(&nopt);
+  nopt.viterbi = segmode == "vit";
+  nopt.fw_beam = config["fw-beam"].get_float();
+  nopt.bw_beam = config["bw-beam"].get_float();
+  nopt.ac_scale = config["ac-scale"].get_float();
+  nopt.ac_scale_given = config["ac-scale"].specified;
   const std::string out = config["out"].get_str();
   opt.out = out.c_str();
   aasr_spkc *spk = nullptr;
@@ -128,7 +151,9 @@ int main(int argc, char *argv[]) {
   opt.speakers = spk;
   aasr_run_stats st;
   memset(&st, 0, sizeof st);
-  if (aasr_run_stats_recipe(feat, gmm, topo, config["recipe"].get_str().c_str(), &opt, &st) != AASR_OK)
+  const std::string recipe = config["recipe"].get_str();
+  if ((networks ? aasr_run_stats_networks_recipe(feat, gmm, topo, recipe.c_str(), &opt, &nopt, &st)
+                : aasr_run_stats_recipe(feat, gmm, topo, recipe.c_str(), &opt, &st)) != AASR_OK)
     die(aasr_last_error());
   aasr_spkc_destroy(spk);
   aasr_topo_destroy(topo);

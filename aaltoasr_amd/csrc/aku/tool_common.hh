@@ -66,9 +66,9 @@ static inline void check_speakers(const std::string &path, const std::string &to
   }
 }
 
-// recipe lines with start-line / end-line, refused as the drivers refuse them
-static inline void check_recipe_line_limits(const std::string &path, int num_batches, int batch_index,
-                                            bool cluster_speakers, const std::string &tool) {
+// the recipe's lines of this batch as aasr_recipe_read_all gives them: 13 fields a line
+static inline std::vector<std::vector<std::string>> recipe_lines(const std::string &path, int num_batches, int batch_index,
+                                                                 bool cluster_speakers) {
   std::ifstream in(path);
   if (!in) die("could not open " + path);
   std::stringstream ss;
@@ -79,6 +79,7 @@ static inline void check_recipe_line_limits(const std::string &path, int num_bat
     die(aasr_last_error());
   const std::string t(table, (size_t)len);
   aasr_free(table);
+  std::vector<std::vector<std::string>> out;
   std::istringstream lines(t);
   std::string line;
   while (std::getline(lines, line)) {
@@ -90,9 +91,23 @@ static inline void check_recipe_line_limits(const std::string &path, int num_bat
       if (b == std::string::npos) break;
       a = b + 1;
     }
+    out.push_back(fl);
+  }
+  return out;
+}
+
+// recipe lines with start-line / end-line, refused as the drivers refuse them
+static inline void check_recipe_line_limits(const std::string &path, int num_batches, int batch_index,
+                                            bool cluster_speakers, const std::string &tool) {
+  for (const std::vector<std::string> &fl : recipe_lines(path, num_batches, batch_index, cluster_speakers))
     if (fl.size() == 13 && (atoi(fl[9].c_str()) > 0 || atoi(fl[10].c_str()) > 0))
       die(tool + ": recipe line limits (start-line / end-line) are not supported");
-  }
+}
+
+// a network tool's recipe: every line names its hmmnet= file (Recipe::Info::init_hmmnet_files, Recipe.cc:198-231)
+static inline void check_recipe_hmmnets(const std::string &path, int num_batches, int batch_index, bool cluster_speakers) {
+  for (const std::vector<std::string> &fl : recipe_lines(path, num_batches, batch_index, cluster_speakers))
+    if (fl.size() == 13 && fl[4].empty()) die("Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
 }
 
 #endif

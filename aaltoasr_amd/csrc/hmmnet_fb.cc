@@ -1,7 +1,9 @@
 // hmmnet_fb.cc -- the handle of the forward-backward pass over HMM networks (aasr_fb_batch_*): packs the
 // utterances' networks (hmmnet.h) into the blobs of hmmnet_fb.h, launches k_hmmnet_fb over the batch, and
 // relaunches the utterances whose backward pass missed the initial node with a wider backward beam
-// (aku/logl.cc:183-199: 2x, 3x, ... the original, the forward beam unchanged).
+// (aku/logl.cc:183-199: 2x, 3x, ... the original, the forward beam unchanged).  With device_occ the occupancies stay on
+// the device and aasr_fb_batch_entries_dev turns them into the weighted entries of the statistics accumulation
+// (fb_entries.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "fb_entries.h"
 #include "hmmnet.h"
 #include "hmmnet_fb.h"
 
@@ -33,6 +36,21 @@ struct aasr_fb_batch {
   int64_t bytes = 0;
   // the last launch (aasr_debug_fb_shape): utterances, 1 = LDS node vectors / 0 = global, LDS bytes, attempt
   int32_t last_shape[4] = {0, 0, 0, 0};
+  // the entries of the last aasr_fb_batch_entries_dev call (fb_entries.h)
+  std::vector<FbEntryUtt> e_utt;
+  std::vector<FbEntryPair> e_pairs;
+  std::vector<int32_t> e_counts, e_index;  // entries per pair; per utterance its place in e_utt, -1: not covered
+  std::vector<int64_t> e_out;
+  std::vector<double> e_sums;  // host copy of the frame sums, fetched by the first aasr_fb_batch_frame_sums
+  bool e_built = false, e_sums_fetched = false;
+  hipStream_t e_stream = nullptr;
+  DevBuf<FbEntryUtt> d_e_utt;
+  DevBuf<FbEntryPair> d_e_pairs;
+  DevBuf<int32_t> d_e_counts, d_e_rows;
+  DevBuf<int64_t> d_e_out;
+  DevBuf<double> d_e_sums, d_e_weights;
+  // aasr_debug_fb_entries_shape: entries, utterances covered, workgroups of the sum, count and fill kernels
+  int32_t entries_shape[5] = {0, 0, 0, 0, 0};
 };
 
 extern "C" {
@@ -156,10 +174,12 @@ aasr_status aasr_fb_batch_create(const aasr_fb_options *opt, int32_t n_utt, cons
     b->d_work.alloc((size_t)std::max<int64_t>(1, work));
     if (opt->want_pdf_occ) b->d_occ.alloc((size_t)std::max<int64_t>(1, occ));
     if (opt->want_tr_occ) b->d_trocc.alloc((size_t)std::max<int64_t>(1, trocc));
-    b->occ.assign(opt->want_pdf_occ ? (size_t)occ : 0, 0.0);
+    if (opt->device_occ && !opt->want_pdf_occ)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_create: device_occ without want_pdf_occ");
+    b->occ.assign(opt->want_pdf_occ && !opt->device_occ ? (size_t)occ : 0, 0.0);
     b->trocc.assign(opt->want_tr_occ ? (size_t)trocc : 0, 0.0);
     b->result.assign((size_t)n_utt, FbResult{FB_ZERO, FB_ZERO, 0, 0});
-    b->bytes = (int64_t)(ints.size() * 4 + doubles.size() * 8 + (size_t)work * 8 + b->occ.size() * 8 + b->trocc.size() * 8 +
+    b->bytes = (int64_t)(ints.size() * 4 + doubles.size() * 8 + (size_t)work * 8 + (opt->want_pdf_occ ? (size_t)occ : 0) * 8 + b->trocc.size() * 8 +
                          nu * (sizeof(FbUttDev) + sizeof(FbResult) + 4));
     *out = b.release();
   });
@@ -182,6 +202,7 @@ aasr_status aasr_fb_batch_dev(aasr_fb_batch *b, const void *d_state_loglik, int6
     if (attempt < 1 || attempt > b->opt.max_attempts)
       raise(AASR_ERR_INVALID, "aasr_fb_batch_dev: attempt %d outside 1 .. %d", attempt, b->opt.max_attempts);
     const hipStream_t st = (hipStream_t)stream;
+    b->e_built = b->e_sums_fetched = false;  // (entries of an earlier pass describe occupancies this one rewrites)
     b->list.clear();
     for (int u = 0; u < b->n; u++) {
       const aasr_hmmnet &h = *b->nets[(size_t)u];
@@ -260,6 +281,9 @@ aasr_status aasr_fb_batch_result(const aasr_fb_batch *b, int32_t u, int32_t *sta
     if (attempts) *attempts = r.attempts;
     if (pdf_occ) {
       if (!b->opt.want_pdf_occ) raise(AASR_ERR_INVALID, "aasr_fb_batch_result: the batch was created without pdf occupancies");
+      if (b->opt.device_occ)
+        raise(AASR_ERR_INVALID, "aasr_fb_batch_result: the batch keeps its pdf occupancies on the device (device_occ); "
+                                "use aasr_fb_batch_entries_dev");
       if (r.status == FB_OK) std::copy(b->occ.begin() + d.occ, b->occ.begin() + d.occ + (int64_t)d.T * d.net.n_pdf, pdf_occ);
     }
     if (tr_occ) {
@@ -267,6 +291,127 @@ aasr_status aasr_fb_batch_result(const aasr_fb_batch *b, int32_t u, int32_t *sta
       if (r.status == FB_OK) std::copy(b->trocc.begin() + d.trocc, b->trocc.begin() + d.trocc + d.net.n_tr, tr_occ);
     }
   });
+}
+
+aasr_status aasr_fb_batch_entries_dev(aasr_fb_batch *b, int32_t n_states, const int64_t *row0, void *stream, int64_t *cnt,
+                                      const int32_t **d_rows, const double **d_weights) {
+  return guarded([&] {
+    if (!b || n_states < 0 || (b->n > 0 && !row0) || !cnt || !d_rows || !d_weights)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_dev: bad argument");
+    if (!b->opt.want_pdf_occ || !b->opt.device_occ)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_dev: the batch was created without device_occ");
+    const hipStream_t st = (hipStream_t)stream;
+    *d_rows = nullptr;
+    *d_weights = nullptr;
+    b->e_built = b->e_sums_fetched = false;
+    b->e_utt.clear();
+    b->e_pairs.clear();
+    b->e_index.assign((size_t)b->n, -1);
+    // the utterances that ran, and their (pdf, utterance) pairs ordered by global pdf, then by utterance
+    std::vector<std::pair<int32_t, FbEntryPair>> keyed;
+    int64_t sums = 0;
+    int32_t max_T = 0;
+    for (int u = 0; u < b->n; u++) {
+      if (b->result[(size_t)u].status != FB_OK) continue;
+      const FbUttDev &d = b->utt[(size_t)u];
+      const aasr_hmmnet &h = *b->nets[(size_t)u];
+      if (row0[u] < 0 || row0[u] + d.T > (int64_t)INT32_MAX)
+        raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_dev: utterance %d has frame rows %lld .. %lld, outside 0 .. 2^31", u,
+              (long long)row0[u], (long long)(row0[u] + d.T));
+      b->e_index[(size_t)u] = (int32_t)b->e_utt.size();
+      for (int32_t j = 0; j < (int32_t)h.pdfs.size(); j++) {
+        if (h.pdfs[(size_t)j] < 0 || h.pdfs[(size_t)j] >= n_states)
+          raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_dev: utterance %d uses pdf %d, the model has %d", u, h.pdfs[(size_t)j],
+                n_states);
+        keyed.push_back({h.pdfs[(size_t)j], FbEntryPair{(int32_t)b->e_utt.size(), j}});
+      }
+      b->e_utt.push_back(FbEntryUtt{d.occ, sums, row0[u], d.T, d.net.n_pdf});
+      sums += d.T;
+      max_T = std::max(max_T, d.T);
+    }
+    std::stable_sort(keyed.begin(), keyed.end(),
+                     [](const std::pair<int32_t, FbEntryPair> &a, const std::pair<int32_t, FbEntryPair> &c) { return a.first < c.first; });
+    for (const auto &k : keyed) b->e_pairs.push_back(k.second);
+    const int32_t n_utt = (int32_t)b->e_utt.size(), n_pairs = (int32_t)b->e_pairs.size();
+    std::fill(cnt, cnt + (size_t)n_states + 1, (int64_t)0);
+    std::fill(b->entries_shape, b->entries_shape + 5, 0);
+    b->entries_shape[1] = n_utt;
+    b->e_out.assign((size_t)n_pairs + 1, 0);
+    b->e_sums.assign((size_t)sums, 0.0);
+    b->e_stream = st;
+    if (n_pairs == 0) {
+      b->e_built = true;
+      return;
+    }
+    b->d_e_utt.ensure((size_t)n_utt);
+    b->d_e_pairs.ensure((size_t)n_pairs);
+    b->d_e_counts.ensure((size_t)n_pairs);
+    b->d_e_out.ensure((size_t)n_pairs + 1);
+    b->d_e_sums.ensure((size_t)sums);
+    AASR_HIP(hipMemcpyAsync(b->d_e_utt.p, b->e_utt.data(), (size_t)n_utt * sizeof(FbEntryUtt), hipMemcpyHostToDevice, st));
+    AASR_HIP(hipMemcpyAsync(b->d_e_pairs.p, b->e_pairs.data(), (size_t)n_pairs * sizeof(FbEntryPair), hipMemcpyHostToDevice, st));
+    fb_frame_sums_launch(b->d_e_utt.p, n_utt, max_T, b->d_occ.p, b->d_e_sums.p, st);
+    fb_entry_counts_launch(b->d_e_utt.p, b->d_e_pairs.p, n_pairs, b->d_occ.p, b->d_e_counts.p, st);
+    // the one fetch and the one wait of the call: the entries of every pair
+    b->e_counts.assign((size_t)n_pairs, 0);
+    AASR_HIP(hipMemcpyAsync(b->e_counts.data(), b->d_e_counts.p, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AASR_HIP(hipStreamSynchronize(st));
+    for (int32_t q = 0; q < n_pairs; q++) {
+      if (b->e_counts[(size_t)q] < 0 || b->e_counts[(size_t)q] > b->e_utt[(size_t)b->e_pairs[(size_t)q].utt].T)
+        raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_dev: pair %d reports %d entries", q, b->e_counts[(size_t)q]);
+      b->e_out[(size_t)q + 1] = b->e_out[(size_t)q] + b->e_counts[(size_t)q];
+      cnt[(size_t)keyed[(size_t)q].first + 1] += b->e_counts[(size_t)q];
+    }
+    for (int32_t s = 0; s < n_states; s++) cnt[(size_t)s + 1] += cnt[(size_t)s];
+    const int64_t total = b->e_out[(size_t)n_pairs];
+    if (total > (int64_t)INT32_MAX) raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_dev: more than 2^31 entries in one batch");
+    b->d_e_rows.ensure((size_t)std::max<int64_t>(1, total));
+    b->d_e_weights.ensure((size_t)std::max<int64_t>(1, total));
+    AASR_HIP(hipMemcpyAsync(b->d_e_out.p, b->e_out.data(), b->e_out.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    fb_entry_fill_launch(b->d_e_utt.p, b->d_e_pairs.p, n_pairs, b->d_occ.p, b->d_e_sums.p, b->d_e_out.p, b->d_e_rows.p,
+                         b->d_e_weights.p, st);
+    b->entries_shape[0] = (int32_t)total;
+    b->entries_shape[2] = ((max_T + FBE_THREADS - 1) / FBE_THREADS) * n_utt;
+    b->entries_shape[3] = b->entries_shape[4] = (n_pairs + FBE_THREADS - 1) / FBE_THREADS;
+    b->e_built = true;
+    *d_rows = b->d_e_rows.p;
+    *d_weights = b->d_e_weights.p;
+  });
+}
+
+aasr_status aasr_fb_batch_entries_host(aasr_fb_batch *b, int32_t *rows, double *weights) {
+  return guarded([&] {
+    if (!b) raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_host: null argument");
+    if (!b->e_built) raise(AASR_ERR_INVALID, "aasr_fb_batch_entries_host: call aasr_fb_batch_entries_dev first");
+    const size_t total = (size_t)b->e_out.back();
+    if (total == 0) return;
+    if (rows) AASR_HIP(hipMemcpyAsync(rows, b->d_e_rows.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, b->e_stream));
+    if (weights) AASR_HIP(hipMemcpyAsync(weights, b->d_e_weights.p, total * sizeof(double), hipMemcpyDeviceToHost, b->e_stream));
+    AASR_HIP(hipStreamSynchronize(b->e_stream));
+  });
+}
+
+aasr_status aasr_fb_batch_frame_sums(aasr_fb_batch *b, int32_t u, double *sums) {
+  return guarded([&] {
+    if (!b || u < 0 || u >= b->n || !sums) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_sums: bad argument");
+    if (!b->e_built) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_sums: call aasr_fb_batch_entries_dev first");
+    const int32_t e = b->e_index[(size_t)u];
+    if (e < 0) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_sums: utterance %d did not run (status %d)", u, b->result[(size_t)u].status);
+    if (!b->e_sums_fetched) {  // every covered utterance's sums in one copy, on the stream that computed them
+      if (!b->e_sums.empty()) {
+        AASR_HIP(hipMemcpyAsync(b->e_sums.data(), b->d_e_sums.p, b->e_sums.size() * sizeof(double), hipMemcpyDeviceToHost, b->e_stream));
+        AASR_HIP(hipStreamSynchronize(b->e_stream));
+      }
+      b->e_sums_fetched = true;
+    }
+    const FbEntryUtt &eu = b->e_utt[(size_t)e];
+    std::copy(b->e_sums.begin() + eu.sums, b->e_sums.begin() + eu.sums + eu.T, sums);
+  });
+}
+
+void aasr_debug_fb_entries_shape(const aasr_fb_batch *b, int32_t *out) {
+  if (!b || !out) return;
+  std::copy(b->entries_shape, b->entries_shape + 5, out);
 }
 
 }  // extern "C"

@@ -8,7 +8,6 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -146,13 +145,10 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
     if (opt->bw_beam > 0) fo.bw_beam = opt->bw_beam;
     if (opt->ac_scale_given) fo.ac_scale = opt->ac_scale;
     fo.mode = opt->vit ? AASR_FB_VITERBI : AASR_FB_BAUM_WELCH;
-    const int S = aasr_gmm_num_states(gmm), D = aasr_gmm_dim(gmm);
+    const int S = aasr_gmm_num_states(gmm);
     const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
-    std::map<std::string, std::unique_ptr<aasr_hmmnet, void (*)(aasr_hmmnet *)>> net_cache;
-    DevBuf<double> d_scores64;
-    DevBuf<float> d_scores32, d_x32;
-    std::vector<double> x64;
-    std::vector<float> x32;
+    NetworkCache net_cache(topo, S);
+    GroupScores scores;
     size_t next = 0;
     while (next < infos.size()) {
       double t = now_s();
@@ -169,28 +165,12 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
         if (!opt->den_hmmnet && u.hmmnet_path.empty())
           raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
         const std::string &path = opt->den_hmmnet ? u.den_hmmnet_path : u.hmmnet_path;
-        auto it = net_cache.find(path);
-        if (it == net_cache.end()) {
-          aasr_hmmnet *net = nullptr;
-          const aasr_status rs = aasr_hmmnet_read(topo, path.c_str(), &net);
-          if (rs != AASR_OK) raise(rs, "%s", last_error().c_str());
-          it = net_cache.emplace(path, std::unique_ptr<aasr_hmmnet, void (*)(aasr_hmmnet *)>(net, aasr_hmmnet_destroy)).first;
-        }
-        for (int32_t pdf : it->second->pdfs)
-          if (pdf >= S) raise(AASR_ERR_INVALID, "%s: state %d is not below the model's %d states", path.c_str(), pdf, S);
-        group_nets.push_back(it->second.get());
-        // the frame limits (Recipe.cc:223-228, HmmNetBaumWelch::generate_features): first .. last, or to the last frame
-        // of the audio; a limit past the audio is cut to it
-        int first, last;
-        frame_range(u, fr, &first, &last);
-        const int eof = aasr_feat_eof_frame(feat, (int64_t)audio.back().size());
-        const int end = last > 0 ? std::min(last, eof) : eof;
-        if (end - first < 1)
-          raise(AASR_ERR_INVALID, "HmmNetBaumWelch: no frames for %s (frames %d to %d)", u.audio_path.c_str(), first, end);
-        if (end - first == 1) fprintf(stderr, "HmmNetBaumWelch: Warning: Single frame utterance\n");
+        group_nets.push_back(net_cache.get(path));
+        int first, n;
+        network_frame_range(u, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), &first, &n);
         start.push_back(first);
-        rows.push_back(end - first);
-        rows_total += end - first;
+        rows.push_back(n);
+        rows_total += n;
       }
       t_host += now_s() - t;
       t = now_s();
@@ -199,25 +179,7 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
       t_feat += now_s() - t;
       t = now_s();
       check_stats_model(gmm, "logl");
-      const void *d_rows = nullptr;
-      if (f64) {
-        d_scores64.ensure((size_t)rows_total * S);
-        if (aasr_gmm_score_f64_dev(gmm, stager.d_x.p, rows_total, d_scores64.p, stream) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        d_rows = d_scores64.p;
-      } else {
-        // the scoring entry of the default mode takes float frames
-        x64.resize((size_t)rows_total * D);
-        AASR_HIP(hipMemcpyAsync(x64.data(), stager.d_x.p, x64.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        AASR_HIP(hipStreamSynchronize(stream));
-        x32.assign(x64.begin(), x64.end());
-        d_x32.ensure(x32.size());
-        d_scores32.ensure((size_t)rows_total * S);
-        AASR_HIP(hipMemcpyAsync(d_x32.p, x32.data(), x32.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (aasr_gmm_score_dev(gmm, d_x32.p, rows_total, d_scores32.p, stream) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        d_rows = d_scores32.p;
-      }
+      const void *d_rows = scores.score(gmm, stager.d_x.p, rows_total, f64, stream);
       if (timing) AASR_HIP(hipStreamSynchronize(stream));
       t_score += now_s() - t;
       t = now_s();

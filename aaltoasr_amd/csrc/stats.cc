@@ -1,8 +1,10 @@
 // stats.cc -- ML statistics collection (aku/stats.cc with --ml over .phn segmentations): the statistics
 // handle that drives the device accumulation (stats_accum.hip), the dump writers of
 // HmmSet::dump_statistics and the stats main loop over a recipe (aasr_run_stats_recipe,
-// stats.cc:73-170, 540-620, 740-795).  The segmentation reader is recipe_pass.cc's.  A handle made by
-// aasr_stats_create_full also collects the full second moments (stats_full_accum.hip) and dumps mode 3.
+// stats.cc:73-170, 540-620, 740-795) over .phn segmentations, or with aasr_run_stats_networks_recipe Baum-Welch over
+// the recipe's HMM networks (hmmnet_fb.hip, fb_entries.hip, stats_weighted.hip).  The segmentation reader is
+// recipe_pass.cc's.  A handle made by aasr_stats_create_full also collects the full second moments
+// (stats_full_accum.hip) and dumps mode 3.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +19,8 @@
 
 #include "common.h"
 #include "gmm.h"
+#include "hmmnet.h"
+#include "hmmnet_fb.h"
 #include "recipe_pass.h"
 #include "stats.h"
 #include "stats_full.h"
@@ -106,6 +110,33 @@ static void stats_launch_shape(int max_comps, int rec, int32_t *block, int32_t *
     raise(AASR_ERR_UNSUPPORTED, "stats: mixtures of %d components exceed the accumulation kernel's LDS", max_comps);
   *block = b;
   *lds_recs = (size_t)(b * (max_comps + 2) + max_comps * rec) * 8 + (size_t)b * 8 <= 64 * 1024 ? 1 : 0;
+}
+
+// The work items of a call from the first entry of every pdf in its row list (cnt, S + 1 entries): per pdf with entries
+// items of at most STATS_CHUNK of them, the pdfs that have items and their first item -> the doubles of the slabs.
+static int64_t stats_build_items(aasr_stats *h, const std::vector<int64_t> &cnt) {
+  h->h_items.clear();
+  h->h_pdfs.clear();
+  h->h_item_begin.assign(1, 0);
+  int64_t slab_total = 0;
+  for (int s = 0; s < h->S; s++) {
+    const int64_t c = cnt[(size_t)s + 1] - cnt[(size_t)s];
+    const int M = h->mix_off[(size_t)s + 1] - h->mix_off[(size_t)s];
+    if (c == 0) continue;  // (a mixture without components still gets its items: total 0, safe_log(0) per frame)
+    const int64_t pieces = (c + STATS_CHUNK - 1) / STATS_CHUNK, per = (c + pieces - 1) / pieces;
+    for (int64_t b = 0; b < c; b += per) {
+      StatsItem it;
+      it.row_begin = cnt[(size_t)s] + b;
+      it.n = (int32_t)std::min(per, c - b);
+      it.pdf = s;
+      it.slab = slab_total;
+      slab_total += (int64_t)M * h->W + 2;
+      h->h_items.push_back(it);
+    }
+    h->h_pdfs.push_back(s);
+    h->h_item_begin.push_back((int32_t)h->h_items.size());
+  }
+  return slab_total;
 }
 
 // The full second moments of a call whose row list (grouped by pdf, cnt[s] the first entry of pdf s) is on its way to
@@ -311,27 +342,7 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
     // frames grouped by pdf (frame order within a pdf), cut into items of at most STATS_CHUNK frames
     std::vector<int64_t> cnt;
     rows_by_pdf("aasr_stats_accumulate_dev", h->S, pdf, n_frames, &cnt, &h->h_rows);
-    h->h_items.clear();
-    h->h_pdfs.clear();
-    h->h_item_begin.assign(1, 0);
-    int64_t slab_total = 0;
-    for (int s = 0; s < h->S; s++) {
-      const int64_t c = cnt[(size_t)s + 1] - cnt[(size_t)s];
-      const int M = h->mix_off[(size_t)s + 1] - h->mix_off[(size_t)s];
-      if (c == 0) continue;  // (a mixture without components still gets its items: total 0, safe_log(0) per frame)
-      const int64_t pieces = (c + STATS_CHUNK - 1) / STATS_CHUNK, per = (c + pieces - 1) / pieces;
-      for (int64_t b = 0; b < c; b += per) {
-        StatsItem it;
-        it.row_begin = cnt[(size_t)s] + b;
-        it.n = (int32_t)std::min(per, c - b);
-        it.pdf = s;
-        it.slab = slab_total;
-        slab_total += (int64_t)M * h->W + 2;
-        h->h_items.push_back(it);
-      }
-      h->h_pdfs.push_back(s);
-      h->h_item_begin.push_back((int32_t)h->h_items.size());
-    }
+    const int64_t slab_total = stats_build_items(h, cnt);
     if (h->h_items.empty()) return;
     std::vector<FullLaunch> full_launches;
     if (h->full) full_launches = stats_full_prepare(h, cnt);
@@ -366,6 +377,58 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
     stats_pdf_reduce_launch(h->d_pdfs.p, h->d_item_begin.p, (int)h->h_pdfs.size(), h->d_items.p, h->slab.p,
                             h->gmm->f64_state_off.p, h->D, h->racc.p, h->pacc.p, st);
     if (h->full) stats_full_pass(h, d_frames, full_launches, st);
+    h->fetched = false;
+  });
+}
+
+aasr_status aasr_stats_accumulate_weighted_dev(aasr_stats *h, const double *d_frames, int64_t n_frames, const int64_t *cnt,
+                                               const int32_t *d_rows, const double *d_weights, void *stream) {
+  return guarded([&] {
+    if (!h || n_frames < 0 || !cnt) raise(AASR_ERR_INVALID, "aasr_stats_accumulate_weighted_dev: bad argument");
+    if (h->full)  // (before anything is queued)
+      raise(AASR_ERR_UNSUPPORTED, "aasr_stats_accumulate_weighted_dev: full second moments are not collected from weighted "
+                                  "entries (a handle of aasr_stats_create_full)");
+    if (n_frames > INT32_MAX) raise(AASR_ERR_INVALID, "aasr_stats_accumulate_weighted_dev: more than 2^31 frames in one call");
+    if (cnt[0] != 0) raise(AASR_ERR_INVALID, "aasr_stats_accumulate_weighted_dev: cnt[0] is %lld, not 0", (long long)cnt[0]);
+    for (int s = 0; s < h->S; s++)
+      if (cnt[s + 1] < cnt[s]) raise(AASR_ERR_INVALID, "aasr_stats_accumulate_weighted_dev: cnt decreases at pdf %d", s);
+    const int64_t entries = cnt[h->S];
+    if (entries > INT32_MAX) raise(AASR_ERR_INVALID, "aasr_stats_accumulate_weighted_dev: more than 2^31 entries in one call");
+    if (entries == 0) return;
+    if (!d_frames || !d_rows || !d_weights || n_frames == 0)
+      raise(AASR_ERR_INVALID, "aasr_stats_accumulate_weighted_dev: %lld entries without frames, rows or weights", (long long)entries);
+    const hipStream_t st = (hipStream_t)stream;
+    if (h->staged_pending) AASR_HIP(hipEventSynchronize(h->staged));
+    h->staged_pending = false;
+    const int64_t slab_total = stats_build_items(h, std::vector<int64_t>(cnt, cnt + h->S + 1));
+    if (h->h_items.empty()) return;
+    StatsParams p{};
+    p.max_comps = h->max_comps;
+    p.rec = h->rec;
+    stats_launch_shape(p.max_comps, p.rec, &p.block, &p.lds_recs);
+    h->d_items.ensure(h->h_items.size());
+    h->d_pdfs.ensure(h->h_pdfs.size());
+    h->d_item_begin.ensure(h->h_item_begin.size());
+    h->slab.ensure((size_t)slab_total);
+    AASR_HIP(hipMemcpyAsync(h->d_items.p, h->h_items.data(), h->h_items.size() * sizeof(StatsItem), hipMemcpyHostToDevice, st));
+    AASR_HIP(hipMemcpyAsync(h->d_pdfs.p, h->h_pdfs.data(), h->h_pdfs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    AASR_HIP(hipMemcpyAsync(h->d_item_begin.p, h->h_item_begin.data(), h->h_item_begin.size() * sizeof(int32_t),
+                            hipMemcpyHostToDevice, st));
+    AASR_HIP(hipEventRecord(h->staged, st));
+    h->staged_pending = true;
+    p.x = d_frames;
+    p.dim = h->D;
+    p.rows = d_rows;
+    p.items = h->d_items.p;
+    p.recs = h->gmm->f64_recs.p;
+    p.state_off = h->gmm->f64_state_off.p;
+    p.slab = h->slab.p;
+    p.frame_ll = nullptr;
+    const int32_t shape[5] = {h->dimp, p.block, p.lds_recs, p.max_comps, (int32_t)h->h_items.size()};
+    std::copy(shape, shape + 5, h->last_shape);
+    stats_items_w_launch(p, d_weights, n_frames, h->dimp, (int)h->h_items.size(), st);
+    stats_pdf_reduce_launch(h->d_pdfs.p, h->d_item_begin.p, (int)h->h_pdfs.size(), h->d_items.p, h->slab.p,
+                            h->gmm->f64_state_off.p, h->D, h->racc.p, h->pacc.p, st);
     h->fetched = false;
   });
 }
@@ -679,14 +742,182 @@ void aasr_stats_default_options(aasr_stats_options *o) {
 
 // ---- the stats main loop over a recipe ---------------------------------------------------------
 
-extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
-                                             const char *recipe_path, const aasr_stats_options *opt,
-                                             aasr_run_stats *stats) {
+// ---- Baum-Welch over the recipe's HMM networks (aku/stats.cc with -H) ----------------------------
+
+namespace {
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// The network mode of aasr_run_stats_recipe: per group the steps of logl.cc's network branch, then the occupancies as
+// weighted entries into the accumulation.  -> total_ll, num_frames of the utterances that ran
+void run_stats_networks(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const std::vector<RecipeInfo> &infos,
+                        const aasr_stats_options *opt, const aasr_stats_network_options *nopt, aasr_stats *h,
+                        GroupStager &stager, double *total_ll, int64_t *num_frames) {
+  const hipStream_t stream = stager.stream;
+  const bool accumulate = !opt->no_train, transitions = opt->transitions != 0;
+  const bool timing = getenv("AASR_RECIPE_TIMING") != nullptr;
+  double t_host = 0, t_feat = 0, t_score = 0, t_fb = 0, t_acc = 0;
+  aasr_fb_options fo;
+  aasr_fb_default_options(&fo);
+  if (nopt->fw_beam > 0) fo.fw_beam = nopt->fw_beam;  // set_pruning_thresholds: 0 keeps the default
+  if (nopt->bw_beam > 0) fo.bw_beam = nopt->bw_beam;
+  if (nopt->ac_scale_given) fo.ac_scale = nopt->ac_scale;
+  fo.mode = nopt->viterbi ? AASR_FB_VITERBI : AASR_FB_BAUM_WELCH;
+  fo.want_pdf_occ = 1;
+  fo.device_occ = 1;
+  fo.want_tr_occ = transitions ? 1 : 0;
+  const int S = aasr_gmm_num_states(gmm);
+  const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
+  const float fr = aasr_feat_frame_rate(feat);
+  constexpr int64_t group_frames = (int64_t)1 << 18, group_scores = (int64_t)1 << 27;  // as logl.cc cuts its groups
+  NetworkCache net_cache(topo, S);
+  GroupScores scores;
+  std::vector<int64_t> cnt((size_t)S + 1);
+  std::vector<double> sums, tr_occ;
+  double max_dev = 0;  // max |1 - s_t| over the run
+  int64_t entries = 0;
+  size_t next = 0;
+  while (next < infos.size()) {
+    double t = now_s();
+    const size_t group_first = next;
+    std::vector<std::vector<int16_t>> audio;
+    std::vector<int32_t> start, rows;
+    std::vector<const aasr_hmmnet *> group_nets;
+    int64_t rows_total = 0;
+    while (next < infos.size() && audio.size() < 1024 &&
+           (audio.empty() || (rows_total < group_frames && rows_total * S < group_scores))) {
+      const RecipeInfo &u = infos[next++];
+      announce(u, opt->info);
+      audio.push_back(load_utterance_input(feat, u));
+      // Recipe::Info::init_hmmnet_files (Recipe.cc:198-231)
+      if (u.hmmnet_path.empty()) raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
+      group_nets.push_back(net_cache.get(u.hmmnet_path));
+      int first, n;
+      network_frame_range(u, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), &first, &n);
+      start.push_back(first);
+      rows.push_back(n);
+      rows_total += n;
+    }
+    t_host += now_s() - t;
+    t = now_s();
+    stager.stage(audio, start, rows, [&](size_t i) {
+      if (!opt->speakers) return;
+      const RecipeInfo &u = infos[group_first + i];
+      if (aasr_spkc_set_speaker(opt->speakers, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      if (opt->uttadap && !u.utterance_id.empty() && aasr_spkc_set_utterance(opt->speakers, u.utterance_id.c_str()) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      check_stats_model(gmm);
+    });
+    if (timing) AASR_HIP(hipStreamSynchronize(stream));
+    t_feat += now_s() - t;
+    t = now_s();
+    const void *d_scores = scores.score(gmm, stager.d_x.p, rows_total, f64, stream);
+    if (timing) AASR_HIP(hipStreamSynchronize(stream));
+    t_score += now_s() - t;
+    t = now_s();
+    aasr_fb_batch *b = nullptr;
+    if (aasr_fb_batch_create(&fo, (int32_t)group_nets.size(), group_nets.data(), rows.data(), &b) != AASR_OK)
+      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+    std::unique_ptr<aasr_fb_batch, void (*)(aasr_fb_batch *)> bguard(b, aasr_fb_batch_destroy);
+    std::vector<int64_t> row0;
+    int64_t at = 0;
+    for (int32_t r : rows) {
+      row0.push_back(at);
+      at += r;
+    }
+    // simple_train (aku/stats.cc:79-102): a failed initialisation is run again with 2x ... 5x the backward beam -- new
+    // launches over the failed utterances only
+    int32_t failed = 0;
+    for (int attempt = 1; attempt <= fo.max_attempts; attempt++) {
+      if (aasr_fb_batch_dev(b, d_scores, S, rows_total, f64 ? 1 : 0, row0.data(), attempt, stream) != AASR_OK ||
+          aasr_fb_batch_sync(b, stream, &failed) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      if (failed == 0) break;
+    }
+    const int32_t *d_rows = nullptr;
+    const double *d_weights = nullptr;
+    if (aasr_fb_batch_entries_dev(b, S, row0.data(), stream, cnt.data(), &d_rows, &d_weights) != AASR_OK)
+      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+    entries += cnt[(size_t)S];
+    t_fb += now_s() - t;
+    t = now_s();
+    // the messages in recipe order, and the frame sums: HmmNetBaumWelch::next_frame's sanity check (:772-779)
+    std::vector<char> ran(group_nets.size(), 0);
+    for (size_t i = 0; i < group_nets.size(); i++) {
+      int32_t status = 0, attempts = 0;
+      if (aasr_fb_batch_result(b, (int32_t)i, &status, nullptr, nullptr, &attempts, nullptr, nullptr) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      if (attempts > 1 || status == FB_FAILED_BACKWARD) fprintf(stderr, "Could not initialize the utterance segmentation.\n");
+      for (int k = 2; k <= attempts; k++) fprintf(stderr, "Increasing beam to %.1f\n", k * fo.bw_beam);
+      if (status == FB_FAILED_BACKWARD) {
+        fprintf(stderr, "Giving up for this file\n");
+        continue;
+      }
+      if (status != FB_OK) raise(AASR_ERR_INVALID, "No paths survived to the end of the network!");
+      ran[i] = 1;
+      sums.resize((size_t)rows[i]);
+      if (aasr_fb_batch_frame_sums(b, (int32_t)i, sums.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      for (int32_t f = 0; f < rows[i]; f++) {
+        const double dev = std::fabs(1 - sums[(size_t)f]);
+        if (dev > 0.02) {
+          fprintf(stderr, "Warning: Sum of PDF probabilities is %g at frame %i\n", sums[(size_t)f], start[i] + f);
+          if (sums[(size_t)f] < 0.01)  // (the reference exits here)
+            raise(AASR_ERR_INVALID, "HmmNetBaumWelch: the sum of PDF probabilities is %g at frame %d of %s", sums[(size_t)f],
+                  start[i] + f, infos[group_first + i].audio_path.c_str());
+        }
+        max_dev = std::max(max_dev, dev);
+      }
+    }
+    if (accumulate && cnt[(size_t)S] > 0 &&
+        aasr_stats_accumulate_weighted_dev(h, stager.d_x.p, rows_total, cnt.data(), d_rows, d_weights, stream) != AASR_OK)
+      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+    for (size_t i = 0; i < group_nets.size(); i++) {
+      if (!ran[i]) continue;
+      const aasr_hmmnet &net = *group_nets[i];
+      double fw = 0;
+      tr_occ.assign(std::max<size_t>(1, net.trs.size()), 0.0);
+      if (aasr_fb_batch_result(b, (int32_t)i, nullptr, nullptr, &fw, nullptr, nullptr, transitions ? tr_occ.data() : nullptr) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      if (accumulate && transitions)
+        for (size_t k = 0; k < net.trs.size(); k++) {
+          if (net.trs[k] < 0 || (size_t)net.trs[k] >= h->tr_count.size())
+            raise(AASR_ERR_INVALID, "%s: transition %d is not one of the model's %zu", infos[group_first + i].hmmnet_path.c_str(),
+                  net.trs[k], h->tr_count.size());
+          h->tr_count[(size_t)net.trs[k]] += tr_occ[k];
+        }
+      fprintf(stderr, "  %g\n", fw);  // simple_train: the segmentator's total log-likelihood
+      *total_ll += fw;
+      *num_frames += rows[i];
+    }
+    // the batch owns the entries that the accumulation reads: it goes when the stream is done with them
+    AASR_HIP(hipStreamSynchronize(stream));
+    t_acc += now_s() - t;
+  }
+  if (opt->info > 0) {
+    fprintf(stderr, "Largest |1 - sum of PDF probabilities| of a frame: %g\n", max_dev);
+    fprintf(stderr, "Weighted entries: %lld over %lld frames\n", (long long)entries, (long long)*num_frames);
+  }
+  if (timing)
+    fprintf(stderr,
+            "stats timing: input and networks %.3f s, features %.3f s, scoring %.3f s, forward-backward and entries %.3f s, "
+            "accumulation %.3f s\n",
+            t_host, t_feat, t_score, t_fb, t_acc);
+}
+
+}  // namespace
+
+static aasr_status run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                    const aasr_stats_options *opt, const aasr_stats_network_options *nopt,
+                                    aasr_run_stats *stats) {
   return guarded([&] {
     if (!feat || !gmm || !topo || !recipe_path || !opt || (!opt->no_train && !opt->out))
-      raise(AASR_ERR_INVALID, "aasr_run_stats_recipe: null argument");
+      raise(AASR_ERR_INVALID, "%s: null argument", nopt ? "aasr_run_stats_networks_recipe" : "aasr_run_stats_recipe");
     const auto t0 = std::chrono::steady_clock::now();
     check_feature_dim(gmm, feat);
+    if (nopt && opt->full_stats)
+      raise(AASR_ERR_UNSUPPORTED, "stats: --full-stats is not supported with --networks (full second moments are collected over .phn files only)");
+    if (nopt && opt->ophn)
+      raise(AASR_ERR_UNSUPPORTED, "stats: -O is not supported with --networks (a network line has no segmentation to choose)");
     // stats reads its recipe with cluster_speakers = false (aku/stats.cc:422-424)
     const std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, false);
     refuse_line_limits(infos, "stats");
@@ -707,6 +938,10 @@ extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, con
     // groups of utterances accumulated in one launch; their frames stay on the device
     const int64_t max_group_frames = (int64_t)1 << 20;
     size_t next = 0;
+    if (nopt) {
+      run_stats_networks(feat, gmm, topo, infos, opt, nopt, h, stager, &total_ll, &num_frames);
+      next = infos.size();
+    }
     while (next < infos.size()) {
       // host side first: audio and segmentation, the -i messages in recipe order
       const size_t group_first = next;
@@ -782,3 +1017,25 @@ extern "C" aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, con
     fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
   });
 }
+
+extern "C" {
+
+aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                  const aasr_stats_options *opt, aasr_run_stats *stats) {
+  return run_stats_recipe(feat, gmm, topo, recipe_path, opt, nullptr, stats);
+}
+
+void aasr_stats_network_default_options(aasr_stats_network_options *o) {
+  if (o) memset(o, 0, sizeof *o);
+  if (o) o->ac_scale = 1;
+}
+
+aasr_status aasr_run_stats_networks_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                           const aasr_stats_options *opt, const aasr_stats_network_options *net,
+                                           aasr_run_stats *stats) {
+  aasr_stats_network_options defaults;
+  aasr_stats_network_default_options(&defaults);
+  return run_stats_recipe(feat, gmm, topo, recipe_path, opt, net ? net : &defaults, stats);
+}
+
+}  // extern "C"

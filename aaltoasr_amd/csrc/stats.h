@@ -53,6 +53,11 @@ void check_stats_model(const aasr_gmm *g, const char *tool = "stats");
 
 // per-item partial sums (one workgroup per item)
 void stats_items_launch(const StatsParams &p, int dimp, int n_items, hipStream_t stream);
+// The same with a weight per entry of the row list (stats_weighted.hip): Mixture::accumulate with gamma = weights[e]
+// for entry e, rows a device array like the weights.  p.frame_ll is not written (a frame may have several pdfs).  An
+// entry whose row is outside 0 .. n_frames is the caller's mistake: no frame is read for it and it adds nothing.
+void stats_items_w_launch(const StatsParams &p, const double *weights, int64_t n_frames, int dimp, int n_items,
+                          hipStream_t stream);
 // per-pdf sums of the items' slabs into the record accumulators racc [records x (2 + 2 dim)] and
 // the pdf accumulators pacc [pdfs x 2] (frames with a positive total, mixture_ll)
 void stats_pdf_reduce_launch(const int32_t *pdfs, const int32_t *item_begin, int n_pdfs, const StatsItem *items,

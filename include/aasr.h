@@ -731,6 +731,15 @@ void aasr_stats_destroy(aasr_stats *h);
  * safe_log(state likelihood).  Calls on one handle go to one stream. */
 aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int64_t n_frames,
                                       const int32_t *pdf, double *d_frame_ll, void *stream);
+/* Adds weighted entries: cnt (host, states + 1; cnt[s] the first entry of pdf s) describes d_rows / d_weights (device,
+ * cnt[states] elements): entry e of pdf s is frame row d_rows[e] of d_frames with Mixture::accumulate's gamma
+ * d_weights[e] (aku/Distributions.cc:2134-2161): posteriors gamma * weight * lik / total, mixture_ll += gamma *
+ * safe_log(total) also where total is 0, the frame count and feacount one up per entry with total > 0, aux gamma fabs.
+ * A frame may appear under several pdfs.  With every weight 1.0 and the row list of aasr_stats_accumulate_dev the sums
+ * are that call's, byte for byte; the two may be mixed on one handle.  On `stream`, no host wait
+ * (csrc/stats_weighted.hip).  A handle of aasr_stats_create_full refuses it (AASR_ERR_UNSUPPORTED, nothing queued). */
+aasr_status aasr_stats_accumulate_weighted_dev(aasr_stats *h, const double *d_frames, int64_t n_frames, const int64_t *cnt,
+                                               const int32_t *d_rows, const double *d_weights, void *stream);
 /* counts the transitions transition[0..n) (-1: none) */
 aasr_status aasr_stats_add_transitions(aasr_stats *h, const int32_t *transition, int64_t n);
 /* sums the Gaussians that several mixtures share and fetches everything to the host (waits) */
@@ -746,7 +755,7 @@ aasr_status aasr_stats_mixtures(const aasr_stats *h, int64_t *count, double *gam
 aasr_status aasr_stats_full_moments(const aasr_stats *h, double *sum_xx);
 int32_t aasr_stats_num_transitions(const aasr_stats *h);
 aasr_status aasr_stats_transitions(const aasr_stats *h, int32_t *source, int32_t *target_offset, double *count);
-/* Diagnostic, read-only: the launch shape of the last aasr_stats_accumulate_dev call that reached the
+/* Diagnostic, read-only: the launch shape of the last aasr_stats_accumulate_dev / _weighted_dev call that reached the
  * accumulation kernel -- out[0] the kernel's dimension instance, out[1] frames per sub-block (256, 192,
  * 128 or 64), out[2] 1 when the mixture records were staged in LDS, out[3] the model's largest mixture,
  * out[4] work items launched.  Five zeros before the first such call. */
@@ -774,6 +783,16 @@ typedef struct aasr_stats_options {
   int32_t full_stats;   /* --full-stats: full second moments, mode-3 dumps   */
 } aasr_stats_options;
 void aasr_stats_default_options(aasr_stats_options *opt);
+/* What Baum-Welch over HMM networks adds (aasr_run_stats_networks_recipe).  A struct of its own: aasr_stats_options ends
+ * with full_stats for its callers. */
+typedef struct aasr_stats_network_options {
+  int32_t viterbi;        /* -M vit: the best path instead of Baum-Welch          */
+  int32_t ac_scale_given; /* 1: -A was on the command line                        */
+  double fw_beam;         /* -F: 0 keeps the default 15 (set_pruning_thresholds)  */
+  double bw_beam;         /* -W: 0 keeps the default 200                          */
+  double ac_scale;        /* -A                                                   */
+} aasr_stats_network_options;
+void aasr_stats_network_default_options(aasr_stats_network_options *opt);
 
 /* stats main loop (aku/stats.cc:540-795, --ml with .phn segmentations) over one recipe slice: audio,
  * speaker configuration, features on the device and segmentations per utterance, the accumulation
@@ -781,6 +800,18 @@ void aasr_stats_default_options(aasr_stats_options *opt);
 aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
                                   const char *recipe_path, const aasr_stats_options *opt,
                                   aasr_run_stats *stats);
+/* The same loop with Baum-Welch over the recipe's hmmnet= networks in place of the .phn files (the reference's
+ * stats -H): per group of utterances the state rows of the model's scoring entry in the model's precision mode, the
+ * forward-backward pass (aasr_fb_batch_*; retries as simple_train, aku/stats.cc:79-102: 2x ... 5x the backward beam, the
+ * reference's messages, a given-up utterance adds nothing), the occupancies as weighted entries into the accumulation
+ * (aasr_fb_batch_entries_dev, aasr_stats_accumulate_weighted_dev), with opt->transitions the pass's transition
+ * occupancies (summed over frames, not divided by the frame's probability sum), and out.lls with the sum of the forward
+ * totals and the frames of the utterances that ran.  A line without hmmnet= is the reference's error; a frame whose
+ * probabilities sum to less than 0.01 (where the reference exits) is AASR_ERR_INVALID.  Refused (AASR_ERR_UNSUPPORTED):
+ * opt->full_stats, opt->ophn.  net NULL: the defaults. */
+aasr_status aasr_run_stats_networks_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
+                                           const char *recipe_path, const aasr_stats_options *opt,
+                                           const aasr_stats_network_options *net, aasr_run_stats *stats);
 
 /* ---------------------------------------------------------------------------
  * The log-likelihood of a state segmentation, per frame: what aku/vtln.cc:99-114 asks of the model for every frame,
@@ -897,6 +928,8 @@ typedef struct aasr_fb_options {
   int32_t want_pdf_occ;  /* keep, per frame, the occupancy of every pdf of the network's pdf list             */
   int32_t want_tr_occ;   /* keep, per transition index of the network, the occupancy summed over the frames   */
   int32_t force_global;  /* node vectors in global memory whatever the networks' size (csrc/hmmnet_fb.h)      */
+  int32_t device_occ;    /* with want_pdf_occ: the occupancies stay on the device for aasr_fb_batch_entries_dev --
+                            aasr_fb_batch_sync copies none and aasr_fb_batch_result refuses pdf_occ; 0: as before  */
 } aasr_fb_options;
 void aasr_fb_default_options(aasr_fb_options *opt);
 typedef struct aasr_fb_batch aasr_fb_batch;
@@ -924,6 +957,29 @@ aasr_status aasr_fb_batch_result(const aasr_fb_batch *b, int32_t u, int32_t *sta
 /* Diagnostic, read-only: the last aasr_fb_batch_dev call -- out[0] utterances launched, out[1] 1: node vectors in LDS,
  * 0: in global memory, out[2] LDS bytes of a workgroup, out[3] the attempt.  Four zeros before the first call. */
 void aasr_debug_fb_shape(const aasr_fb_batch *b, int32_t *out);
+
+/* The occupancies as weighted statistics entries, on the device (csrc/fb_entries.hip): what HmmNetBaumWelch::next_frame
+ * (aku/HmmNetBaumWelch.cc:714-789) hands to the trainer.  Per frame s_t = sum_j occ[t][j] in the order of the network's
+ * pdf list; an entry (t, j) exists where occ[t][j] > 0 and weighs occ[t][j] / s_t.  (The reference counts an arc whose
+ * posterior underflowed to exactly 0 as an entry of weight 0; here it is none.)
+ * After a sync, on a batch created with want_pdf_occ and device_occ; covers the AASR_FB_OK utterances only.  row0[u]: the
+ * frame row of utterance u's first frame in the caller's frame buffer.  Entries are grouped by global pdf, ascending;
+ * within a pdf the utterances come in batch order and the frames ascending -- for one pdf per frame the row list that
+ * aasr_stats_accumulate_dev builds.  cnt (host, n_states + 1): cnt[s] is the first entry of pdf s, cnt[n_states] the number
+ * of entries; it is the only thing copied back (one fetch, one wait).  *d_rows / *d_weights: device arrays of cnt[n_states]
+ * elements owned by the batch, valid until the next call on it (NULL without entries), written on `stream`.  No atomics:
+ * the same input gives the same bytes. */
+aasr_status aasr_fb_batch_entries_dev(aasr_fb_batch *b, int32_t n_states, const int64_t *row0, void *stream, int64_t *cnt,
+                                      const int32_t **d_rows, const double **d_weights);
+/* After aasr_fb_batch_entries_dev: the entries copied to the host (rows / weights: as many elements as that call's
+ * cnt[n_states]; either may be NULL), for callers that look at them rather than accumulate them.  Waits. */
+aasr_status aasr_fb_batch_entries_host(aasr_fb_batch *b, int32_t *rows, double *weights);
+/* After aasr_fb_batch_entries_dev: s_t of the frames of utterance u (n_frames doubles; the first call fetches every
+ * utterance's).  AASR_ERR_INVALID for an utterance the entries do not cover. */
+aasr_status aasr_fb_batch_frame_sums(aasr_fb_batch *b, int32_t u, double *sums);
+/* Diagnostic, read-only: the last aasr_fb_batch_entries_dev call -- out[0] entries, out[1] utterances covered, out[2..4]
+ * workgroups of the frame-sum, count and fill kernels.  Five zeros before the first call. */
+void aasr_debug_fb_entries_shape(const aasr_fb_batch *b, int32_t *out);
 
 /* logl main loop (aku/logl.cc:145-234) over one recipe slice (read with cluster_speakers): per utterance the sum of the
  * frame log-likelihoods along its .phn segmentation (aasr_segll; logl.cc's transtat is an unset global, so no
