@@ -190,6 +190,11 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_fb_batch_entries_dev.argtypes = [vp, i32, vp, vp, vp, pvp, pvp]
     L.aasr_fb_batch_entries_host.argtypes = [vp, vp, vp]
     L.aasr_fb_batch_frame_sums.argtypes = [vp, i32, vp]
+    L.aasr_fb_batch_path.argtypes = [vp, i32, vp]
+    L.aasr_dur_est_default_options.argtypes = [vp]
+    L.aasr_dur_est_default_options.restype = None
+    L.aasr_run_dur_est.argtypes = [cp, cp, vp]
+    L.aasr_dur_est_fit_gamma.argtypes = [vp, i32, C.POINTER(d), C.POINTER(d)]
     L.aasr_debug_fb_entries_shape.argtypes = [vp, C.POINTER(i32)]
     L.aasr_debug_fb_entries_shape.restype = None
     L.aasr_logl_default_options.argtypes = [vp]
@@ -1390,9 +1395,9 @@ class Stats:
 
 
 class StatsNetworkOptions(C.Structure):
-    """aasr_stats_network_options: what stats --networks adds (-M vit, -F, -W, -A)."""
+    """aasr_stats_network_options: what stats --networks adds (-M vit, -F, -W, -A, -a)."""
     _fields_ = [("viterbi", C.c_int32), ("ac_scale_given", C.c_int32), ("fw_beam", C.c_double), ("bw_beam", C.c_double),
-                ("ac_scale", C.c_double)]
+                ("ac_scale", C.c_double), ("alignment", C.c_int32)]
 
     @classmethod
     def defaults(cls, **kw) -> "StatsNetworkOptions":
@@ -1542,16 +1547,37 @@ class HmmNet:
 
 
 class FbOptions(C.Structure):
-    """aasr_fb_options"""
+    """aasr_fb_options up to device_occ: the fields the struct had before want_path, under the name their callers
+    know.  The library reads the whole struct, FbPathOptions below; defaults() returns that, and fb_batch /
+    fb_batch_entries complete an instance of this class before they hand it on.
+    Never pass C.byref(FbOptions()) to the library yourself: it reads want_path, 4 bytes past this class's end."""
     _fields_ = [("fw_beam", C.c_double), ("bw_beam", C.c_double), ("ac_scale", C.c_double), ("mode", C.c_int32),
                 ("max_attempts", C.c_int32), ("want_pdf_occ", C.c_int32), ("want_tr_occ", C.c_int32),
                 ("force_global", C.c_int32), ("device_occ", C.c_int32)]
 
     @classmethod
-    def defaults(cls) -> "FbOptions":
-        o = cls()
+    def defaults(cls) -> "FbPathOptions":
+        o = FbPathOptions()
         lib().aasr_fb_default_options(C.byref(o))
         return o
+
+
+class FbPathOptions(FbOptions):
+    """The whole aasr_fb_options: FbOptions and the struct's last field, want_path (a ctypes subclass appends its
+    fields to its base's: want_path lies at offset 48, as in the header)."""
+    _fields_ = [("want_path", C.c_int32)]
+
+
+def _whole_fb_options(opts: Optional[FbOptions]) -> FbPathOptions:
+    if opts is None:
+        return FbOptions.defaults()
+    if isinstance(opts, FbPathOptions):
+        return opts
+    o = FbPathOptions()
+    for name, _ in FbOptions._fields_:
+        setattr(o, name, getattr(opts, name))
+    assert C.sizeof(o) == 56 and FbPathOptions.want_path.offset == 48      # sizeof(aasr_fb_options)
+    return o
 
 
 def fb_batch(nets: list, n_frames: list, scores, row0: list, opts: Optional[FbOptions] = None, stream: int = 0) -> list:
@@ -1559,9 +1585,11 @@ def fb_batch(nets: list, n_frames: list, scores, row0: list, opts: Optional[FbOp
     of state log-likelihood rows (float32 or float64), row0[u] the row of utterance u's first frame.  Utterances whose
     backward pass misses the initial node are launched again with backward beam 2x, 3x, ... up to max_attempts.
     Returns per utterance a dict: status, backward_total, forward_total, attempts, pdf_occ, tr_occ (the last two None
-    unless the options ask for them), and `shape`, the launch shape of the first attempt."""
+    unless the options ask for them), and `shape`, the launch shape of the first attempt.  With opts.want_path also
+    `path`, the emitting arc of every frame (int32), or for an utterance that did not run `path_refused`: the status
+    and message with which aasr_fb_batch_path refused it."""
     L = lib()
-    opts = opts or FbOptions.defaults()
+    opts = _whole_fb_options(opts)
     n = len(nets)
     handles = (C.c_void_p * max(n, 1))(*[h.handle for h in nets])
     T = np.ascontiguousarray(n_frames, np.int32)
@@ -1591,6 +1619,13 @@ def fb_batch(nets: list, n_frames: list, scores, row0: list, opts: Optional[FbOp
             check(L.aasr_fb_batch_result(b, u, C.byref(st), C.byref(bt), C.byref(ft), C.byref(at), _ptr(occ), _ptr(trocc)))
             out.append({"status": st.value, "backward_total": bt.value, "forward_total": ft.value, "attempts": at.value,
                         "pdf_occ": occ, "tr_occ": trocc, "shape": shape, "device_bytes": L.aasr_fb_batch_device_bytes(b)})
+            if opts.want_path:
+                path = np.full(int(T[u]), -1, np.int32)
+                rc = L.aasr_fb_batch_path(b, u, _ptr(path))
+                if rc == 0:
+                    out[-1]["path"] = path
+                else:
+                    out[-1]["path_refused"] = (int(rc), L.aasr_last_error().decode())
         return out
     finally:
         L.aasr_fb_batch_destroy(b)
@@ -1605,7 +1640,7 @@ def fb_batch_entries(nets: list, n_frames: list, scores, row0: list, n_states: i
     for the others), shape (aasr_debug_fb_entries_shape) and pdf_occ_refused: the message with which
     aasr_fb_batch_result refused the occupancies."""
     L = lib()
-    o = FbOptions.defaults() if opts is None else opts
+    o = _whole_fb_options(opts)
     o.want_pdf_occ = o.device_occ = 1
     n = len(nets)
     handles = (C.c_void_p * max(n, 1))(*[h.handle for h in nets])
@@ -2475,3 +2510,35 @@ def run_tie_recipe(cfg_text: str, recipe_path: str, rule: str, out: Optional[str
     return {"utterances": st.utterances, "frames": st.frames, "clusters": opts.clusters, "seconds_total": st.seconds_total,
             "seconds_features": opts.seconds_features, "seconds_scatter": opts.seconds_scatter,
             "seconds_split": opts.seconds_split, "seconds_merge": opts.seconds_merge}
+
+
+# ---- state duration models (dur_est) -----------------------------------------------------------
+
+class DurEstOptions(C.Structure):
+    """aasr_dur_est_options"""
+    _fields_ = [("ophn", C.c_int32), ("maxdur", C.c_int32), ("skip", C.c_int32), ("mincount", C.c_int32),
+                ("info", C.c_int32), ("hist", C.c_char_p), ("gamma", C.c_char_p)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "DurEstOptions":
+        o = cls()
+        lib().aasr_dur_est_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_dur_est(ph_path: str, recipe_path: str, hist: Optional[str] = None, gamma: Optional[str] = None,
+                opts: Optional[DurEstOptions] = None) -> None:
+    """The dur_est tool's run: duration histograms (hist) and their gamma fits (gamma, the .dur file).  Host only."""
+    opts = opts or DurEstOptions.defaults()
+    opts.hist, opts.gamma = (hist.encode() if hist else None), (gamma.encode() if gamma else None)
+    check(lib().aasr_run_dur_est(ph_path.encode(), recipe_path.encode(), C.byref(opts)))
+
+
+def dur_est_fit_gamma(hist) -> Optional[tuple]:
+    """estimate_gamma_models on one histogram (hist[i]: occurrences of duration i + 1) -> (a, b), None with fewer than
+    two points.  Host only."""
+    h = np.ascontiguousarray(hist, np.int32)
+    a, b = C.c_double(), C.c_double()
+    return (a.value, b.value) if lib().aasr_dur_est_fit_gamma(_ptr(h), len(h), C.byref(a), C.byref(b)) else None

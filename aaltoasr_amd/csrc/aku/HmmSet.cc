@@ -181,6 +181,8 @@ int HmmSet::dim() {
 }
 
 int HmmSet::num_states() {
+  // a set that has read its .ph alone (aku/dur_est.cc:165-171 reads nothing else) has the states of that file
+  if (!m_gmm && m_gk.empty() && m_mc.empty() && !m_states.empty()) return (int)m_states.size();
   ensure_model();
   return aasr_gmm_num_states(m_gmm);
 }

@@ -3,15 +3,17 @@
 // for many utterances per launch (aasr_run_stats_recipe), dumps as HmmSet::dump_statistics writes them.
 //
 //   stats (-b BASE | -g GK -m MC -p PH) -c CFG -r RECIPE -o OUT --ml [--full-stats] [-t] [-O] [-S SPKC [-U]] [-n]
-//         [-B n -I k] [-i level] [--networks [-F fw] [-W bw] [-A scale] [-M bw|vit]]
+//         [-B n -I k] [-i level] [--networks [-F fw] [-W bw] [-A scale] [-M bw|vit] [-a]]
 //
 // --full-stats (an extension of this tool, like --device) collects the full second moments sum gamma x x^T and writes
 // mode-3 dumps, what estimate --mllt reads; pools of more than 127 dimensions are refused with it.
 // --networks is the reference's -H under a spelling of its own: Baum-Welch (or with -M vit Viterbi) over the recipe's
 // hmmnet= networks on the device, with -F / -W / -A honoured; -M mpv, --full-stats and -O are refused with it, and a
 // recipe line without hmmnet= is the reference's error.  Without it -F / -W / -A / -M are read and ignored, as before.
-// Built: --ml over .phn files or networks.  -H itself (use --networks), --mmi / --mpe / --grad, --mllt, -P, --savelat,
-// -a and --nseggk / --nsegmc are refused before the device is opened, and so are full-covariance or
+// With --networks -M vit, -a writes every utterance's best path as a state-numbered alignment into the recipe line's
+// alignment= file (what dur_est reads); -a under -M bw, with -O or without --networks is refused.
+// Built: --ml over .phn files or networks.  -H itself (use --networks), --mmi / --mpe / --grad, --mllt, -P, --savelat
+// and --nseggk / --nsegmc are refused before the device is opened, and so are full-covariance or
 // subspace pools and speaker files with model transforms.
 #include <cstdio>
 #include <cstdlib>
@@ -74,20 +76,25 @@ int main(int argc, char *argv[]) {
                               {"mllt", "--mllt"},
                               {"precomplat", "-P (precomputed lattices)"},
                               {"savelat", "--savelat"},
-                              {"alignment", "-a (alignment output)"},
                               {"nseggk", "--nseggk (numerator segmentation model)"},
                               {"nsegmc", "--nsegmc (numerator segmentation model)"}};
   for (const auto &r : refused)
     if (config[r[0]].specified)
       die(std::string("stats: ") + r[1] + " is not supported; only --ml over .phn files is" +
           (std::string(r[0]) == "hmmnet" ? ", and over HMM networks with --networks" : ""));
-  const bool networks = config["networks"].specified;
+  const bool networks = config["networks"].specified, alignment = config["alignment"].specified;
   const std::string segmode = config["segmode"].get_str();
+  // -a: the best path's alignments, over networks only (aku/stats.cc:513-524)
+  if (alignment && config["ophn"].specified) die("Can not read and write to output PHNs");
+  if (alignment && !networks)
+    die("stats: -a (alignment output) is not supported; only --ml over .phn files is, and -a over HMM networks with --networks -M vit");
   if (networks) {
     if (segmode == "mpv") die("stats: -M mpv (multipath Viterbi) is not supported with --networks; use -M bw or -M vit");
     if (segmode != "bw" && segmode != "vit") die("stats: -M " + segmode + ": invalid segmentation mode (bw, vit)");
+    if (alignment && segmode != "vit")
+      die("stats: -a (alignment output) needs -M vit with --networks: under Baum-Welch no single arc belongs to a frame");
     if (config["full-stats"].specified) die("stats: --full-stats is not supported with --networks");
-    if (config["ophn"].specified) die("stats: -O (output phns) is not supported with --networks");
+    if (config["ophn"].specified) die("stats: -O (output phns) is not supported with --networks");  // (with -a: above)
   }
 
   std::string gk, mc, ph;
@@ -141,6 +148,7 @@ int main(int argc, char *argv[]) {
   nopt.bw_beam = config["bw-beam"].get_float();
   nopt.ac_scale = config["ac-scale"].get_float();
   nopt.ac_scale_given = config["ac-scale"].specified;
+  nopt.alignment = alignment;
   const std::string out = config["out"].get_str();
   opt.out = out.c_str();
   aasr_spkc *spk = nullptr;

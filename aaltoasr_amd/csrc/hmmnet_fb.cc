@@ -29,7 +29,10 @@ struct aasr_fb_batch {
   std::vector<FbResult> result;
   std::vector<int32_t> list;
   std::vector<double> occ, trocc;  // host copies after a sync
-  DevBuf<int32_t> d_ints, d_list;
+  std::vector<int32_t> path;       // host copy of the paths (want_path), fetched by the first aasr_fb_batch_path
+  bool synced = false, path_fetched = false;
+  hipStream_t sync_stream = nullptr;
+  DevBuf<int32_t> d_ints, d_list, d_path;
   DevBuf<double> d_doubles, d_work, d_occ, d_trocc;
   DevBuf<FbUttDev> d_utt;
   DevBuf<FbResult> d_result;
@@ -77,6 +80,8 @@ aasr_status aasr_fb_batch_create(const aasr_fb_options *opt, int32_t n_utt, cons
     if (opt->mode != AASR_FB_BAUM_WELCH && opt->mode != AASR_FB_VITERBI)
       raise(AASR_ERR_UNSUPPORTED, "aasr_fb_batch_create: mode %d (multipath Viterbi is not built)", opt->mode);
     if (opt->max_attempts < 1) raise(AASR_ERR_INVALID, "aasr_fb_batch_create: max_attempts must be at least 1");
+    if (opt->want_path && opt->mode != AASR_FB_VITERBI)
+      raise(AASR_ERR_UNSUPPORTED, "aasr_fb_batch_create: want_path needs the Viterbi mode (Baum-Welch has no single arc per frame)");
     for (int u = 0; u < n_utt; u++) {
       if (!nets[u]) raise(AASR_ERR_INVALID, "aasr_fb_batch_create: utterance %d has no network", u);
       if (n_frames[u] < 1) raise(AASR_ERR_INVALID, "aasr_fb_batch_create: utterance %d has %d frames", u, n_frames[u]);
@@ -101,7 +106,7 @@ aasr_status aasr_fb_batch_create(const aasr_fb_options *opt, int32_t n_utt, cons
       return at;
     };
     int32_t max_nodes = 0;
-    int64_t work = 0, occ = 0, trocc = 0;
+    int64_t work = 0, occ = 0, trocc = 0, path = 0;
     b->utt.resize((size_t)n_utt);
     for (int u = 0; u < n_utt; u++) {
       const aasr_hmmnet &h = *nets[u];
@@ -160,6 +165,8 @@ aasr_status aasr_fb_batch_create(const aasr_fb_options *opt, int32_t n_utt, cons
       occ += (int64_t)d.T * d.net.n_pdf;
       d.trocc = trocc;
       trocc += d.net.n_tr;
+      d.path = path;
+      path += d.T;
       max_nodes = std::max(max_nodes, h.n_nodes);
     }
     b->lds_form = max_nodes <= FB_LDS_NODES && !opt->force_global;
@@ -174,13 +181,15 @@ aasr_status aasr_fb_batch_create(const aasr_fb_options *opt, int32_t n_utt, cons
     b->d_work.alloc((size_t)std::max<int64_t>(1, work));
     if (opt->want_pdf_occ) b->d_occ.alloc((size_t)std::max<int64_t>(1, occ));
     if (opt->want_tr_occ) b->d_trocc.alloc((size_t)std::max<int64_t>(1, trocc));
+    if (opt->want_path) b->d_path.alloc((size_t)std::max<int64_t>(1, path));
     if (opt->device_occ && !opt->want_pdf_occ)
       raise(AASR_ERR_INVALID, "aasr_fb_batch_create: device_occ without want_pdf_occ");
     b->occ.assign(opt->want_pdf_occ && !opt->device_occ ? (size_t)occ : 0, 0.0);
     b->trocc.assign(opt->want_tr_occ ? (size_t)trocc : 0, 0.0);
+    b->path.assign(opt->want_path ? (size_t)path : 0, -1);
     b->result.assign((size_t)n_utt, FbResult{FB_ZERO, FB_ZERO, 0, 0});
     b->bytes = (int64_t)(ints.size() * 4 + doubles.size() * 8 + (size_t)work * 8 + (opt->want_pdf_occ ? (size_t)occ : 0) * 8 + b->trocc.size() * 8 +
-                         nu * (sizeof(FbUttDev) + sizeof(FbResult) + 4));
+                         b->path.size() * 4 + nu * (sizeof(FbUttDev) + sizeof(FbResult) + 4));
     *out = b.release();
   });
 }
@@ -203,6 +212,7 @@ aasr_status aasr_fb_batch_dev(aasr_fb_batch *b, const void *d_state_loglik, int6
       raise(AASR_ERR_INVALID, "aasr_fb_batch_dev: attempt %d outside 1 .. %d", attempt, b->opt.max_attempts);
     const hipStream_t st = (hipStream_t)stream;
     b->e_built = b->e_sums_fetched = false;  // (entries of an earlier pass describe occupancies this one rewrites)
+    b->synced = b->path_fetched = false;     // (and so do its results and paths)
     b->list.clear();
     for (int u = 0; u < b->n; u++) {
       const aasr_hmmnet &h = *b->nets[(size_t)u];
@@ -244,6 +254,7 @@ aasr_status aasr_fb_batch_dev(aasr_fb_batch *b, const void *d_state_loglik, int6
     p.occ = b->d_occ.p;
     p.trocc = b->d_trocc.p;
     p.result = b->d_result.p;
+    p.path = b->opt.want_path ? b->d_path.p : nullptr;
     hmmnet_fb_launch(p, (int32_t)b->list.size(), b->lds_form, st);
     AASR_HIP(hipGetLastError());
     // the host tables of this call are read by the copies above: wait for them before the next call rewrites them
@@ -263,6 +274,8 @@ aasr_status aasr_fb_batch_sync(aasr_fb_batch *b, void *stream, int32_t *n_failed
         AASR_HIP(hipMemcpyAsync(b->trocc.data(), b->d_trocc.p, b->trocc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
       AASR_HIP(hipStreamSynchronize(st));
     }
+    b->synced = true;
+    b->sync_stream = st;
     int failed = 0;
     for (const FbResult &r : b->result) failed += r.status == FB_FAILED_BACKWARD;
     if (n_failed_backward) *n_failed_backward = failed;
@@ -289,6 +302,32 @@ aasr_status aasr_fb_batch_result(const aasr_fb_batch *b, int32_t u, int32_t *sta
     if (tr_occ) {
       if (!b->opt.want_tr_occ) raise(AASR_ERR_INVALID, "aasr_fb_batch_result: the batch was created without transition occupancies");
       if (r.status == FB_OK) std::copy(b->trocc.begin() + d.trocc, b->trocc.begin() + d.trocc + d.net.n_tr, tr_occ);
+    }
+  });
+}
+
+aasr_status aasr_fb_batch_path(aasr_fb_batch *b, int32_t u, int32_t *arcs) {
+  return guarded([&] {
+    if (!b || u < 0 || u >= b->n || !arcs) raise(AASR_ERR_INVALID, "aasr_fb_batch_path: bad argument");
+    if (!b->opt.want_path) raise(AASR_ERR_INVALID, "aasr_fb_batch_path: the batch was created without want_path");
+    if (!b->synced) raise(AASR_ERR_INVALID, "aasr_fb_batch_path: call aasr_fb_batch_sync first");
+    if (b->result[(size_t)u].status != FB_OK)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_path: utterance %d did not run (status %d)", u, b->result[(size_t)u].status);
+    // d_path is never initialised: an utterance that failed keeps stale arcs in its slice.  The status check above keeps
+    // them from the caller, and the range check below holds whatever the device wrote.
+    if (!b->path_fetched) {  // every utterance's path in one copy, on the stream of the sync
+      if (!b->path.empty()) {
+        AASR_HIP(hipMemcpyAsync(b->path.data(), b->d_path.p, b->path.size() * sizeof(int32_t), hipMemcpyDeviceToHost, b->sync_stream));
+        AASR_HIP(hipStreamSynchronize(b->sync_stream));
+      }
+      b->path_fetched = true;
+    }
+    const FbUttDev &d = b->utt[(size_t)u];
+    const int32_t n_em = d.net.n_em;
+    for (int32_t t = 0; t < d.T; t++) {
+      const int32_t a = b->path[(size_t)d.path + t];
+      if (a < 0 || a >= n_em) raise(AASR_ERR_INVALID, "aasr_fb_batch_path: utterance %d has arc %d at frame %d", u, a, t);
+      arcs[t] = a;
     }
   });
 }

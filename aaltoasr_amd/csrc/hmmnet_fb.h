@@ -12,6 +12,9 @@
 // CU's 160 KB, so four utterances fit a CU) and in global memory beyond that or when the handle was created
 // with force_global.  aasr_debug_fb_shape reports which form the last launch ran.  The arc-sized scratch
 // (two doubles per emitting arc) is in global memory in both forms.
+//
+// With want_path the Viterbi walk also keeps which emitting arc it took at each frame: T int32 per utterance in a
+// path buffer, stored by the lane that walks, next to the occupancy it sets.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,6 +49,7 @@ struct FbUttDev {
   int64_t nodes;     // 2 x n_nodes doubles (the global form's node vectors)
   int64_t occ;       // T x n_pdf doubles in the occupancy buffer (want_pdf_occ)
   int64_t trocc;     // n_tr doubles in the transition occupancy buffer (want_tr_occ)
+  int64_t path;      // T int32 in the path buffer (want_path)
 };
 
 struct FbResult {
@@ -65,6 +69,7 @@ struct FbParams {
   double fw_beam, bw_beam, ac_scale;
   double *work, *occ, *trocc;
   FbResult *result;
+  int32_t *path;         // nullptr, or Viterbi mode's emitting arc of every frame (want_path)
 };
 
 void hmmnet_fb_launch(const FbParams &p, int32_t n_list, bool lds_form, hipStream_t stream);

@@ -149,6 +149,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_hmmnet_fb(FbParams p) {
   FbResult &res = p.result[u];
   double *occ = p.want_pdf_occ ? p.occ + ud.occ : nullptr;
   double *trocc = p.want_tr_occ ? p.trocc + ud.trocc : nullptr;
+  int32_t *path = p.path ? p.path + ud.path : nullptr;
   const int32_t P = nd.n_pdf, K = nd.n_tr;
 
   // ---- backward: beta row T is the closure of the final node, then frame by frame from the last ----
@@ -248,6 +249,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_hmmnet_fb(FbParams p) {
         node = v.I[v.op->em_tgt + taken];
         if (occ) occ[(int64_t)t * P + v.I[v.op->em_slot + taken]] = 1.0;
         if (trocc) trocc[v.I[v.op->em_trslot + taken]] += 1.0;
+        if (path) path[t] = taken;
       }
       res.status = alive ? FB_OK : FB_FAILED_FORWARD;
       if (alive) res.forward_total = alpha;

@@ -748,6 +748,57 @@ namespace {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// HmmNetBaumWelch::next_frame's label of an emitting arc (:763-768): the arc's label without its '#' end marks
+// (LatticeLabel::remove_end_marks) -- the transition index, then the ";..." part the reader kept -- and, where that
+// splits at ';' into three or more fields (mixture;state;phone;...), "phone.state"
+std::string alignment_label(const aasr_hmmnet &net, int32_t arc) {
+  std::string label = std::to_string(net.em_tr[(size_t)arc]);
+  for (char c : net.em_label[(size_t)arc])
+    if (c != '#') label += c;
+  std::vector<std::string> fields;
+  size_t at = 0;
+  for (;;) {
+    const size_t stop = label.find(';', at);
+    fields.push_back(label.substr(at, stop == std::string::npos ? std::string::npos : stop - at));
+    if (stop == std::string::npos) break;
+    at = stop + 1;
+  }
+  return fields.size() >= 3 ? fields[2] + "." + fields[1] : label;
+}
+
+// The alignment file of one utterance as simple_train writes it (aku/stats.cc:116-131, 179-188): runs of one label text,
+// "start end label" in samples; the last line ends one frame past the range (the reference's own "+1": next_frame has
+// stepped once more before it returned false).  cache: the network's labels, filled as they are asked for.
+std::string alignment_text(const aasr_hmmnet &net, std::vector<std::string> &cache, const std::vector<int32_t> &path, int first_frame,
+                           int frame_mult) {
+  cache.resize(net.em_src.size());
+  std::string text;
+  char head[64];
+  int cur_start = -1;
+  const std::string *cur = nullptr;
+  auto put = [&](int end) {
+    snprintf(head, sizeof head, "%d %d ", cur_start * frame_mult, end * frame_mult);
+    text += head;
+    text += *cur;
+    text += '\n';
+  };
+  for (size_t t = 0; t < path.size(); t++) {
+    std::string &label = cache[(size_t)path[t]];
+    if (label.empty()) label = alignment_label(net, path[t]);
+    const int frame = first_frame + (int)t;
+    if (cur_start < 0) {
+      cur_start = frame;
+      cur = &label;
+    } else if (*cur != label) {
+      put(frame);
+      cur_start = frame;
+      cur = &label;
+    }
+  }
+  if (cur_start >= 0) put(first_frame + (int)path.size() + 1);
+  return text;
+}
+
 // The network mode of aasr_run_stats_recipe: per group the steps of logl.cc's network branch, then the occupancies as
 // weighted entries into the accumulation.  -> total_ll, num_frames of the utterances that ran
 void run_stats_networks(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const std::vector<RecipeInfo> &infos,
@@ -766,6 +817,10 @@ void run_stats_networks(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, c
   fo.want_pdf_occ = 1;
   fo.device_occ = 1;
   fo.want_tr_occ = transitions ? 1 : 0;
+  fo.want_path = nopt->alignment ? 1 : 0;
+  std::map<const aasr_hmmnet *, std::vector<std::string>> labels;  // per network, per emitting arc ("" until asked for)
+  std::vector<int32_t> path;
+  const int frame_mult = (int)(16000 / aasr_feat_frame_rate(feat));  // print_alignment_line (aku/stats.cc:59-70)
   const int S = aasr_gmm_num_states(gmm);
   const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
   const float fr = aasr_feat_frame_rate(feat);
@@ -783,11 +838,18 @@ void run_stats_networks(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, c
     std::vector<std::vector<int16_t>> audio;
     std::vector<int32_t> start, rows;
     std::vector<const aasr_hmmnet *> group_nets;
+    std::vector<char> align_open;  // with -a: the utterance's alignment file could be opened
     int64_t rows_total = 0;
     while (next < infos.size() && audio.size() < 1024 &&
            (audio.empty() || (rows_total < group_frames && rows_total * S < group_scores))) {
       const RecipeInfo &u = infos[next++];
       announce(u, opt->info);
+      if (nopt->alignment) {  // aku/stats.cc:565-572: the file exists, empty, before the utterance is looked at
+        FILE *af = fopen(u.alignment_path.c_str(), "w");
+        if (!af) fprintf(stderr, "Could not open alignment file %s\n", u.alignment_path.c_str());
+        else fclose(af);
+        align_open.push_back(af != nullptr);
+      }
       audio.push_back(load_utterance_input(feat, u));
       // Recipe::Info::init_hmmnet_files (Recipe.cc:198-231)
       if (u.hmmnet_path.empty()) raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
@@ -867,6 +929,12 @@ void run_stats_networks(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, c
         }
         max_dev = std::max(max_dev, dev);
       }
+      if (nopt->alignment && align_open[i]) {
+        path.resize((size_t)rows[i]);
+        if (aasr_fb_batch_path(b, (int32_t)i, path.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        const std::string text = alignment_text(*group_nets[i], labels[group_nets[i]], path, start[i], frame_mult);
+        write_text_file(infos[group_first + i].alignment_path.c_str(), text.data(), text.size());
+      }
     }
     if (accumulate && cnt[(size_t)S] > 0 &&
         aasr_stats_accumulate_weighted_dev(h, stager.d_x.p, rows_total, cnt.data(), d_rows, d_weights, stream) != AASR_OK)
@@ -916,6 +984,9 @@ static aasr_status run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_t
     check_feature_dim(gmm, feat);
     if (nopt && opt->full_stats)
       raise(AASR_ERR_UNSUPPORTED, "stats: --full-stats is not supported with --networks (full second moments are collected over .phn files only)");
+    if (nopt && nopt->alignment && opt->ophn) raise(AASR_ERR_INVALID, "Can not read and write to output PHNs");  // aku/stats.cc:516-517
+    if (nopt && nopt->alignment && !nopt->viterbi)
+      raise(AASR_ERR_UNSUPPORTED, "stats: alignment output needs the Viterbi mode (-M vit): under Baum-Welch no single arc belongs to a frame");
     if (nopt && opt->ophn)
       raise(AASR_ERR_UNSUPPORTED, "stats: -O is not supported with --networks (a network line has no segmentation to choose)");
     // stats reads its recipe with cluster_speakers = false (aku/stats.cc:422-424)

@@ -791,6 +791,7 @@ typedef struct aasr_stats_network_options {
   double fw_beam;         /* -F: 0 keeps the default 15 (set_pruning_thresholds)  */
   double bw_beam;         /* -W: 0 keeps the default 200                          */
   double ac_scale;        /* -A                                                   */
+  int32_t alignment;      /* -a: write the best path's state alignment to each line's alignment= file (-M vit only) */
 } aasr_stats_network_options;
 void aasr_stats_network_default_options(aasr_stats_network_options *opt);
 
@@ -808,7 +809,14 @@ aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_top
  * occupancies (summed over frames, not divided by the frame's probability sum), and out.lls with the sum of the forward
  * totals and the frames of the utterances that ran.  A line without hmmnet= is the reference's error; a frame whose
  * probabilities sum to less than 0.01 (where the reference exits) is AASR_ERR_INVALID.  Refused (AASR_ERR_UNSUPPORTED):
- * opt->full_stats, opt->ophn.  net NULL: the defaults. */
+ * opt->full_stats, opt->ophn.  net NULL: the defaults.
+ * With net->alignment (and net->viterbi; AASR_ERR_UNSUPPORTED under Baum-Welch, where no single arc belongs to a frame) every
+ * utterance's alignment= file is written as aku/stats.cc writes it (:116-131, 179-188): a frame's label is its arc's label
+ * (transition index and the ";..." part, '#' end marks dropped), "fields[2].fields[1]" where that splits at ';' into three
+ * or more fields (HmmNetBaumWelch.cc:763-768); runs of one label make a line "start end label", in samples at 16 kHz
+ * ((int)(16000 / frame_rate) per frame), frames counted from the line's start time; the last line ends one frame past the
+ * range, the reference's own "+1".  A file that cannot be opened is the reference's message on stderr and the utterance
+ * runs without it; a given-up utterance leaves its file empty.  opt->no_train still writes the alignments. */
 aasr_status aasr_run_stats_networks_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
                                            const char *recipe_path, const aasr_stats_options *opt,
                                            const aasr_stats_network_options *net, aasr_run_stats *stats);
@@ -930,6 +938,8 @@ typedef struct aasr_fb_options {
   int32_t force_global;  /* node vectors in global memory whatever the networks' size (csrc/hmmnet_fb.h)      */
   int32_t device_occ;    /* with want_pdf_occ: the occupancies stay on the device for aasr_fb_batch_entries_dev --
                             aasr_fb_batch_sync copies none and aasr_fb_batch_result refuses pdf_occ; 0: as before  */
+  int32_t want_path;     /* AASR_FB_VITERBI only (AASR_ERR_UNSUPPORTED otherwise): keep the emitting arc taken at
+                            every frame for aasr_fb_batch_path; 0: every other output keeps its bytes              */
 } aasr_fb_options;
 void aasr_fb_default_options(aasr_fb_options *opt);
 typedef struct aasr_fb_batch aasr_fb_batch;
@@ -954,6 +964,11 @@ aasr_status aasr_fb_batch_sync(aasr_fb_batch *b, void *stream, int32_t *n_failed
  * arrays and are written for AASR_FB_OK only; either may be NULL. */
 aasr_status aasr_fb_batch_result(const aasr_fb_batch *b, int32_t u, int32_t *status, double *backward_total,
                                  double *forward_total, int32_t *attempts, double *pdf_occ, double *tr_occ);
+/* After a sync, on a batch created with want_path: the emitting arc of each of utterance u's n_frames frames along the
+ * best path, numbered as the network's emitting arcs are (csrc/hmmnet.h, aasr_hmmnet_arc_label); for an utterance that
+ * was retried, the path of its last attempt.  The first call copies the whole batch's paths.  AASR_ERR_INVALID for an
+ * utterance whose status is not AASR_FB_OK and for a batch made without want_path. */
+aasr_status aasr_fb_batch_path(aasr_fb_batch *b, int32_t u, int32_t *arcs);
 /* Diagnostic, read-only: the last aasr_fb_batch_dev call -- out[0] utterances launched, out[1] 1: node vectors in LDS,
  * 0: in global memory, out[2] LDS bytes of a workgroup, out[3] the attempt.  Four zeros before the first call. */
 void aasr_debug_fb_shape(const aasr_fb_batch *b, int32_t *out);
@@ -1514,6 +1529,34 @@ void aasr_tie_default_options(aasr_tie_options *opt);
  * the file's last, with the frames it has before the end or none; the sums stay on the device for the split, the merge (with mloss_given) and the
  * writer.  A frame that two lines of one file claim is AASR_ERR_UNSUPPORTED. */
 aasr_status aasr_run_tie_recipe(const char *feat_cfg_text, const char *recipe_path, aasr_tie_options *opt, aasr_run_stats *stats);
+
+/* ---------------------------------------------------------------------------
+ * State duration models: aku/dur_est.cc over state-numbered .phn files (what stats --networks -M vit -a writes).  Host
+ * only: no device is opened. */
+typedef struct aasr_dur_est_options {
+  int32_t ophn;       /* -O: read the recipe's alignment= files            */
+  int32_t maxdur;     /* -M (100): longer durations count as this          */
+  int32_t skip;       /* --skip (0): the first states get no model         */
+  int32_t mincount;   /* --mincount (10)                                   */
+  int32_t info;       /* -i                                                */
+  const char *hist;   /* --hist: the histogram file to write, or NULL      */
+  const char *gamma;  /* --gamma: the .dur file to write, or NULL          */
+} aasr_dur_est_options;
+void aasr_dur_est_default_options(aasr_dur_est_options *opt);
+/* dur_est's main (aku/dur_est.cc:142-218).  The reader runs at PhnReader's default frame rate of 125 (Recipe.cc:158, no
+ * feature configuration), with the line's start-time / end-time and start-line / end-line as PhnReader applies them
+ * (PhnReader.cc:83-124; a start-line past the file's end or past end-line, where the reference never returns, ends the
+ * file's lines).  init_utterance_segmentation consumes a file's first line; every later line adds end - start frames
+ * (capped at maxdur) to the histogram of the state `state` of the HMM `label`.  A line without a state number is
+ * "Collecting duration statistics requires phn files with state numbers!"; an unknown label, a state the HMM does not
+ * have, or a line of no frames (where the reference indexes out of its tables) is AASR_ERR_INVALID.  A file without
+ * lines gives the reference's two messages on stderr and the run goes on.  hist: per state from skip on "state c1 c2
+ * ... \n"; gamma: "4\n<states>\n" and per state "state a b" with %.4f, the golden-section fit of estimate_gamma_models
+ * operation for operation, "0.0000 0.0000" for a state below skip, below mincount or with fewer than two points. */
+aasr_status aasr_run_dur_est(const char *ph_path, const char *recipe_path, const aasr_dur_est_options *opt);
+/* estimate_gamma_models on one histogram (hist[i]: occurrences of duration i + 1).  -> 1 and *a, *b, or 0 with fewer
+ * than two points.  Host only. */
+int32_t aasr_dur_est_fit_gamma(const int32_t *hist, int32_t n, double *a, double *b);
 
 #ifdef __cplusplus
 }
