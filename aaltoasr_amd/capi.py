@@ -197,6 +197,10 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_dur_est_fit_gamma.argtypes = [vp, i32, C.POINTER(d), C.POINTER(d)]
     L.aasr_debug_fb_entries_shape.argtypes = [vp, C.POINTER(i32)]
     L.aasr_debug_fb_entries_shape.restype = None
+    L.aasr_fb_batch_frame_entries_dev.argtypes = [vp, i32, vp, i64, vp, C.POINTER(i64), pvp, pvp, pvp]
+    L.aasr_fb_batch_frame_entries_host.argtypes = [vp, vp, vp, vp]
+    L.aasr_debug_fb_frame_entries_shape.argtypes = [vp, C.POINTER(i32)]
+    L.aasr_debug_fb_frame_entries_shape.restype = None
     L.aasr_logl_default_options.argtypes = [vp]
     L.aasr_logl_default_options.restype = None
     L.aasr_run_logl_recipe.argtypes = [vp, vp, vp, cp, vp, C.POINTER(d), vp]
@@ -214,6 +218,10 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_mllr_destroy.restype = None
     L.aasr_mllr_reset.argtypes = [vp, vp]
     L.aasr_mllr_accumulate_dev.argtypes = [vp, vp, i64, vp, vp]
+    L.aasr_mllr_accumulate_weighted_dev.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp]
+    L.aasr_mllr_network_default_options.argtypes = [vp]
+    L.aasr_mllr_network_default_options.restype = None
+    L.aasr_run_mllr_networks_recipe.argtypes = [vp, vp, vp, cp, vp, vp, vp]
     L.aasr_mllr_fetch.argtypes = [vp, vp]
     L.aasr_mllr_get.argtypes = [vp, vp, vp, C.POINTER(d)]
     L.aasr_mllr_solve.argtypes = [i32, vp, vp, d, vp]
@@ -1689,6 +1697,70 @@ def fb_batch_entries(nets: list, n_frames: list, scores, row0: list, n_states: i
         L.aasr_fb_batch_destroy(b)
 
 
+def fb_batch_frame_entries(nets: list, n_frames: list, scores, row0: list, n_states: int, opts: Optional[FbOptions] = None,
+                           frame_row0: Optional[list] = None, n_rows: Optional[int] = None, stream: int = 0,
+                           pdf_major: bool = False) -> dict:
+    """fb_batch_entries' pass with the entries grouped by frame (aasr_fb_batch_frame_entries_dev): off (n_rows + 1), pdf
+    and weight copied to the host, status / forward_total / attempts per utterance, sums (per utterance that ran, its
+    frame sums, fetched after the frame-major call), shape (aasr_debug_fb_frame_entries_shape).  n_rows: the rows of the
+    caller's frame buffer (default: the rows of `scores`).  pdf_major: also cnt / rows / weights of
+    aasr_fb_batch_entries_dev on the same batch, taken first."""
+    L = lib()
+    o = _whole_fb_options(opts)
+    o.want_pdf_occ = o.device_occ = 1
+    n = len(nets)
+    handles = (C.c_void_p * max(n, 1))(*[h.handle for h in nets])
+    T = np.ascontiguousarray(n_frames, np.int32)
+    r0 = np.ascontiguousarray(row0, np.int64)
+    fr0 = np.ascontiguousarray(row0 if frame_row0 is None else frame_row0, np.int64)
+    n_rows = int(scores.shape[0] if n_rows is None else n_rows)
+    b = C.c_void_p()
+    check(L.aasr_fb_batch_create(C.byref(o), n, handles, _ptr(T), C.byref(b)))
+    try:
+        f64 = 1 if str(scores.dtype) == "torch.float64" else 0
+        failed = C.c_int32(0)
+        for attempt in range(1, o.max_attempts + 1):
+            check(L.aasr_fb_batch_dev(b, _ptr(scores), scores.shape[1], scores.shape[0], f64, _ptr(r0), attempt, stream))
+            check(L.aasr_fb_batch_sync(b, stream, C.byref(failed)))
+            if failed.value == 0:
+                break
+        out = {"status": [], "forward_total": [], "attempts": [], "sums": []}
+        if pdf_major:
+            cnt = np.zeros(n_states + 1, np.int64)
+            d_rows, d_w = C.c_void_p(), C.c_void_p()
+            check(L.aasr_fb_batch_entries_dev(b, n_states, _ptr(fr0), stream, _ptr(cnt), C.byref(d_rows), C.byref(d_w)))
+            rows, weights = np.zeros(int(cnt[-1]), np.int32), np.zeros(int(cnt[-1]), np.float64)
+            check(L.aasr_fb_batch_entries_host(b, _ptr(rows), _ptr(weights)))
+            out.update(cnt=cnt, rows=rows, weights=weights)
+        total = C.c_int64(0)
+        d_off, d_pdf, d_w = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(L.aasr_fb_batch_frame_entries_dev(b, n_states, _ptr(fr0), n_rows, stream, C.byref(total), C.byref(d_off),
+                                                C.byref(d_pdf), C.byref(d_w)))
+        off = np.zeros(n_rows + 1, np.int64)
+        pdf, weight = np.zeros(total.value, np.int32), np.zeros(total.value, np.float64)
+        check(L.aasr_fb_batch_frame_entries_host(b, _ptr(off), _ptr(pdf), _ptr(weight)))
+        for u in range(n):
+            st, at, ft = C.c_int32(), C.c_int32(), C.c_double()
+            check(L.aasr_fb_batch_result(b, u, C.byref(st), None, C.byref(ft), C.byref(at), None, None))
+            out["status"].append(st.value)
+            out["forward_total"].append(ft.value)
+            out["attempts"].append(at.value)
+            if st.value == FB_OK:
+                s = np.zeros(int(T[u]), np.float64)
+                check(L.aasr_fb_batch_frame_sums(b, u, _ptr(s)))
+                out["sums"].append(s)
+            else:
+                out["sums"].append(None)
+        sh = (C.c_int32 * 5)()
+        L.aasr_debug_fb_frame_entries_shape(b, sh)
+        out["shape"] = {"entries": int(sh[0]), "utterances": int(sh[1]), "count_groups": int(sh[2]), "scan_groups": int(sh[3]),
+                        "fill_groups": int(sh[4])}
+        out.update(n_entries=total.value, off=off, pdf=pdf, weight=weight)
+        return out
+    finally:
+        L.aasr_fb_batch_destroy(b)
+
+
 class LoglOptions(C.Structure):
     """aasr_logl_options: logl's options (aku/logl.cc:91-112)."""
     _fields_ = [("ophn", C.c_int32), ("snl", C.c_int32), ("hmmnet", C.c_int32), ("den_hmmnet", C.c_int32),
@@ -1816,6 +1888,14 @@ class Mllr:
         p = np.ascontiguousarray(pdf, np.int32)
         check(lib().aasr_mllr_accumulate_dev(self._h, _ptr(d_frames), len(p), _ptr(p), _stream_handle(stream)))
 
+    def accumulate_weighted_dev(self, d_frames, d_off, d_pdf, d_weight, stream=None) -> None:
+        """d_frames: a float64 device tensor [n x dim]; d_off: an int64 device tensor [n + 1] of offsets into d_pdf (int32)
+        and d_weight (float64), device tensors of the entries -- the layout of aasr_fb_batch_frame_entries_dev."""
+        n, e = int(d_off.shape[0]) - 1, int(d_pdf.shape[0])
+        assert n >= 0 and int(d_weight.shape[0]) == e and (n == 0 or int(d_frames.shape[0]) >= n)
+        check(lib().aasr_mllr_accumulate_weighted_dev(self._h, _ptr(d_frames), n, _ptr(d_off), _ptr(d_pdf) if e else None,
+                                                      _ptr(d_weight) if e else None, e, _stream_handle(stream)))
+
     def fetch(self, stream=None):
         """Waits for the device; -> G [dim][dim + 1][dim + 1], k [dim][dim + 1], beta."""
         L = lib()
@@ -1846,14 +1926,32 @@ def mllr_compose(W, old_A=None, old_b=None):
     return A, b
 
 
+class MllrNetworkOptions(C.Structure):
+    """aasr_mllr_network_options: what mllr --networks adds (--segmode vit, -F, -W)."""
+    _fields_ = [("networks", C.c_int32), ("viterbi", C.c_int32), ("fw_beam", C.c_double), ("bw_beam", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "MllrNetworkOptions":
+        o = cls()
+        lib().aasr_mllr_network_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
 def run_mllr_recipe(feat: "Feat", gmm: "Gmm", topo: Topology, recipe_path: str, speakers: SpeakerConfig,
                     out: Optional[str] = None, module: Optional[str] = None,
-                    opts: Optional[MllrOptions] = None) -> dict:
+                    opts: Optional[MllrOptions] = None, networks: Optional[MllrNetworkOptions] = None) -> dict:
+    """mllr over a recipe; with `networks` (its networks field set) over the recipe's hmmnet= networks (mllr --networks)"""
     opts = opts or MllrOptions.defaults()
     ob, mb = (out.encode() if out else None), (module.encode() if module else None)
     opts.out, opts.module, opts.speakers = ob, mb, speakers._h
     st = RunStats()
-    check(lib().aasr_run_mllr_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    if networks is None:
+        check(lib().aasr_run_mllr_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    else:
+        check(lib().aasr_run_mllr_networks_recipe(feat._h, gmm._h, topo.handle, recipe_path.encode(), C.byref(opts),
+                                                  C.byref(networks), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total}
 
 

@@ -4,10 +4,14 @@
 // the speaker file as SpeakerConfig::write_speaker_file writes it.
 //
 //   mllr (-b BASE | -g GK -m MC -p PH) -c CFG -r RECIPE -S SPKC [-M MODULE] [-O] [-o OUT] [-B n -I k] [-i level]
+//        [--networks [-F fw] [-W bw] [--segmode bw|vit]]
 //
 // Built: one global transform per speaker, for the lin_transform module -M names or (no -M) as a model-side
-// cmllr block with unitmode UNIT_NO.  Refused before the device is opened: -H and --segmode (HMM networks),
-// -R and tree generation (-s with -t > 1), --snl, --rsamp, recipe start-line / end-line, non-diagonal pools.
+// cmllr block with unitmode UNIT_NO.  --networks is the reference's -H under a spelling of its own: Baum-Welch (or with
+// --segmode vit Viterbi) over the recipe's hmmnet= networks on the device (aasr_run_mllr_networks_recipe), with -F / -W
+// honoured; --segmode mpv and -O are refused with it, and a recipe line without hmmnet= is the reference's error.
+// Refused before the device is opened: -H itself (use --networks), --segmode without --networks, -R and tree
+// generation (-s with -t > 1), --snl, --rsamp, recipe start-line / end-line, non-diagonal pools.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,7 +51,8 @@ int main(int argc, char *argv[]) {
     ('B', "batch=INT", "arg", "0", "number of batch processes with the same recipe")
     ('I', "bindex=INT", "arg", "0", "batch process index")
     ('i', "info=INT", "arg", "0", "info level")
-    ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)");
+    ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)")
+    ('\0', "networks", "", "", "segment with the recipe's hmmnet= networks; the reference's -H");
   config.default_parse(argc, argv);
 
   if (config["ords"].specified)
@@ -59,9 +64,20 @@ int main(int argc, char *argv[]) {
                               {"regtree", "-R (regression tree)"},
                               {"snl", "--snl (state number labels)"},
                               {"rsamp", "--rsamp (relative sample numbers)"}};
-  for (const auto &r : refused)
+  const bool networks = config["networks"].specified;
+  for (const auto &r : refused) {
+    if (networks && std::string(r[0]) == "segmode") continue;
     if (config[r[0]].specified)
-      die(std::string("mllr: ") + r[1] + " is not supported; only global transforms over .phn files are");
+      die(std::string("mllr: ") + r[1] + " is not supported; only global transforms over .phn files are" +
+          (std::string(r[0]) == "hmmnet" ? ", and over HMM networks with --networks" : ""));
+  }
+  const std::string segmode = config["segmode"].get_str();
+  if (networks) {
+    if (segmode == "mpv")
+      die("mllr: --segmode mpv (multipath Viterbi) is not supported with --networks; use --segmode bw or --segmode vit");
+    if (segmode != "bw" && segmode != "vit") die("Invalid segmentation mode " + segmode);  // aku/mllr.cc:208-210
+    if (config["ophn"].specified) die("mllr: -O (output phns) is not supported with --networks");
+  }
   const bool global_transform = config["mllr"].specified;
   if (config["mcs"].specified && config["terminalnodes"].get_int() > 1 && !global_transform) {
     // the reference checks the unit before it builds the tree (aku/mllr.cc:238-242)
@@ -75,6 +91,8 @@ int main(int argc, char *argv[]) {
   check_pool(gk, "mllr");
   check_recipe_line_limits(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int(), true,
                            "mllr");
+  if (networks)
+    check_recipe_hmmnets(config["recipe"].get_str(), config["batch"].get_int(), config["bindex"].get_int(), true);
 
   const int device = config["device"].get_int();
   if (device >= 0 && aasr_set_device(device) != AASR_OK) die(aasr_last_error());
@@ -110,7 +128,13 @@ int main(int argc, char *argv[]) {
   opt.out = config["out"].specified ? out.c_str() : nullptr;
   aasr_run_stats st;
   memset(&st, 0, sizeof st);
-  if (aasr_run_mllr_recipe(feat, gmm, topo, config["recipe"].get_str().c_str(), &opt, &st) != AASR_OK)
+  aasr_mllr_network_options nopt;
+  aasr_mllr_network_default_options(&nopt);
+  nopt.networks = networks;
+  nopt.viterbi = segmode == "vit";
+  nopt.fw_beam = config["fw-beam"].get_float();
+  nopt.bw_beam = config["bw-beam"].get_float();
+  if (aasr_run_mllr_networks_recipe(feat, gmm, topo, config["recipe"].get_str().c_str(), &opt, &nopt, &st) != AASR_OK)
     die(aasr_last_error());
   aasr_spkc_destroy(spk);
   aasr_topo_destroy(topo);

@@ -3,7 +3,8 @@
 // relaunches the utterances whose backward pass missed the initial node with a wider backward beam
 // (aku/logl.cc:183-199: 2x, 3x, ... the original, the forward beam unchanged).  With device_occ the occupancies stay on
 // the device and aasr_fb_batch_entries_dev turns them into the weighted entries of the statistics accumulation
-// (fb_entries.hip).
+// (fb_entries.hip), aasr_fb_batch_frame_entries_dev into the frame-major (pdf, weight) lists of the CMLLR accumulation
+// (fb_frame_entries.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 
 #include "common.h"
 #include "fb_entries.h"
+#include "fb_frame_entries.h"
 #include "hmmnet.h"
 #include "hmmnet_fb.h"
 
@@ -46,6 +48,7 @@ struct aasr_fb_batch {
   std::vector<int64_t> e_out;
   std::vector<double> e_sums;  // host copy of the frame sums, fetched by the first aasr_fb_batch_frame_sums
   bool e_built = false, e_sums_fetched = false;
+  bool s_built = false;  // e_utt, e_index and the frame sums on the device are those of the last entries call of either kind
   hipStream_t e_stream = nullptr;
   DevBuf<FbEntryUtt> d_e_utt;
   DevBuf<FbEntryPair> d_e_pairs;
@@ -54,6 +57,16 @@ struct aasr_fb_batch {
   DevBuf<double> d_e_sums, d_e_weights;
   // aasr_debug_fb_entries_shape: entries, utterances covered, workgroups of the sum, count and fill kernels
   int32_t entries_shape[5] = {0, 0, 0, 0, 0};
+  // the frame-major entries of the last aasr_fb_batch_frame_entries_dev call (fb_frame_entries.h)
+  std::vector<int64_t> f_pdf_at;  // per covered utterance the start of its network's pdf list in f_pdfs
+  std::vector<int32_t> f_pdfs;
+  bool f_built = false;
+  int64_t f_total = 0, f_rows = 0;
+  DevBuf<int64_t> d_f_pdf_at, d_f_off, d_f_block_sums;
+  DevBuf<int32_t> d_f_pdfs, d_f_counts, d_f_pdf;
+  DevBuf<double> d_f_weight;
+  // aasr_debug_fb_frame_entries_shape: entries, utterances covered, workgroups of the count, offset and fill kernels
+  int32_t frame_entries_shape[5] = {0, 0, 0, 0, 0};
 };
 
 extern "C" {
@@ -212,6 +225,7 @@ aasr_status aasr_fb_batch_dev(aasr_fb_batch *b, const void *d_state_loglik, int6
       raise(AASR_ERR_INVALID, "aasr_fb_batch_dev: attempt %d outside 1 .. %d", attempt, b->opt.max_attempts);
     const hipStream_t st = (hipStream_t)stream;
     b->e_built = b->e_sums_fetched = false;  // (entries of an earlier pass describe occupancies this one rewrites)
+    b->s_built = b->f_built = false;
     b->synced = b->path_fetched = false;     // (and so do its results and paths)
     b->list.clear();
     for (int u = 0; u < b->n; u++) {
@@ -343,6 +357,7 @@ aasr_status aasr_fb_batch_entries_dev(aasr_fb_batch *b, int32_t n_states, const 
     *d_rows = nullptr;
     *d_weights = nullptr;
     b->e_built = b->e_sums_fetched = false;
+    b->s_built = b->f_built = false;  // (the frame-major entries index e_utt as their call left it)
     b->e_utt.clear();
     b->e_pairs.clear();
     b->e_index.assign((size_t)b->n, -1);
@@ -379,7 +394,7 @@ aasr_status aasr_fb_batch_entries_dev(aasr_fb_batch *b, int32_t n_states, const 
     b->e_sums.assign((size_t)sums, 0.0);
     b->e_stream = st;
     if (n_pairs == 0) {
-      b->e_built = true;
+      b->e_built = b->s_built = true;
       return;
     }
     b->d_e_utt.ensure((size_t)n_utt);
@@ -412,7 +427,7 @@ aasr_status aasr_fb_batch_entries_dev(aasr_fb_batch *b, int32_t n_states, const 
     b->entries_shape[0] = (int32_t)total;
     b->entries_shape[2] = ((max_T + FBE_THREADS - 1) / FBE_THREADS) * n_utt;
     b->entries_shape[3] = b->entries_shape[4] = (n_pairs + FBE_THREADS - 1) / FBE_THREADS;
-    b->e_built = true;
+    b->e_built = b->s_built = true;
     *d_rows = b->d_e_rows.p;
     *d_weights = b->d_e_weights.p;
   });
@@ -433,7 +448,7 @@ aasr_status aasr_fb_batch_entries_host(aasr_fb_batch *b, int32_t *rows, double *
 aasr_status aasr_fb_batch_frame_sums(aasr_fb_batch *b, int32_t u, double *sums) {
   return guarded([&] {
     if (!b || u < 0 || u >= b->n || !sums) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_sums: bad argument");
-    if (!b->e_built) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_sums: call aasr_fb_batch_entries_dev first");
+    if (!b->s_built) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_sums: call aasr_fb_batch_entries_dev first");
     const int32_t e = b->e_index[(size_t)u];
     if (e < 0) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_sums: utterance %d did not run (status %d)", u, b->result[(size_t)u].status);
     if (!b->e_sums_fetched) {  // every covered utterance's sums in one copy, on the stream that computed them
@@ -446,6 +461,119 @@ aasr_status aasr_fb_batch_frame_sums(aasr_fb_batch *b, int32_t u, double *sums) 
     const FbEntryUtt &eu = b->e_utt[(size_t)e];
     std::copy(b->e_sums.begin() + eu.sums, b->e_sums.begin() + eu.sums + eu.T, sums);
   });
+}
+
+aasr_status aasr_fb_batch_frame_entries_dev(aasr_fb_batch *b, int32_t n_states, const int64_t *row0, int64_t n_rows,
+                                            void *stream, int64_t *n_entries, const int64_t **d_off, const int32_t **d_pdf,
+                                            const double **d_weight) {
+  return guarded([&] {
+    if (!b || n_states < 0 || n_rows < 0 || (b->n > 0 && !row0) || !n_entries || !d_off || !d_pdf || !d_weight)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: bad argument");
+    if (!b->opt.want_pdf_occ || !b->opt.device_occ)
+      raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: the batch was created without device_occ");
+    if (!b->synced) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: call aasr_fb_batch_sync first");
+    if (n_rows >= (int64_t)INT32_MAX) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: more than 2^31 frame rows");
+    const hipStream_t st = (hipStream_t)stream;
+    *n_entries = 0;
+    *d_off = nullptr;
+    *d_pdf = nullptr;
+    *d_weight = nullptr;
+    // the pdf-major entries go: both calls keep the covered utterances and their frame sums in the same members
+    b->e_built = b->e_sums_fetched = b->s_built = b->f_built = false;
+    b->e_utt.clear();
+    b->e_index.assign((size_t)b->n, -1);
+    b->f_pdf_at.clear();
+    b->f_pdfs.clear();
+    std::fill(b->frame_entries_shape, b->frame_entries_shape + 5, 0);
+    int64_t sums = 0, bound = 0;
+    int32_t max_T = 0;
+    std::vector<std::pair<int64_t, int64_t>> windows;  // the utterances' rows must not overlap: a row has one lane
+    for (int u = 0; u < b->n; u++) {
+      if (b->result[(size_t)u].status != FB_OK) continue;
+      const FbUttDev &d = b->utt[(size_t)u];
+      const aasr_hmmnet &h = *b->nets[(size_t)u];
+      if (row0[u] < 0 || row0[u] + d.T > n_rows)
+        raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: utterance %d has frame rows %lld .. %lld of %lld", u,
+              (long long)row0[u], (long long)(row0[u] + d.T), (long long)n_rows);
+      for (int32_t pdf : h.pdfs)
+        if (pdf < 0 || pdf >= n_states)
+          raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: utterance %d uses pdf %d, the model has %d", u, pdf, n_states);
+      windows.push_back({row0[u], row0[u] + d.T});
+      b->e_index[(size_t)u] = (int32_t)b->e_utt.size();
+      b->e_utt.push_back(FbEntryUtt{d.occ, sums, row0[u], d.T, d.net.n_pdf});
+      b->f_pdf_at.push_back((int64_t)b->f_pdfs.size());
+      b->f_pdfs.insert(b->f_pdfs.end(), h.pdfs.begin(), h.pdfs.end());
+      sums += d.T;
+      bound += (int64_t)d.T * d.net.n_pdf;
+      max_T = std::max(max_T, d.T);
+    }
+    std::sort(windows.begin(), windows.end());
+    for (size_t i = 1; i < windows.size(); i++)
+      if (windows[i].first < windows[i - 1].second)
+        raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: two utterances share frame row %lld", (long long)windows[i].first);
+    const int32_t n_utt = (int32_t)b->e_utt.size();
+    b->e_sums.assign((size_t)sums, 0.0);
+    b->e_stream = st;
+    b->f_total = 0;
+    b->f_rows = n_rows;
+    b->frame_entries_shape[1] = n_utt;
+    b->d_f_counts.ensure((size_t)n_rows + 1);
+    b->d_f_off.ensure((size_t)n_rows + 1);
+    const int64_t scan_blocks = fb_frame_scan_blocks(n_rows);
+    b->d_f_block_sums.ensure((size_t)scan_blocks + 1);
+    AASR_HIP(hipMemsetAsync(b->d_f_counts.p, 0, ((size_t)n_rows + 1) * sizeof(int32_t), st));
+    if (n_utt > 0) {
+      b->d_e_utt.ensure((size_t)n_utt);
+      b->d_e_sums.ensure((size_t)sums);
+      b->d_f_pdf_at.ensure((size_t)n_utt);
+      b->d_f_pdfs.ensure(std::max<size_t>(1, b->f_pdfs.size()));
+      AASR_HIP(hipMemcpyAsync(b->d_e_utt.p, b->e_utt.data(), (size_t)n_utt * sizeof(FbEntryUtt), hipMemcpyHostToDevice, st));
+      AASR_HIP(hipMemcpyAsync(b->d_f_pdf_at.p, b->f_pdf_at.data(), (size_t)n_utt * sizeof(int64_t), hipMemcpyHostToDevice, st));
+      if (!b->f_pdfs.empty())
+        AASR_HIP(hipMemcpyAsync(b->d_f_pdfs.p, b->f_pdfs.data(), b->f_pdfs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      fb_frame_sums_launch(b->d_e_utt.p, n_utt, max_T, b->d_occ.p, b->d_e_sums.p, st);
+      fb_frame_counts_launch(b->d_e_utt.p, n_utt, max_T, b->d_occ.p, b->d_f_counts.p, st);
+    }
+    fb_frame_offsets_launch(b->d_f_counts.p, n_rows, b->d_f_block_sums.p, b->d_f_off.p, st);
+    // the one fetch and the one wait of the call: the number of entries
+    int64_t total = 0;
+    AASR_HIP(hipMemcpyAsync(&total, b->d_f_off.p + n_rows, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    AASR_HIP(hipStreamSynchronize(st));
+    if (total < 0 || total > bound) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: the frames report %lld entries", (long long)total);
+    if (total > (int64_t)INT32_MAX) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_dev: more than 2^31 entries in one batch");
+    b->d_f_pdf.ensure((size_t)std::max<int64_t>(1, total));
+    b->d_f_weight.ensure((size_t)std::max<int64_t>(1, total));
+    if (total > 0)
+      fb_frame_fill_launch(b->d_e_utt.p, b->d_f_pdf_at.p, b->d_f_pdfs.p, n_utt, max_T, b->d_occ.p, b->d_e_sums.p, b->d_f_off.p,
+                           b->d_f_pdf.p, b->d_f_weight.p, st);
+    b->f_total = total;
+    b->frame_entries_shape[0] = (int32_t)total;
+    b->frame_entries_shape[2] = ((max_T + FBF_THREADS - 1) / FBF_THREADS) * n_utt;
+    b->frame_entries_shape[3] = (int32_t)scan_blocks;
+    b->frame_entries_shape[4] = total > 0 ? b->frame_entries_shape[2] : 0;
+    b->f_built = b->s_built = true;
+    *n_entries = total;
+    *d_off = b->d_f_off.p;
+    *d_pdf = b->d_f_pdf.p;
+    *d_weight = b->d_f_weight.p;
+  });
+}
+
+aasr_status aasr_fb_batch_frame_entries_host(aasr_fb_batch *b, int64_t *off, int32_t *pdf, double *weight) {
+  return guarded([&] {
+    if (!b) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_host: null argument");
+    if (!b->f_built) raise(AASR_ERR_INVALID, "aasr_fb_batch_frame_entries_host: call aasr_fb_batch_frame_entries_dev first");
+    const size_t total = (size_t)b->f_total;
+    if (off) AASR_HIP(hipMemcpyAsync(off, b->d_f_off.p, ((size_t)b->f_rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, b->e_stream));
+    if (pdf && total) AASR_HIP(hipMemcpyAsync(pdf, b->d_f_pdf.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, b->e_stream));
+    if (weight && total) AASR_HIP(hipMemcpyAsync(weight, b->d_f_weight.p, total * sizeof(double), hipMemcpyDeviceToHost, b->e_stream));
+    AASR_HIP(hipStreamSynchronize(b->e_stream));
+  });
+}
+
+void aasr_debug_fb_frame_entries_shape(const aasr_fb_batch *b, int32_t *out) {
+  if (!b || !out) return;
+  std::copy(b->frame_entries_shape, b->frame_entries_shape + 5, out);
 }
 
 void aasr_debug_fb_entries_shape(const aasr_fb_batch *b, int32_t *out) {

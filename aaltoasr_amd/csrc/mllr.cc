@@ -1,7 +1,8 @@
 // mllr.cc -- constrained MLLR estimation (aku/mllr.cc, aku/MllrTrainer.cc): the statistics handle that drives the
 // device accumulation (mllr_accum.hip), the host solver of MllTrainerComponent::calculate_transform /
 // calculate_alpha (MllrTrainer.cc:165-253) in double with its own LU, and the mllr main loop over a recipe
-// (aasr_run_mllr_recipe, mllr.cc:54-71, 126-145, 213-332).
+// (aasr_run_mllr_recipe, mllr.cc:54-71, 126-145, 213-332), over .phn files or, with aasr_run_mllr_networks_recipe, over
+// the recipe's HMM networks (mllr.cc:73-104: hmmnet_fb.hip, fb_frame_entries.hip, mllr_entries.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,8 @@
 #include "common.h"
 #include "feat.h"
 #include "gmm.h"
+#include "hmmnet.h"
+#include "hmmnet_fb.h"
 #include "mllr.h"
 #include "mllt.h"
 #include "recipe_pass.h"
@@ -148,6 +151,50 @@ aasr_status aasr_mllr_accumulate_dev(aasr_mllr *h, const double *d_frames, int64
       p.pdf = h->d_pdf.p + f0;
       p.n = (int32_t)std::min(launch, n_frames - f0);
       mllr_weights_launch(p, st);
+      mllr_rank_launch(p, h->slab.p, h->acc.p, st);
+    }
+    h->fetched = false;
+  });
+}
+
+aasr_status aasr_mllr_accumulate_weighted_dev(aasr_mllr *h, const double *d_frames, int64_t n_frames, const int64_t *d_off,
+                                              const int32_t *d_pdf, const double *d_weight, int64_t n_entries, void *stream) {
+  return guarded([&] {
+    if (!h || n_frames < 0 || n_entries < 0 || (n_frames > 0 && (!d_frames || !d_off)) || (n_entries > 0 && (!d_pdf || !d_weight)))
+      raise(AASR_ERR_INVALID, "aasr_mllr_accumulate_weighted_dev: bad argument");
+    if (n_frames > INT32_MAX) raise(AASR_ERR_INVALID, "aasr_mllr_accumulate_weighted_dev: more than 2^31 frames in one call");
+    if (n_frames == 0) return;
+    check_mllr_model(h->gmm);
+    const hipStream_t st = (hipStream_t)stream;
+    // the cuts of aasr_mllr_accumulate_dev: launches of MLLR_CHUNK MLLR_MAX_CHUNKS frames
+    const int64_t launch = (int64_t)MLLR_CHUNK * MLLR_MAX_CHUNKS;
+    const int64_t cap = std::min(launch, n_frames);
+    h->w.ensure((size_t)cap * h->D);
+    h->u.ensure((size_t)cap * (h->D + 1));
+    h->ok.ensure((size_t)cap);
+    h->slab.ensure((size_t)((cap + MLLR_CHUNK - 1) / MLLR_CHUNK) * h->SL);
+    MllrEntryParams q{};
+    MllrParams &p = q.p;
+    p.dim = h->D;
+    p.recs = h->gmm->f64_recs.p;
+    p.dimp = h->gmm->f64_dimp;
+    p.rec = 2 * p.dimp + 2;
+    p.state_off = h->gmm->f64_state_off.p;
+    p.inv_var = h->inv_var.p;
+    p.mean_var = h->mean_var.p;
+    p.max_comps = h->max_comps;
+    p.w = h->w.p;
+    p.u = h->u.p;
+    p.ok = h->ok.p;
+    q.pdf = d_pdf;
+    q.weight = d_weight;
+    q.n_entries = n_entries;
+    q.n_states = h->S;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += launch) {
+      p.x = d_frames + (size_t)f0 * h->D;
+      q.off = d_off + f0;
+      p.n = (int32_t)std::min(launch, n_frames - f0);
+      mllr_entry_weights_launch(q, st);
       mllr_rank_launch(p, h->slab.p, h->acc.p, st);
     }
     h->fetched = false;
@@ -362,11 +409,15 @@ void aasr_mllr_default_options(aasr_mllr_options *o) {
 
 // ---- the mllr main loop over a recipe ----------------------------------------------------------
 
-extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
-                                            const aasr_mllr_options *opt, aasr_run_stats *stats) {
+// nopt: the network mode (aasr_run_mllr_networks_recipe), or NULL for the .phn files
+static aasr_status run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                   const aasr_mllr_options *opt, const aasr_mllr_network_options *nopt,
+                                   aasr_run_stats *stats) {
   return guarded([&] {
     if (!feat || !gmm || !topo || !recipe_path || !opt || !opt->speakers)
-      raise(AASR_ERR_INVALID, "aasr_run_mllr_recipe: null argument");
+      raise(AASR_ERR_INVALID, "%s: null argument", nopt ? "aasr_run_mllr_networks_recipe" : "aasr_run_mllr_recipe");
+    if (nopt && opt->ophn)
+      raise(AASR_ERR_UNSUPPORTED, "mllr: -O is not supported with --networks (a network line has no segmentation to choose)");
     const auto t0 = std::chrono::steady_clock::now();
     aasr_spkc *spk = opt->speakers;
     // Recipe::read with cluster_speakers = true, then sort_infos (aku/mllr.cc:213-216)
@@ -447,6 +498,96 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
       have_trainer = false;
     };
 
+    // The network mode's step for a staged group (get_segmentator and train_mllr, aku/mllr.cc:73-104, 126-145): state
+    // scores, one forward-backward batch with its retries, the frame-major entries, the weighted accumulation.
+    // -> the frames of the utterances that ran
+    aasr_fb_options fo;
+    aasr_fb_default_options(&fo);
+    if (nopt) {
+      if (nopt->fw_beam > 0) fo.fw_beam = nopt->fw_beam;  // set_pruning_thresholds: 0 keeps the default
+      if (nopt->bw_beam > 0) fo.bw_beam = nopt->bw_beam;
+      fo.mode = nopt->viterbi ? AASR_FB_VITERBI : AASR_FB_BAUM_WELCH;
+    }
+    fo.want_pdf_occ = 1;
+    fo.device_occ = 1;
+    fo.max_attempts = 5;  // (counter >= 5, aku/mllr.cc:90)
+    const int S = aasr_gmm_num_states(gmm);
+    NetworkCache net_cache(topo, S);
+    GroupScores scores;
+    std::vector<double> sums;
+    double total_ll = 0, max_dev = 0;  // the forward totals; max |1 - s_t| over the run
+    int64_t entries = 0;
+    auto networks_group = [&](const std::vector<RecipeInfo> &infos, size_t group_first,
+                              const std::vector<const aasr_hmmnet *> &group_nets, const std::vector<int32_t> &start,
+                              const std::vector<int32_t> &rows, int64_t rows_total) -> int64_t {
+      if (group_nets.empty() || rows_total <= 0) return 0;
+      // in model mode the model is the unadapted one the statistics are collected on (loading is disabled above)
+      const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
+      const void *d_scores = scores.score(gmm, stager.d_x.p, rows_total, f64, stream);
+      aasr_fb_batch *b = nullptr;
+      if (aasr_fb_batch_create(&fo, (int32_t)group_nets.size(), group_nets.data(), rows.data(), &b) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      std::unique_ptr<aasr_fb_batch, void (*)(aasr_fb_batch *)> bguard(b, aasr_fb_batch_destroy);
+      std::vector<int64_t> row0;
+      int64_t at = 0;
+      for (int32_t r : rows) {
+        row0.push_back(at);
+        at += r;
+      }
+      // aku/mllr.cc:87-102: a failed backward pass is run again with 2x ... 5x the original backward beam, the forward
+      // beam as it stands -- new launches over the failed utterances only
+      int32_t failed = 0;
+      for (int attempt = 1; attempt <= fo.max_attempts; attempt++) {
+        if (aasr_fb_batch_dev(b, d_scores, S, rows_total, f64 ? 1 : 0, row0.data(), attempt, stream) != AASR_OK ||
+            aasr_fb_batch_sync(b, stream, &failed) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        if (failed == 0) break;
+      }
+      int64_t n_entries = 0;
+      const int64_t *d_off = nullptr;
+      const int32_t *d_pdf = nullptr;
+      const double *d_weight = nullptr;
+      if (aasr_fb_batch_frame_entries_dev(b, S, row0.data(), rows_total, stream, &n_entries, &d_off, &d_pdf, &d_weight) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      entries += n_entries;
+      // the messages in recipe order, and the frame sums: HmmNetBaumWelch::next_frame's sanity check (:772-779)
+      int64_t frames = 0;
+      for (size_t i = 0; i < group_nets.size(); i++) {
+        const RecipeInfo &u = infos[group_first + i];
+        int32_t status = 0, attempts = 0;
+        double fw = 0;
+        if (aasr_fb_batch_result(b, (int32_t)i, &status, nullptr, &fw, &attempts, nullptr, nullptr) != AASR_OK)
+          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        for (int k = 2; k <= attempts; k++) fprintf(stderr, "Warning: Backward phase failed, increasing beam to %.1f\n", k * fo.bw_beam);
+        if (status == FB_FAILED_BACKWARD) {
+          fprintf(stderr, "Could not run Baum-Welch for file %s\n", u.audio_path.c_str());
+          fprintf(stderr, "The HMM network may be incorrect or initial beam too low.\n");
+          continue;
+        }
+        if (status != FB_OK) raise(AASR_ERR_INVALID, "No paths survived to the end of the network!");
+        sums.resize((size_t)rows[i]);
+        if (aasr_fb_batch_frame_sums(b, (int32_t)i, sums.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        for (int32_t f = 0; f < rows[i]; f++) {
+          const double dev = std::fabs(1 - sums[(size_t)f]);
+          if (dev > 0.02) {
+            fprintf(stderr, "Warning: Sum of PDF probabilities is %g at frame %i\n", sums[(size_t)f], start[i] + f);
+            if (sums[(size_t)f] < 0.01)  // (the reference exits here)
+              raise(AASR_ERR_INVALID, "HmmNetBaumWelch: the sum of PDF probabilities is %g at frame %d of %s", sums[(size_t)f],
+                    start[i] + f, u.audio_path.c_str());
+          }
+          max_dev = std::max(max_dev, dev);
+        }
+        total_ll += fw;  // train_mllr: get_total_log_likelihood (aku/mllr.cc:143-144)
+        frames += rows[i];
+      }
+      if (n_entries > 0 &&
+          aasr_mllr_accumulate_weighted_dev(h, stager.d_x.p, rows_total, d_off, d_pdf, d_weight, n_entries, stream) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      // the batch owns the entries that the accumulation reads: it goes when the stream is done with them
+      AASR_HIP(hipStreamSynchronize(stream));
+      return frames;
+    };
+
     size_t next = 0;
     while (next < infos.size()) {
       if (infos[next].speaker_id.empty()) raise(AASR_ERR_INVALID, "Speaker ID is missing");
@@ -462,12 +603,24 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
       const size_t group_first = next;
       std::vector<std::vector<int16_t>> audio;
       std::vector<int32_t> start, rows, pdfs;
+      std::vector<const aasr_hmmnet *> group_nets;
       int64_t rows_total = 0;
       while (next < infos.size() && infos[next].speaker_id == cur_speaker && audio.size() < 1024 &&
              rows_total < max_group_frames) {
         const RecipeInfo &u = infos[next];
         announce(u, opt->info, (int)next, (int)infos.size());
         audio.push_back(load_utterance_input(feat, u));
+        if (nopt) {  // Recipe::Info::init_hmmnet_files (Recipe.cc:198-231)
+          if (u.hmmnet_path.empty()) raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
+          group_nets.push_back(net_cache.get(u.hmmnet_path));
+          int first, n;
+          network_frame_range(u, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), &first, &n);
+          start.push_back(first);
+          rows.push_back(n);
+          rows_total += n;
+          next++;
+          continue;
+        }
         // train_mllr hands the segmentator's PDF index to model.state() and takes that state's emission_pdf
         // (aku/mllr.cc:136-140): a double lookup.  In the .ph files this engine reads a state's emission pdf is the
         // state's own index (HmmSet::read_ph, legacy format) and the engine takes state == pdf throughout, so
@@ -488,6 +641,10 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
         if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
           raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       });
+      if (nopt) {
+        num_frames += networks_group(infos, group_first, group_nets, start, rows, rows_total);
+        continue;
+      }
       if (rows_total > 0) {
         if (aasr_mllr_accumulate_dev(h, stager.d_x.p, rows_total, pdfs.data(), stream) != AASR_OK)
           raise(AASR_ERR_INVALID, "%s", aasr_last_error());
@@ -496,9 +653,33 @@ extern "C" aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, cons
       num_frames += rows_total;
     }
     if (have_trainer) finish_speaker();
+    if (nopt && opt->info > 0) {
+      fprintf(stderr, "Largest |1 - sum of PDF probabilities| of a frame: %g\n", max_dev);
+      fprintf(stderr, "Weighted entries: %lld over %lld frames\n", (long long)entries, (long long)num_frames);
+    }
 
     // the new speaker configuration (aku/mllr.cc:318-332)
     if (opt->out) write_speaker_file_for_batch(spk, updated, opt->num_batches, opt->batch_index, opt->out);
+    if (opt->info > 0 && total_ll != 0) fprintf(stderr, "Total log likelihood: %f\n", total_ll);  // aku/mllr.cc:334-336
     fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
   });
 }
+
+extern "C" {
+
+aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                 const aasr_mllr_options *opt, aasr_run_stats *stats) {
+  return run_mllr_recipe(feat, gmm, topo, recipe_path, opt, nullptr, stats);
+}
+
+void aasr_mllr_network_default_options(aasr_mllr_network_options *o) {
+  if (o) memset(o, 0, sizeof *o);
+}
+
+aasr_status aasr_run_mllr_networks_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
+                                          const aasr_mllr_options *opt, const aasr_mllr_network_options *net,
+                                          aasr_run_stats *stats) {
+  return run_mllr_recipe(feat, gmm, topo, recipe_path, opt, net && net->networks ? net : nullptr, stats);
+}
+
+}  // extern "C"

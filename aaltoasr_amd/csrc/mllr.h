@@ -53,4 +53,18 @@ void mllr_weights_launch(const MllrParams &p, hipStream_t stream);
 void mllr_rank_launch(const MllrParams &p, double *slab, double *acc, hipStream_t stream);
 size_t mllr_weights_lds_bytes(int dim, int max_comps);
 
+// Pass 1 from weighted entries (mllr_entries.hip): frame t has the entries off[t] .. off[t + 1] of (pdf, weight), walked
+// in list order; entry (pdf, p) adds p lik_g / sum_g lik_g per Gaussian to the frame's running w, u and beta share.  It
+// writes the w, u and ok that passes 2 and 3 read, for every frame of the launch (zeros for a frame without entries).
+struct MllrEntryParams {
+  MllrParams p;           // pdf unused; x, w, u, ok of the launch's frames
+  const int64_t *off;     // [n + 1] of the launch's frames, absolute into pdf / weight
+  const int32_t *pdf;     // per entry; outside 0 .. n_states: the entry is skipped
+  const double *weight;   // per entry
+  int64_t n_entries;      // an offset outside 0 .. n_entries ends the frame's list
+  int32_t n_states;
+};
+void mllr_entry_weights_launch(const MllrEntryParams &p, hipStream_t stream);
+size_t mllr_entry_weights_lds_bytes(int dim, int max_comps);
+
 }  // namespace aasr

@@ -996,6 +996,27 @@ aasr_status aasr_fb_batch_frame_sums(aasr_fb_batch *b, int32_t u, double *sums);
  * workgroups of the frame-sum, count and fill kernels.  Five zeros before the first call. */
 void aasr_debug_fb_entries_shape(const aasr_fb_batch *b, int32_t *out);
 
+/* The same entries grouped by frame, on the device (csrc/fb_frame_entries.hip): what the CMLLR accumulation walks
+ * (aasr_mllr_accumulate_weighted_dev).  Preconditions as aasr_fb_batch_entries_dev: after a sync, on a batch created with
+ * want_pdf_occ and device_occ; covers the AASR_FB_OK utterances only.  row0[u]: the frame row of utterance u's first frame
+ * in the caller's frame buffer of n_rows rows; the utterances' rows must not overlap.  *d_off (n_rows + 1 offsets): the
+ * entries of frame row r are d_off[r] .. d_off[r + 1]; a row that no covered utterance owns has none.  *d_pdf / *d_weight
+ * (*n_entries elements): the global pdf and the weight occ[t][j] / s_t of every entry, a frame's entries in the order of
+ * its network's pdf list (the order in which s_t is summed); s_t is the value of the pdf-major call, so a weight has the
+ * same bytes in both.  The arrays are owned by the batch and valid until the next entries call of either kind on it (which
+ * also replaces the other kind's entries).  The host fetches the number of entries only (one fetch, one wait), never the
+ * offsets.  No atomics: the same input gives the same bytes. */
+aasr_status aasr_fb_batch_frame_entries_dev(aasr_fb_batch *b, int32_t n_states, const int64_t *row0, int64_t n_rows,
+                                            void *stream, int64_t *n_entries, const int64_t **d_off, const int32_t **d_pdf,
+                                            const double **d_weight);
+/* After aasr_fb_batch_frame_entries_dev: the three arrays copied to the host (off: that call's n_rows + 1 elements; pdf /
+ * weight: its *n_entries; any may be NULL), for callers that look at them rather than accumulate them.  Waits.
+ * aasr_fb_batch_frame_sums works after either entries call. */
+aasr_status aasr_fb_batch_frame_entries_host(aasr_fb_batch *b, int64_t *off, int32_t *pdf, double *weight);
+/* Diagnostic, read-only: the last aasr_fb_batch_frame_entries_dev call -- out[0] entries, out[1] utterances covered,
+ * out[2..4] workgroups of the count, offset (first step) and fill kernels.  Five zeros before the first call. */
+void aasr_debug_fb_frame_entries_shape(const aasr_fb_batch *b, int32_t *out);
+
 /* logl main loop (aku/logl.cc:145-234) over one recipe slice (read with cluster_speakers): per utterance the sum of the
  * frame log-likelihoods along its .phn segmentation (aasr_segll; logl.cc's transtat is an unset global, so no
  * transition terms enter), or with hmmnet / den_hmmnet the forward total of the pass above over the recipe's hmmnet= /
@@ -1044,6 +1065,17 @@ aasr_status aasr_mllr_reset(aasr_mllr *h, void *stream);
  * `stream`, no host wait.  Calls on one handle go to one stream. */
 aasr_status aasr_mllr_accumulate_dev(aasr_mllr *h, const double *d_frames, int64_t n_frames,
                                      const int32_t *pdf, void *stream);
+/* The same sums from weighted entries, all on the device (csrc/mllr_entries.hip): frame row t has the entries
+ * d_off[t] .. d_off[t + 1] (d_off: n_frames + 1 ascending offsets into d_pdf / d_weight of n_entries elements, the
+ * layout of aasr_fb_batch_frame_entries_dev).  Per frame, in list order, entry (pdf, p) adds p lik_g / sum_g lik_g per
+ * Gaussian of the pdf's mixture (MllrTrainer::collect_data with the segmentator's probability, aku/mllr.cc:136-141) to
+ * the frame's running weights and to beta; a value that is not > 0 adds nothing, an entry whose pdf is outside the model
+ * is skipped, a frame without entries (or whose beta share is not > 0) adds nothing.  With one entry of weight 1.0 per
+ * frame the accumulator gets the bytes of aasr_mllr_accumulate_dev with that pdf[]; both calls may be mixed on a handle.
+ * d_off's last offset must not exceed n_entries (the caller's contract: the offsets are not fetched).  No host wait. */
+aasr_status aasr_mllr_accumulate_weighted_dev(aasr_mllr *h, const double *d_frames, int64_t n_frames,
+                                              const int64_t *d_off, const int32_t *d_pdf, const double *d_weight,
+                                              int64_t n_entries, void *stream);
 /* fetches the sums to the host (waits) */
 aasr_status aasr_mllr_fetch(aasr_mllr *h, void *stream);
 /* after a fetch: G [dim][dim + 1][dim + 1] (symmetric), k [dim][dim + 1], *beta; any pointer may be NULL */
@@ -1076,6 +1108,31 @@ void aasr_mllr_default_options(aasr_mllr_options *opt);
 aasr_status aasr_run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
                                  const char *recipe_path, const aasr_mllr_options *opt,
                                  aasr_run_stats *stats);
+
+/* What the HMM networks add (aasr_run_mllr_networks_recipe).  A struct of its own: aasr_mllr_options stays as it is for
+ * its callers. */
+typedef struct aasr_mllr_network_options {
+  int32_t networks;  /* 1: segment with the recipe's hmmnet= networks; 0: the call is aasr_run_mllr_recipe */
+  int32_t viterbi;   /* --segmode vit: the best path instead of Baum-Welch                                  */
+  double fw_beam;    /* -F: 0 keeps the default 15 (set_pruning_thresholds)                                 */
+  double bw_beam;    /* -W: 0 keeps the default 200                                                         */
+} aasr_mllr_network_options;
+void aasr_mllr_network_default_options(aasr_mllr_network_options *opt);
+/* The same loop with the recipe's hmmnet= networks in place of the .phn files (the reference's mllr -H,
+ * aku/mllr.cc:73-145): per speaker and group of at most 2^18 frames the features under the speaker's current
+ * configuration, the state rows of the model's scoring entry in the model's precision mode (in model mode: the unadapted
+ * model's, the one the statistics are collected on), one forward-backward batch (aasr_fb_batch_*), the frame-major entries
+ * (aasr_fb_batch_frame_entries_dev) and the weighted accumulation (aasr_mllr_accumulate_weighted_dev); fetch and solve
+ * per speaker as in the .phn mode.  A failed backward pass is run again up to four times with 2x ... 5x the original
+ * backward beam and the forward beam unchanged (aku/mllr.cc:87-102), new launches over the failed utterances only, with
+ * the reference's messages on stderr; an utterance that still fails is reported and adds nothing.  The frame sums s_t are
+ * checked as aasr_run_stats_networks_recipe checks them (the reference's warning above 0.02, AASR_ERR_INVALID where the
+ * reference exits below 0.01, the largest |1 - s_t| on stderr at info > 0).  With info > 0 and a non-zero total, "Total
+ * log likelihood: %f" on stderr: the sum of the forward totals of the utterances that ran.  A line without hmmnet= is the
+ * reference's error.  Refused (AASR_ERR_UNSUPPORTED): opt->ophn.  net NULL or net->networks 0: aasr_run_mllr_recipe. */
+aasr_status aasr_run_mllr_networks_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo,
+                                          const char *recipe_path, const aasr_mllr_options *opt,
+                                          const aasr_mllr_network_options *net, aasr_run_stats *stats);
 
 /* ---------------------------------------------------------------------------
  * LDA estimation: aku/lda.cc over state-segmented .phn files.
