@@ -427,6 +427,9 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_gmm_score_pitch_ok.argtypes = [vp]
     L.aasr_gmm_score_dev_pitched.argtypes = [vp, vp, i64, vp, i64, vp]
     L.aasr_lna_encode_dev_pitched.argtypes = [vp, i64, i64, i32, C.c_int, C.c_int, vp, vp, vp]
+    L.aasr_gmm_score_lna_pitched_dev.argtypes = [vp, vp, i64, vp, i64, C.c_int, C.c_int, vp, i64, vp]
+    L.aasr_gmm_score_lna_overlap_active.argtypes = [vp, i64, i64, i64]
+    L.aasr_gmm_score_lna_overlap_active.restype = C.c_int
     L.aasr_feat_write_config.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(i64)]
     L.aasr_recipe_read.argtypes = [cp, i32, i32, C.POINTER(C.c_void_p), C.POINTER(i64)]
     L.aasr_recipe_read_all.argtypes = [cp, i32, i32, i32, C.POINTER(C.c_void_p), C.POINTER(i64)]
@@ -740,6 +743,17 @@ class Gmm:
         """d_out: device buffer of frames x pitch floats (pitch >= states)."""
         check(lib().aasr_gmm_score_dev_pitched(self._h, _ptr(d_frames), d_frames.shape[0], _ptr(d_out),
                                                pitch, _stream_handle(stream)))
+
+    def score_lna_dev_pitched(self, d_frames, d_scores, pitch: int, d_bytes, normalize: bool = True, lnabytes: int = 2,
+                              chunk_frames: int = 0, stream=None) -> None:
+        """score_dev_pitched + lna_encode_dev in one call: the LNA pass of a frame chunk runs beside the scoring of the
+        next chunk where the model allows it (score_lna_overlap_active), the plain sequence otherwise; same results."""
+        check(lib().aasr_gmm_score_lna_pitched_dev(self._h, _ptr(d_frames), d_frames.shape[0], _ptr(d_scores), pitch,
+                                                   int(normalize), lnabytes, _ptr(d_bytes), chunk_frames,
+                                                   _stream_handle(stream)))
+
+    def score_lna_overlap_active(self, n_frames: int, pitch: int, chunk_frames: int = 0) -> bool:
+        return bool(lib().aasr_gmm_score_lna_overlap_active(self._h, n_frames, pitch, chunk_frames))
 
     def gauss_loglik(self, frames: np.ndarray) -> np.ndarray:
         frames = np.ascontiguousarray(frames, np.float32)

@@ -488,6 +488,24 @@ aasr_status aasr_gmm_score_dev_pitched(aasr_gmm *h, const float *d_frames, int64
   });
 }
 
+aasr_status aasr_gmm_score_lna_pitched_dev(aasr_gmm *h, const float *d_frames, int64_t F, float *d_scores, int64_t pitch,
+                                           int normalize, int lnabytes, uint8_t *d_bytes, int64_t chunk_frames,
+                                           void *stream) {
+  return guarded([&] {
+    if (!h || (F > 0 && (!d_frames || !d_scores || !d_bytes)))
+      raise(AASR_ERR_INVALID, "aasr_gmm_score_lna_pitched_dev: null argument");
+    if (lnabytes != 2 && lnabytes != 4) raise(AASR_ERR_INVALID, "lnabytes must be 2 or 4, got %d", lnabytes);
+    if (pitch < h->S) raise(AASR_ERR_INVALID, "aasr_gmm_score_lna_pitched_dev: pitch %ld < %ld states", (long)pitch, (long)h->S);
+    gmm_score_lna_chunked(h, d_frames, F, d_scores, pitch, normalize, lnabytes, d_bytes, chunk_frames, (hipStream_t)stream);
+  });
+}
+
+int aasr_gmm_score_lna_overlap_active(const aasr_gmm *h, int64_t F, int64_t pitch, int64_t chunk_frames) {
+  int active = 0;
+  if (h && F > 0 && pitch >= h->S) (void)guarded([&] { active = gmm_score_lna_chunk(h, F, pitch, chunk_frames) > 0 ? 1 : 0; });
+  return active;
+}
+
 aasr_status aasr_lna_encode(const float *state_loglik, int64_t F, int32_t S, int normalize,
                             int lnabytes, float *lp_out, uint8_t *bytes_out) {
   return guarded([&] {

@@ -450,6 +450,18 @@ struct aasr_gmm {
   // frame operand of the split-term kernels (k_frame_operand): the K x 64 operand of every block of 64 frames, formed
   // once per launch; per-launch scratch, hence mutable
   mutable aasr::DevBuf<uint32_t> fop_scratch;
+  // side stream + events of the chunked score + LNA step (gmm_score_lna.cc), created on first use
+  std::shared_ptr<void> score_lna_side;
+  // A frame operand formed ahead of the scoring calls that use it (gmm_form_frame_operand, for that step): fop_scratch
+  // holds the operand of the frames [frames, frames + F * dim) in NS terms.  A one-pivot launch_pl_t call of the same NS
+  // whose frames begin on a 512-frame boundary of that range and end inside it takes its operand from there and launches
+  // no k_frame_operand; every other call is what it was.  frames == nullptr: none.
+  struct FopAhead {
+    const float *frames = nullptr;
+    int64_t F = 0, stride = 0;
+    int ns = 0;
+  };
+  mutable FopAhead fop_ahead;
 };
 
 namespace aasr {
@@ -492,6 +504,23 @@ const int32_t *gmm_engine_colmap(const aasr_gmm *g);
 void gmm_score_launch_engine(aasr_gmm *g, const float *d_frames, int64_t F, float *d_out, int64_t pitch, hipStream_t stream);
 void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize, int lnabytes, float *d_lp,
                        uint8_t *d_bytes, hipStream_t stream, int64_t in_pitch, const int32_t *d_colmap = nullptr);
+// whether a pitched scoring call on this model is one track-kernel launch that writes rows of `pitch` floats with state s in
+// column s -- what the chunked score + LNA step overlaps (gmm_score_lna.cc)
+bool gmm_score_single_track_launch(const aasr_gmm *g, int64_t pitch);
+// ... and whether that kernel reads a frame operand formed by a k_frame_operand launch of its own (the pipelined kernel:
+// two terms, three terms up to five K slabs) or forms what it needs itself (f32 rows, the wave-group kernel): 2 / 3 = the
+// operand's terms, 0 = none.  gmm_form_frame_operand() launches that operand for F frames and leaves it on the handle
+// (aasr_gmm::fop_ahead) until gmm_drop_frame_operand().
+int gmm_score_frame_operand_terms(const aasr_gmm *g);
+void gmm_form_frame_operand(aasr_gmm *g, const float *d_frames, int64_t F, hipStream_t stream);
+void gmm_drop_frame_operand(const aasr_gmm *g);
+// scores + LNA bytes of F frames: frame chunks scored on `stream`, the LNA pass of a chunk on the handle's side stream
+// beside the scoring of the next (chunk_frames = 0: one round of the chip per chunk); the plain sequence where
+// gmm_score_single_track_launch() says no.  gmm_score_lna_chunk(): the frames per chunk such a call takes, 0: the plain
+// sequence (raises AASR_ERR_INVALID for a chunk_frames that is no multiple of 512)
+int64_t gmm_score_lna_chunk(const aasr_gmm *g, int64_t F, int64_t pitch, int64_t chunk_frames);
+void gmm_score_lna_chunked(aasr_gmm *g, const float *d_frames, int64_t F, float *d_scores, int64_t pitch, int normalize,
+                           int lnabytes, uint8_t *d_bytes, int64_t chunk_frames, hipStream_t stream);
 void gmm_build_centred(aasr_gmm *g);
 void gmm_build_fullcov(aasr_gmm *g);
 void gmm_full_launch(aasr_gmm *g, const float *d_frames, int64_t F, float *d_out,

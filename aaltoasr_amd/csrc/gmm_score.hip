@@ -571,6 +571,41 @@ bool gmm_score_pitch_ok(const aasr_gmm *g) {
   return (g->precision == AASR_PREC_F32 || g->precision == AASR_PREC_BF16X3 || g->precision == AASR_PREC_F16X2) && L.ok;
 }
 
+// The cases in which gmm_score_launch_pitched() is one launch of a track kernel (plus its frame operand) that writes state s
+// into column s: a one-pivot two-term, three-term or f32 layout with nothing beside it -- no engine parts, clustering, class
+// routing, outlier or centred pass, frame transform or dimension parts.
+bool gmm_score_single_track_launch(const aasr_gmm *g, int64_t pitch) {
+  if (pitch < g->S || !g->dim_parts.empty() || g->cl.enabled || g->class_routing || g->host.factor_path()) return false;
+  if (g->precision != AASR_PREC_F32 && g->precision != AASR_PREC_BF16X3 && g->precision != AASR_PREC_F16X2) return false;
+  if (gmm_engine_parts_active(g) || g->ill_conditioned || g->hyb_enabled || g->xf_a.p) return false;
+  if ((g->layout_mask & 3) != 3) return false;
+  const TrackLayout &L = g->paired.ok ? g->paired : g->tracks;
+  if (!L.ok || L.n_pg > 1) return false;
+  return pitch == g->S || gmm_score_pitch_ok(g);
+}
+
+// Mirrors launch_bf16 / launch_split / launch_split_instance for the layout gmm_score_launch_pitched scores a one-pivot
+// model with: two terms where the precision asks for them and the layout has the rows, else three -- on the pipelined
+// kernel up to five K slabs, on the wave-group kernel (no operand launch) beyond; no split rows: the f32 track kernel.
+int gmm_score_frame_operand_terms(const aasr_gmm *g) {
+  if (!g->use_bf16x3) return 0;
+  const TrackLayout &L = g->paired.ok ? g->paired : g->tracks;
+  if (!L.ok || L.n_pg > 1) return 0;
+  if (L.nk16 < 1 || L.nk16 == 7 || L.nk16 > 8) return 0;   // (no split instance: launch_split returns false)
+  if (g->precision == AASR_PREC_F16X2 && L.a16h.p) return 2;
+  return L.a16.p && L.nk16 <= 5 ? 3 : 0;
+}
+
+void gmm_form_frame_operand(aasr_gmm *g, const float *d_frames, int64_t F, hipStream_t stream) {
+  const TrackLayout &L = g->paired.ok ? g->paired : g->tracks;
+  const int ns = gmm_score_frame_operand_terms(g);
+  if (ns == 2) form_frame_operand<2>(g, L, d_frames, F, stream);
+  else if (ns == 3) form_frame_operand<3>(g, L, d_frames, F, stream);
+  else g->fop_ahead = aasr_gmm::FopAhead();
+}
+
+void gmm_drop_frame_operand(const aasr_gmm *g) { g->fop_ahead = aasr_gmm::FopAhead(); }
+
 // ---------------------------------------------------------------------------
 // The engine's own score layout (recipe driver, aasr_run_utterance, aasr_gmm_score_lna_dev: scores that only the LNA pass
 // reads): rows padded to whole lines; a model with engine parts: every part in its own column range, read through a

@@ -373,5 +373,6 @@ static void launch_bf16_t(const aasr_gmm *g, const TrackLayout &L, const float *
 
 template bool launch_split<3>(const aasr_gmm *, const TrackLayout &, const float *, int64_t, float *, hipStream_t,
                               const ClusterArgs *, int64_t);
+template void form_frame_operand<3>(const aasr_gmm *, const TrackLayout &, const float *, int64_t, hipStream_t);
 
 }  // namespace aasr

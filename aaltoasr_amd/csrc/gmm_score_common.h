@@ -244,6 +244,8 @@ bool launch_tracks(const aasr_gmm *g, const TrackLayout &L, const float *d_frame
 template <int NS>
 bool launch_split(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F,
                   float *d_out, hipStream_t stream, const ClusterArgs *cl = nullptr, int64_t pitch = 0);
+template <int NS>
+void form_frame_operand(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F, hipStream_t stream);
 // gmm_score_exact.hip
 extern double g_score_pass_bytes;
 bool launch_centred_ops(const aasr_gmm *g, const CentredOps &ops, int dimp, const float *d_frames,

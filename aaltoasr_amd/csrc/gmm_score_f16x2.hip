@@ -16,6 +16,7 @@ namespace aasr {
 
 template bool launch_split<2>(const aasr_gmm *, const TrackLayout &, const float *, int64_t, float *, hipStream_t,
                               const ClusterArgs *, int64_t);
+template void form_frame_operand<2>(const aasr_gmm *, const TrackLayout &, const float *, int64_t, hipStream_t);
 
 // Diagnostic (bench.py): milliseconds of ONE k_frame_operand launch over F frames for the layout and arithmetic a scoring
 // call would use now -- the launch that precedes k_gmm_diag_score_pl in every scoring call, so that the bench can price
@@ -41,6 +42,13 @@ extern "C" double aasr_debug_frame_operand_ms(aasr_gmm *g, const float *d_frames
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return (double)ms / reps;
+}
+
+// Diagnostic (tests/test_lna_unmapped_notes.py): dynamic LDS bytes of a workgroup of the bench form -- 39 dimensions
+// (five slabs), grouped tracks, two terms -- in its 8-wave (wide) or 4-wave shape; the code object's notes hold only the
+// static part
+extern "C" int aasr_debug_pl_bench_smem_bytes(int wide) {
+  return wide ? PlSmem<5, true, true, 2>::kBytes : PlSmem<5, true, false, 2>::kBytes;
 }
 }  // namespace aasr
 

@@ -912,7 +912,21 @@ static void launch_pl_t(const aasr_gmm *g, const TrackLayout &L, const float *d_
       return;
     }
   }
-  const u32x4 *fop = frame_operand<NS>(g, L, d_frames, F, blocks * NW, stream, &pg.fop_stride);
+  const u32x4 *fop = nullptr;
+  const aasr_gmm::FopAhead &ah = g->fop_ahead;
+  if (!multi && ah.frames && ah.ns == NS && d_frames >= ah.frames) {
+    // an operand formed ahead (form_frame_operand below) that covers this call's frames from a 512-frame boundary on: its
+    // image is whole 512-frame blocks, so the blocks of either wave form that begin there lie inside it
+    const int64_t off = d_frames - ah.frames, unit = (int64_t)512 * g->dim;
+    if (off % unit == 0 && off / g->dim + F <= ah.F) {
+      fop = (const u32x4 *)g->fop_scratch.p + (size_t)(off / g->dim / 64) * ((size_t)L.nk16 * NS * 2 * 64);
+      pg.fop_stride = ah.stride;
+    }
+  }
+  if (!fop) {
+    g->fop_ahead = aasr_gmm::FopAhead();   // (the launch below rewrites the scratch an operand formed ahead lives in)
+    fop = frame_operand<NS>(g, L, d_frames, F, blocks * NW, stream, &pg.fop_stride);
+  }
   if (multi) pg.colend = L.pg_colend.p;
   if constexpr (GROUPED && NS == 2 && !CL) {
     // outlier routing with the merge in the close logic: the launcher has put the outliers' partial sums on the handle
@@ -977,6 +991,20 @@ static void launch_split_n(const aasr_gmm *g, const TrackLayout &L, const float 
   } else {
     launch_split_tracks<N, NS, false, false>(g, L, d_frames, F, d_out, stream, none, pitch);
   }
+}
+
+// The frame operand of F frames of a one-pivot layout, formed ahead of the scoring calls that use it (launch_pl_t takes it
+// for calls inside the range): whole 512-frame blocks, which covers the blocks of the 8-wave and of the 4-wave form.
+template <int NS>
+void form_frame_operand(const aasr_gmm *g, const TrackLayout &L, const float *d_frames, int64_t F, hipStream_t stream) {
+  g->fop_ahead = aasr_gmm::FopAhead();
+  if (F <= 0 || L.n_pg > 1) return;
+  int64_t stride = 0;
+  frame_operand<NS>(g, L, d_frames, F, (F + 511) / 512 * 8, stream, &stride);
+  g->fop_ahead.frames = d_frames;
+  g->fop_ahead.F = F;
+  g->fop_ahead.stride = stride;
+  g->fop_ahead.ns = NS;
 }
 
 // NS = 3: three bf16 terms (AASR_PREC_BF16X3); NS = 2: two fp16 terms (AASR_PREC_F16X2)

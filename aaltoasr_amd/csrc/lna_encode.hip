@@ -92,7 +92,10 @@ __global__ __launch_bounds__(256) void k_state_norm_lna(
 
 // Register-resident variant for S <= 256*VPT: one global read of the row, the
 // three passes (max, sum, pack) run on registers.
-template <int VPT>
+// MAPPED = false (no column map: state i is column i) keeps no col[] and reads row[tid + 256 * j]: VPT registers
+// fewer, which puts the <13> instance under the 96 VGPRs that two scoring waves leave free on a SIMD
+// (gmm_score_lna_chunked, tests/test_lna_unmapped_notes.py).
+template <int VPT, bool MAPPED>
 __global__ __launch_bounds__(256) void k_state_norm_lna_reg(
     const float *__restrict__ loglik, int64_t F, int S, int64_t in_pitch, int normalize, int lnabytes,
     float *__restrict__ lp_out, uint8_t *__restrict__ bytes_out, const int32_t *__restrict__ colmap) {
@@ -102,11 +105,13 @@ __global__ __launch_bounds__(256) void k_state_norm_lna_reg(
   constexpr int JSAFE = VPT == 4 ? 0 : VPT == 8 ? 4 : VPT == 10 ? 8 : VPT == 13 ? 10 : VPT == 16 ? 13 : 0;
   // colmap (engine-internal score layout of a routed model, gmm_engine_colmap): state i sits in column colmap[i] of a
   // score row; the same for every frame, so a thread looks its columns up once
-  int col[VPT];
+  int col[MAPPED ? VPT : 1];
+  if constexpr (MAPPED) {
 #pragma unroll
-  for (int j = 0; j < VPT; j++) {
-    const int i = tid + 256 * j;
-    col[j] = (colmap && (j < JSAFE || i < S)) ? colmap[i] : i;
+    for (int j = 0; j < VPT; j++) {
+      const int i = tid + 256 * j;
+      col[j] = (colmap && (j < JSAFE || i < S)) ? colmap[i] : i;
+    }
   }
   // a workgroup walks frames blockIdx.x, + gridDim.x, ...; the next frame's row is requested
   // before this one is reduced (the four barriers of a frame leave nothing else to hide the
@@ -117,7 +122,7 @@ __global__ __launch_bounds__(256) void k_state_norm_lna_reg(
 #pragma unroll
     for (int j = 0; j < VPT; j++) {
       const int i = tid + 256 * j;
-      vn[j] = ((j < JSAFE || i < S) && (int64_t)blockIdx.x < F) ? row[col[j]] : -INFINITY;
+      vn[j] = ((j < JSAFE || i < S) && (int64_t)blockIdx.x < F) ? row[MAPPED ? col[j] : i] : -INFINITY;
     }
   }
   for (int64_t f = blockIdx.x; f < F; f += gridDim.x) {
@@ -129,7 +134,7 @@ __global__ __launch_bounds__(256) void k_state_norm_lna_reg(
 #pragma unroll
       for (int j = 0; j < VPT; j++) {
         const int i = tid + 256 * j;
-        vn[j] = (j < JSAFE || i < S) ? row[col[j]] : -INFINITY;
+        vn[j] = (j < JSAFE || i < S) ? row[MAPPED ? col[j] : i] : -INFINITY;
       }
     }
     lna_row_from_registers<VPT, JSAFE>(v, S, tid, wave, lane, red, normalize, lnabytes, f, true, lp_out, bytes_out);
@@ -177,6 +182,17 @@ void lna_encode_f64_launch(const double *d_lik, int64_t F, int S, int normalize,
   AASR_HIP(hipGetLastError());
 }
 
+template <int VPT>
+static void launch_lna_reg(unsigned blocks, hipStream_t stream, const float *d_loglik, int64_t F, int S, int64_t in_pitch,
+                           int normalize, int lnabytes, float *d_lp, uint8_t *d_bytes, const int32_t *d_colmap) {
+  if (d_colmap)
+    hipLaunchKernelGGL((k_state_norm_lna_reg<VPT, true>), dim3(blocks), dim3(256), 0, stream, d_loglik, F, S, in_pitch,
+                       normalize, lnabytes, d_lp, d_bytes, d_colmap);
+  else
+    hipLaunchKernelGGL((k_state_norm_lna_reg<VPT, false>), dim3(blocks), dim3(256), 0, stream, d_loglik, F, S, in_pitch,
+                       normalize, lnabytes, d_lp, d_bytes, d_colmap);
+}
+
 void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize,
                        int lnabytes, float *d_lp, uint8_t *d_bytes, hipStream_t stream, int64_t in_pitch,
                        const int32_t *d_colmap) {
@@ -188,24 +204,22 @@ void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize,
   // row prefetched
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (S <= 256 * 16) blocks = std::min<int64_t>(blocks, (int64_t)cus * 32);  // measured: 2.56 ms at 4 per CU, 2.16 at 32, flat above
+  // 32 per CU.  Historical figure, taken when the kernel held 4 waves per SIMD with the column map in registers: 2.56 ms at
+  // 4 per CU, 2.16 at 32, flat above.  The unmapped <13> instance (90 VGPRs) holds 5; the rule has not been re-measured since.
+  if (S <= 256 * 16) blocks = std::min<int64_t>(blocks, (int64_t)cus * 32);
+  const unsigned nb = (unsigned)blocks;
   if (S <= 256 * 4)
-    hipLaunchKernelGGL(k_state_norm_lna_reg<4>, dim3((unsigned)blocks), dim3(256), 0, stream,
-                       d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
+    launch_lna_reg<4>(nb, stream, d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
   else if (S <= 256 * 8)
-    hipLaunchKernelGGL(k_state_norm_lna_reg<8>, dim3((unsigned)blocks), dim3(256), 0, stream,
-                       d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
+    launch_lna_reg<8>(nb, stream, d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
   else if (S <= 256 * 10)
-    hipLaunchKernelGGL(k_state_norm_lna_reg<10>, dim3((unsigned)blocks), dim3(256), 0, stream,
-                       d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
+    launch_lna_reg<10>(nb, stream, d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
   else if (S <= 256 * 13)
-    hipLaunchKernelGGL(k_state_norm_lna_reg<13>, dim3((unsigned)blocks), dim3(256), 0, stream,
-                       d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
+    launch_lna_reg<13>(nb, stream, d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
   else if (S <= 256 * 16)
-    hipLaunchKernelGGL(k_state_norm_lna_reg<16>, dim3((unsigned)blocks), dim3(256), 0, stream,
-                       d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
+    launch_lna_reg<16>(nb, stream, d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
   else
-    hipLaunchKernelGGL(k_state_norm_lna, dim3((unsigned)blocks), dim3(256), 0, stream, d_loglik,
+    hipLaunchKernelGGL(k_state_norm_lna, dim3(nb), dim3(256), 0, stream, d_loglik,
                        F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes);
   AASR_HIP(hipGetLastError());
 }

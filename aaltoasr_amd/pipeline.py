@@ -48,8 +48,8 @@ class FullChainBench:
 
     def step(self) -> None:
         self.feat.run_batch_dev(self.d_pcm, self.pcm_off, self.frame_off, self.d_fea, self.stream)
-        self.gmm.score_dev_pitched(self.d_fea, self.d_ll, self.pitch, self.stream)
-        capi.lna_encode_dev(self.d_ll, True, self.lnabytes, None, self.d_bytes, self.stream, num_states=self.S)
+        # scoring in frame chunks, the LNA pass of a chunk beside the scoring of the next (aasr_gmm_score_lna_pitched_dev)
+        self.gmm.score_lna_dev_pitched(self.d_fea, self.d_ll, self.pitch, self.d_bytes, True, self.lnabytes, 0, self.stream)
 
     def score_only(self) -> None:
         self.gmm.score_dev_pitched(self.d_fea, self.d_ll, self.pitch, self.stream)

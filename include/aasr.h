@@ -364,6 +364,19 @@ aasr_status aasr_lna_encode_dev(const float *d_state_loglik, int64_t F,
                                 int32_t S, int normalize, int lnabytes,
                                 float *d_lp_out, uint8_t *d_bytes_out,
                                 void *stream);
+/* aasr_gmm_score_dev_pitched followed by aasr_lna_encode_dev_pitched (bytes only) as one call: afterwards d_scores
+ * [F x pitch] and d_bytes [F x S x lnabytes] hold exactly what the two calls leave there, ordered on `stream`.  Where the
+ * scoring call is one launch of a track kernel (one-pivot two-term, three-term or f32 layout; no engine parts, clustering,
+ * class routing, AASR_PREC_F64 or a pitch the kernel cannot write) the frames are scored in chunks and the LNA pass of a
+ * chunk runs on a second stream, owned by the handle, beside the scoring of the next chunk; `stream` waits for the last
+ * LNA pass before the call returns to it.  chunk_frames: frames per chunk, a positive multiple of 512, or 0 for the
+ * automatic choice (one 512-frame block per CU per chunk; fewer than two such chunks: the plain sequence).  Every other
+ * case runs the plain sequence on `stream`.  aasr_gmm_score_lna_overlap_active() says whether a call with these arguments
+ * takes the two-stream form (1) or the plain sequence (0). */
+aasr_status aasr_gmm_score_lna_pitched_dev(aasr_gmm *h, const float *d_frames, int64_t F, float *d_scores, int64_t pitch,
+                                           int normalize, int lnabytes, uint8_t *d_bytes, int64_t chunk_frames,
+                                           void *stream);
+int aasr_gmm_score_lna_overlap_active(const aasr_gmm *h, int64_t F, int64_t pitch, int64_t chunk_frames);
 /* Frames straight to LNA codes on the device: aasr_gmm_score_dev followed by
  * aasr_lna_encode_dev, except that the engine may keep the state scores in its
  * own layout in between (rows padded to whole cache lines; a model whose conditioning needs several pivots -- or three
