@@ -504,6 +504,9 @@ const int32_t *gmm_engine_colmap(const aasr_gmm *g);
 void gmm_score_launch_engine(aasr_gmm *g, const float *d_frames, int64_t F, float *d_out, int64_t pitch, hipStream_t stream);
 void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize, int lnabytes, float *d_lp,
                        uint8_t *d_bytes, hipStream_t stream, int64_t in_pitch, const int32_t *d_colmap = nullptr);
+// the same with the grid of the register-resident instances as workgroups per CU (lna_encode_launch: 32)
+void lna_encode_launch_grid(const float *d_loglik, int64_t F, int S, int normalize, int lnabytes, float *d_lp,
+                            uint8_t *d_bytes, hipStream_t stream, int64_t in_pitch, const int32_t *d_colmap, int wgs_per_cu);
 // whether a pitched scoring call on this model is one track-kernel launch that writes rows of `pitch` floats with state s in
 // column s -- what the chunked score + LNA step overlaps (gmm_score_lna.cc)
 bool gmm_score_single_track_launch(const aasr_gmm *g, int64_t pitch);
@@ -515,10 +518,37 @@ int gmm_score_frame_operand_terms(const aasr_gmm *g);
 void gmm_form_frame_operand(aasr_gmm *g, const float *d_frames, int64_t F, hipStream_t stream);
 void gmm_drop_frame_operand(const aasr_gmm *g);
 // scores + LNA bytes of F frames: frame chunks scored on `stream`, the LNA pass of a chunk on the handle's side stream
-// beside the scoring of the next (chunk_frames = 0: one round of the chip per chunk); the plain sequence where
+// beside the scoring of the next (chunk_frames = 0: half a 512-frame block per CU per chunk); the plain sequence where
 // gmm_score_single_track_launch() says no.  gmm_score_lna_chunk(): the frames per chunk such a call takes, 0: the plain
 // sequence (raises AASR_ERR_INVALID for a chunk_frames that is no multiple of 512)
 int64_t gmm_score_lna_chunk(const aasr_gmm *g, int64_t F, int64_t pitch, int64_t chunk_frames);
+// The schedule of that call as data (gmm_score_lna.cc).  plan_score_lna() is a pure host function: the scoring launches in
+// time order and the LNA segments in side-stream order, each with the index of the scoring launch whose event it waits
+// for.  Every frame is in exactly one launch and one segment, a segment's frames lie in launches up to the one it waits
+// for, and every scoring range begins on a multiple of 512 frames.
+// The defaults are the measured choice: remainder first and half-round chunks pay; a share under 1 lowers
+// what the scoring launches pay for the company by less than the longer last pass costs, and no other grid is faster.
+struct ScoreLnaKnobs {
+  bool remainder_first = true;   // the frames past the last whole chunk are scored first and alone
+  double share = 1.0;            // of a chunk's frames: the most an LNA release behind a launch that another one follows
+  int chunk_div = 2;             // automatic chunk: one 512-frame block per CU, over this
+  int lna_grid = 32;             // workgroups per CU of an LNA segment
+};
+struct ScoreLnaRange {
+  int64_t f0, n;
+};
+struct ScoreLnaSegment {
+  int64_t f0, n;
+  int wait;
+};
+struct ScoreLnaPlan {
+  int64_t chunk = 0;   // frames per chunk, 0: the plain sequence (one launch, one segment)
+  std::vector<ScoreLnaRange> score;
+  std::vector<ScoreLnaSegment> lna;
+};
+ScoreLnaKnobs score_lna_default_knobs();
+int64_t score_lna_chunk_frames(int64_t F, int cus, int64_t chunk_frames, const ScoreLnaKnobs &k);
+ScoreLnaPlan plan_score_lna(int64_t F, int cus, int64_t chunk_frames, const ScoreLnaKnobs &k);
 void gmm_score_lna_chunked(aasr_gmm *g, const float *d_frames, int64_t F, float *d_scores, int64_t pitch, int normalize,
                            int lnabytes, uint8_t *d_bytes, int64_t chunk_frames, hipStream_t stream);
 void gmm_build_centred(aasr_gmm *g);

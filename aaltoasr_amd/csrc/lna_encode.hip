@@ -193,9 +193,12 @@ static void launch_lna_reg(unsigned blocks, hipStream_t stream, const float *d_l
                        normalize, lnabytes, d_lp, d_bytes, d_colmap);
 }
 
-void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize,
-                       int lnabytes, float *d_lp, uint8_t *d_bytes, hipStream_t stream, int64_t in_pitch,
-                       const int32_t *d_colmap) {
+// The launch with the workgroups per CU of the register-resident instances given (the chunked score + LNA step, whose
+// passes run beside a scoring kernel: gmm_score_lna.cc).  Which workgroup encodes a frame changes no byte of it.
+void lna_encode_launch_grid(const float *d_loglik, int64_t F, int S, int normalize,
+                            int lnabytes, float *d_lp, uint8_t *d_bytes, hipStream_t stream, int64_t in_pitch,
+                            const int32_t *d_colmap, int wgs_per_cu) {
+  if (wgs_per_cu < 1 || wgs_per_cu > 1024) raise(AASR_ERR_INVALID, "LNA grid of %d workgroups per CU", wgs_per_cu);
   if (in_pitch <= 0) in_pitch = S;  // row stride of the input in floats
   if (F <= 0 || S <= 0) return;
   if (d_colmap && S > 256 * 16) raise(AASR_ERR_UNSUPPORTED, "a column map needs the register-resident LNA kernels (S <= 4096)");
@@ -205,8 +208,10 @@ void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize,
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   // 32 per CU.  Historical figure, taken when the kernel held 4 waves per SIMD with the column map in registers: 2.56 ms at
-  // 4 per CU, 2.16 at 32, flat above.  The unmapped <13> instance (90 VGPRs) holds 5; the rule has not been re-measured since.
-  if (S <= 256 * 16) blocks = std::min<int64_t>(blocks, (int64_t)cus * 32);
+  // 4 per CU, 2.16 at 32, flat above.  The unmapped <13> instance (90 VGPRs) holds 5; re-measured with it in the chunked
+  // score + LNA step, where the passes run beside a scoring kernel: 64, 128 and 256 per CU are within 0.03 ms of 32 per
+  // step and never faster in all four alternating runs, so 32 stays for every caller.
+  if (S <= 256 * 16) blocks = std::min<int64_t>(blocks, (int64_t)cus * wgs_per_cu);
   const unsigned nb = (unsigned)blocks;
   if (S <= 256 * 4)
     launch_lna_reg<4>(nb, stream, d_loglik, F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes, d_colmap);
@@ -222,6 +227,12 @@ void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize,
     hipLaunchKernelGGL(k_state_norm_lna, dim3(nb), dim3(256), 0, stream, d_loglik,
                        F, S, in_pitch, normalize, lnabytes, d_lp, d_bytes);
   AASR_HIP(hipGetLastError());
+}
+
+void lna_encode_launch(const float *d_loglik, int64_t F, int S, int normalize,
+                       int lnabytes, float *d_lp, uint8_t *d_bytes, hipStream_t stream, int64_t in_pitch,
+                       const int32_t *d_colmap) {
+  lna_encode_launch_grid(d_loglik, F, S, normalize, lnabytes, d_lp, d_bytes, stream, in_pitch, d_colmap, 32);
 }
 
 }  // namespace aasr

@@ -368,9 +368,10 @@ aasr_status aasr_lna_encode_dev(const float *d_state_loglik, int64_t F,
  * [F x pitch] and d_bytes [F x S x lnabytes] hold exactly what the two calls leave there, ordered on `stream`.  Where the
  * scoring call is one launch of a track kernel (one-pivot two-term, three-term or f32 layout; no engine parts, clustering,
  * class routing, AASR_PREC_F64 or a pitch the kernel cannot write) the frames are scored in chunks and the LNA pass of a
- * chunk runs on a second stream, owned by the handle, beside the scoring of the next chunk; `stream` waits for the last
- * LNA pass before the call returns to it.  chunk_frames: frames per chunk, a positive multiple of 512, or 0 for the
- * automatic choice (one 512-frame block per CU per chunk; fewer than two such chunks: the plain sequence).  Every other
+ * chunk runs on a second stream, owned by the handle, beside the scoring of the next chunk (the frames past the last
+ * whole chunk are scored first); `stream` waits for the last LNA pass before the call returns to it.  chunk_frames: frames
+ * per chunk, a positive multiple of 512, or 0 for the automatic choice (half a 512-frame block per CU per chunk; fewer
+ * than two 512-frame blocks per CU in all: the plain sequence).  Every other
  * case runs the plain sequence on `stream`.  aasr_gmm_score_lna_overlap_active() says whether a call with these arguments
  * takes the two-stream form (1) or the plain sequence (0). */
 aasr_status aasr_gmm_score_lna_pitched_dev(aasr_gmm *h, const float *d_frames, int64_t F, float *d_scores, int64_t pitch,
