@@ -427,6 +427,7 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_gmm_score_pitch_ok.argtypes = [vp]
     L.aasr_gmm_score_dev_pitched.argtypes = [vp, vp, i64, vp, i64, vp]
     L.aasr_lna_encode_dev_pitched.argtypes = [vp, i64, i64, i32, C.c_int, C.c_int, vp, vp, vp]
+    L.aasr_lna_encode_dev_grid.argtypes = [vp, i64, i64, i32, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     L.aasr_gmm_score_lna_pitched_dev.argtypes = [vp, vp, i64, vp, i64, C.c_int, C.c_int, vp, i64, vp]
     L.aasr_gmm_score_lna_overlap_active.argtypes = [vp, i64, i64, i64]
     L.aasr_gmm_score_lna_overlap_active.restype = C.c_int
@@ -773,10 +774,17 @@ def lna_encode(state_loglik: np.ndarray, normalize: bool = True, lnabytes: int =
 
 
 def lna_encode_dev(d_loglik, normalize: bool, lnabytes: int, d_lp=None, d_bytes=None, stream=None,
-                   num_states: Optional[int] = None):
-    """d_loglik: [F x S], or [F x pitch] with num_states = S < pitch (padded rows)."""
+                   num_states: Optional[int] = None, colmap=None, wgs_per_cu: Optional[int] = None):
+    """d_loglik: [F x S], or [F x pitch] with num_states = S < pitch (padded rows).
+    colmap (device int32 [S]: state i sits in column colmap[i]) and wgs_per_cu (the grid of the register-resident
+    kernels, the library's 32 when only the map is given) go through aasr_lna_encode_dev_grid."""
     F, P = d_loglik.shape
-    if num_states is None or num_states == P:
+    if colmap is not None or wgs_per_cu is not None:
+        check(lib().aasr_lna_encode_dev_grid(_ptr(d_loglik), P, F, P if num_states is None else num_states,
+                                             int(normalize), lnabytes, _ptr(colmap),
+                                             32 if wgs_per_cu is None else wgs_per_cu, _ptr(d_lp), _ptr(d_bytes),
+                                             _stream_handle(stream)))
+    elif num_states is None or num_states == P:
         check(lib().aasr_lna_encode_dev(_ptr(d_loglik), F, P, int(normalize), lnabytes, _ptr(d_lp),
                                         _ptr(d_bytes), _stream_handle(stream)))
     else:

@@ -476,6 +476,20 @@ aasr_status aasr_lna_encode_dev_pitched(const float *d_state_loglik, int64_t in_
   });
 }
 
+aasr_status aasr_lna_encode_dev_grid(const float *d_state_loglik, int64_t in_pitch, int64_t F, int32_t S,
+                                     int normalize, int lnabytes, const int32_t *d_colmap, int wgs_per_cu,
+                                     float *d_lp_out, uint8_t *d_bytes_out, void *stream) {
+  return guarded([&] {
+    if (lnabytes != 2 && lnabytes != 4)
+      raise(AASR_ERR_INVALID, "lnabytes must be 2 or 4, got %d", lnabytes);
+    if (F > 0 && !d_state_loglik) raise(AASR_ERR_INVALID, "aasr_lna_encode_dev_grid: null input");
+    if (S <= 0 || in_pitch < S) raise(AASR_ERR_INVALID, "aasr_lna_encode_dev_grid: need 0 < S <= in_pitch");
+    require_device();
+    lna_encode_launch_grid(d_state_loglik, F, S, normalize, lnabytes, d_lp_out, d_bytes_out,
+                           (hipStream_t)stream, in_pitch, d_colmap, wgs_per_cu);
+  });
+}
+
 int aasr_gmm_score_pitch_ok(const aasr_gmm *h) { return h && gmm_score_pitch_ok(h) ? 1 : 0; }
 
 aasr_status aasr_gmm_score_dev_pitched(aasr_gmm *h, const float *d_frames, int64_t F,

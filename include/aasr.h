@@ -364,6 +364,15 @@ aasr_status aasr_lna_encode_dev(const float *d_state_loglik, int64_t F,
                                 int32_t S, int normalize, int lnabytes,
                                 float *d_lp_out, uint8_t *d_bytes_out,
                                 void *stream);
+/* aasr_lna_encode_dev_pitched with the two further arguments of the launch that the engine sets for itself.  d_colmap
+ * (device, S entries, may be NULL): state i is read from column d_colmap[i] of an input row, every entry in
+ * [0, in_pitch) -- the engine-internal score layout of a routed model; needs S <= 4096 (AASR_ERR_UNSUPPORTED above).
+ * wgs_per_cu: the grid of the register-resident kernels (S <= 4096) in workgroups per CU, 1..1024 (AASR_ERR_INVALID
+ * outside; every other entry point runs 32).  Neither changes a byte of the output; what the tests of the LNA pass
+ * hold it to. */
+aasr_status aasr_lna_encode_dev_grid(const float *d_state_loglik, int64_t in_pitch, int64_t F, int32_t S,
+                                     int normalize, int lnabytes, const int32_t *d_colmap, int wgs_per_cu,
+                                     float *d_lp_out, uint8_t *d_bytes_out, void *stream);
 /* aasr_gmm_score_dev_pitched followed by aasr_lna_encode_dev_pitched (bytes only) as one call: afterwards d_scores
  * [F x pitch] and d_bytes [F x S x lnabytes] hold exactly what the two calls leave there, ordered on `stream`.  Where the
  * scoring call is one launch of a track kernel (one-pivot two-term, three-term or f32 layout; no engine parts, clustering,

@@ -40,3 +40,13 @@ def test_argument_validation(capi):
     assert L.aasr_gmm_create_diag(0, 1, None, None, 1, None, None, None, C.byref(h)) == capi.AASR_ERR_INVALID
     assert L.aasr_lna_encode(None, 1, 3, 1, 3, None, None) == capi.AASR_ERR_INVALID
     assert b"lnabytes" in L.aasr_last_error()
+    # the entry point with a column map and a grid makes the checks of aasr_lna_encode_dev_pitched before it looks for a device
+    assert "aasr_lna_encode_dev_grid" in capi.declared_symbols()
+    assert L.aasr_lna_encode_dev_grid(None, 8, 1, 8, 1, 3, None, 32, None, None, None) == capi.AASR_ERR_INVALID
+    assert b"lnabytes" in L.aasr_last_error()
+    assert L.aasr_lna_encode_dev_grid(None, 8, 1, 8, 1, 2, None, 32, None, None, None) == capi.AASR_ERR_INVALID
+    assert b"null input" in L.aasr_last_error()
+    dummy = np.zeros(8, np.float32)       # never read: S <= 0 and S > in_pitch are refused first
+    for S in (0, 9):
+        assert L.aasr_lna_encode_dev_grid(dummy.ctypes.data, 8, 1, S, 1, 2, None, 32, None, None, None) == capi.AASR_ERR_INVALID
+        assert b"in_pitch" in L.aasr_last_error()
