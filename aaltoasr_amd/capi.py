@@ -930,6 +930,18 @@ def debug_cluster_heap(on: bool) -> None:
     L.aasr_debug_cluster_heap(int(on))
 
 
+def debug_lna_frames_per_pass(q: int) -> None:
+    """Diagnostic: frame rows per workgroup pass of later LNA launches of this process -- 1: the one-frame kernel, 2 or 4:
+    the multi-frame kernel where a call qualifies (2-byte codes, no float output, no column map, S in the <13> range);
+    negative: the compiled-in value.  The bytes do not depend on it."""
+    if q >= 0 and q not in (1, 2, 4):
+        raise ValueError("frames per pass: 1, 2, 4 or a negative value, got %r" % (q,))
+    L = lib()
+    L.aasr_debug_lna_frames_per_pass.argtypes = [C.c_int]
+    L.aasr_debug_lna_frames_per_pass.restype = None
+    L.aasr_debug_lna_frames_per_pass(int(q))
+
+
 def recipe_frame_limits(start_time: float, end_time: float, frame_rate: float):
     """(start_frame, end_frame) of aku/phone_probs.cc:199-206, float arithmetic."""
     a, b = C.c_int32(), C.c_int32()

@@ -3,9 +3,12 @@
 //
 // The two stages want complementary resources: the scoring kernel is bound by the matrix pipe and leaves HBM at an eighth
 // of its rate, the LNA pass is bound by vector issue and HBM and leaves the matrix pipe idle.  They fit on a CU together:
-// a scoring workgroup puts two waves of 208 allocated VGPRs on every SIMD, the unmapped LNA instance
-// (k_state_norm_lna_reg<VPT, false>) needs at most 96, and 64 B of LDS beside the scoring kernel's 131 264
-// (tests/test_lna_unmapped_notes.py holds the three figures).
+// a scoring workgroup puts two waves of 208 allocated VGPRs on every SIMD, and what an LNA segment runs has to fit into the
+// 96 and the 32 576 B of LDS that leaves: the multi-frame kernel of the headline's state range (k_state_norm_lna_multi<13,
+// 4>: four frame rows per workgroup pass, 94 VGPRs, 13 856 B -- three barriers and one logarithm per wave for four frames
+// where the one-frame kernel pays four barriers and a logarithm in every wave per frame) and, for every other S, the
+// unmapped one-frame instance (k_state_norm_lna_reg<VPT, false>: at most 96, 64 B).  tests/test_lna_multi_notes.py and
+// tests/test_lna_unmapped_notes.py hold the figures; lna_encode_launch_grid chooses, and the bytes do not depend on it.
 //
 // The schedule is data: plan_score_lna() -- a pure host function -- returns the scoring launches in time order and the LNA
 // segments with the launch each waits for; gmm_score_lna_chunked() issues it.  With W whole chunks and a remainder:
@@ -18,11 +21,13 @@
 //     and alone: its many short workgroups end in several rounds, and every round boundary on every CU is an opening for
 //     pending LNA workgroups.  Its LNA segment runs beside the first whole chunk, under which nothing could hide before.
 //   - Behind every launch but the last at most `share` of a chunk's frames is released, oldest first, and what
-//     accumulates is encoded behind the last launch, at full rate on an empty chip.  Beside a scoring kernel the LNA pass
-//     gets through about 0.7 of a chunk; at a share of 1 workgroups are still pending when the scoring launch ends, take
-//     every CU, and the next scoring launch's workgroups are placed one by one as that flood drains.  Measured, holding
-//     frames back removes the flood (share 0.7: no LNA kernel runs at the start of a scoring launch) and 0.3 ms of what
-//     the scoring launches pay, and loses more than that to the longer last pass: the compiled-in share is 1.
+//     accumulates is encoded behind the last launch, at full rate on an empty chip.  Beside a scoring kernel an LNA
+//     segment runs at 0.88 of the launch's frame rate with the four-frame kernel (0.84 with the one-frame kernel); at a
+//     share of 1 workgroups are still pending when the scoring launch ends, take every CU, and the next scoring launch's
+//     workgroups are placed one by one as that flood drains.  Measured with the four-frame kernel, holding frames back
+//     removes the flood (share 0.9: no LNA kernel runs at the start of a scoring launch; 0.7 with the one-frame kernel),
+//     leaves the scoring launches as long as they were, and loses 0.03 ms per step to the longer last pass: the
+//     compiled-in share is 1.
 //   - The automatic chunk is half a 512-frame block per CU: at the plan's two cuts per block still one whole round of
 //     workgroups, with half the window in front under which nothing hides and half the last pass behind.
 // Order in time is not frame order; the ranges are disjoint.  Scores do not depend on where the frames are cut (every
