@@ -632,12 +632,7 @@ extern "C" aasr_status aasr_run_align_recipe(aasr_feat *feat, aasr_gmm *gmm, con
         const RecipeInfo &info = u.info;
         if (info.start_line > 0 || info.end_line > 0)  // (here, not up front: the groups before this line are written)
           raise(AASR_ERR_UNSUPPORTED, "align: recipe line limits (start-line / end-line) are not supported");
-        if (opt->speakers) {
-          if (aasr_spkc_set_speaker(opt->speakers, info.speaker_id.c_str()) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          if (!info.utterance_id.empty() && aasr_spkc_set_utterance(opt->speakers, info.utterance_id.c_str()) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        }
+        apply_speaker(opt->speakers, info);
         int16_t *pcm = nullptr;
         int64_t n_samples = 0;
         int32_t rate = 0;

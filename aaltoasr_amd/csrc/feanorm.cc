@@ -511,12 +511,7 @@ extern "C" aasr_status aasr_run_feanorm_recipe(const char *feat_cfg_text, const 
       }
       stager.stage(audio, start, rows, [&](size_t i) {
         if (i == 0) AASR_HIP(hipEventRecord(ev[0], stream));  // the features' interval opens once the buffers stand
-        if (!spk) return;
-        // feanorm.cc:146-152; a parameter change waits for the queued features
-        const RecipeInfo &u = infos[group_first + i];
-        if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        apply_speaker(spk, infos[group_first + i]);  // feanorm.cc:146-152; a parameter change waits for the queued features
       });
       AASR_HIP(hipEventRecord(ev[1], stream));
       if (aasr_moments_accumulate_dev(h, stager.d_x.p, rows_total, segs.data(), (int32_t)(segs.size() / 3), stream) != AASR_OK)

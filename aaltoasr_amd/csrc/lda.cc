@@ -571,12 +571,7 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
       }
       stager.stage(audio, start, rows, [&](size_t i) {
         if (i == 0) AASR_HIP(hipEventRecord(ev[0], stream));  // the features' interval opens once the buffers stand
-        if (!spk) return;
-        // lda.cc:284-289; a parameter change waits for the queued features
-        const RecipeInfo &u = infos[group_first + i];
-        if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+        apply_speaker(spk, infos[group_first + i]);  // lda.cc:284-289; a parameter change waits for the queued features
       });
       AASR_HIP(hipEventRecord(ev[1], stream));
       if (rows_total > 0 && aasr_scatter_accumulate_dev(h, stager.d_x.p, rows_total, cls.data(), nullptr, stream) != AASR_OK)

@@ -1,7 +1,8 @@
 // logl.cc -- the log-likelihood of a recipe (aku/logl.cc): per utterance the sum of the frame log-likelihoods along
 // a .phn state segmentation (seg_loglik.hip; logl.cc's transtat is an unset global, so no transition terms enter), or
 // with -H / -D the forward total of the forward-backward pass over the utterance's HMM network (hmmnet_fb.hip) on the
-// state log-likelihood rows of the model's scoring entry.  The recipe pass is the shared one (recipe_pass.h).
+// state log-likelihood rows of the model's scoring entry.  The recipe pass is the shared one (recipe_pass.h), the
+// network step the network drivers' (network_pass.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,8 +15,7 @@
 
 #include "common.h"
 #include "gmm.h"
-#include "hmmnet.h"
-#include "hmmnet_fb.h"
+#include "network_pass.h"
 #include "phn_line.h"
 #include "recipe_pass.h"
 #include "stats.h"
@@ -24,10 +24,7 @@ using namespace aasr;
 
 namespace {
 
-constexpr int64_t LOGL_GROUP_FRAMES = (int64_t)1 << 18;
-constexpr int64_t LOGL_GROUP_SCORES = (int64_t)1 << 27;  // rows x states of a group's score buffer
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+constexpr int64_t PHN_GROUP_FRAMES = (int64_t)1 << 18;
 
 // logl.cc:71-80
 void print_file_line(const RecipeInfo &u, int info, double ll) {
@@ -35,13 +32,6 @@ void print_file_line(const RecipeInfo &u, int info, double ll) {
   fprintf(stdout, "Log likelihood for file %s", u.audio_path.c_str());
   if (u.start_time || u.end_time) fprintf(stdout, " (%.2f-%.2f)", u.start_time, u.end_time);
   fprintf(stdout, ": %f\n", ll);
-}
-
-void set_speaker(aasr_spkc *spk, const RecipeInfo &u) {
-  if (!spk) return;
-  if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-  if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
-    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
 }
 
 }  // namespace
@@ -69,8 +59,6 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
     const bool nets = opt->hmmnet || opt->den_hmmnet;
     const TopoTables tt(topo);
     const float fr = aasr_feat_frame_rate(feat);
-    const bool timing = getenv("AASR_RECIPE_TIMING") != nullptr;
-    double t_host = 0, t_feat = 0, t_score = 0, t_fb = 0;
     GroupStager stager(feat, spk);
     const hipStream_t stream = stager.stream;
     double total = 0;
@@ -93,7 +81,7 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
         std::vector<int32_t> start, rows, pdfs;
         std::vector<char> ok;
         int64_t rows_total = 0;
-        while (next < infos.size() && audio.size() < 1024 && (audio.empty() || rows_total < LOGL_GROUP_FRAMES)) {
+        while (next < infos.size() && audio.size() < 1024 && (audio.empty() || rows_total < PHN_GROUP_FRAMES)) {
           const RecipeInfo &u = infos[next++];
           audio.push_back(load_utterance_input(feat, u));
           int first, last;
@@ -112,7 +100,7 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
           pdfs.insert(pdfs.end(), seg.pdf.begin(), seg.pdf.end());
           rows_total += (int64_t)seg.pdf.size();
         }
-        stager.stage(audio, start, rows, [&](size_t i) { set_speaker(spk, infos[group_first + i]); });
+        stager.stage(audio, start, rows, [&](size_t i) { apply_speaker(spk, infos[group_first + i]); });
         if (rows_total > 0) {
           check_stats_model(gmm, "logl");  // (a speaker's cmllr block would have reached the model by now)
           d_ll.ensure((size_t)rows_total);
@@ -140,11 +128,9 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
 
     // ---- HMM networks ----
     aasr_fb_options fo;
-    aasr_fb_default_options(&fo);
-    if (opt->fw_beam > 0) fo.fw_beam = opt->fw_beam;  // set_pruning_thresholds: 0 keeps the default
-    if (opt->bw_beam > 0) fo.bw_beam = opt->bw_beam;
-    if (opt->ac_scale_given) fo.ac_scale = opt->ac_scale;
-    fo.mode = opt->vit ? AASR_FB_VITERBI : AASR_FB_BAUM_WELCH;
+    network_fb_options(&fo, opt->fw_beam, opt->bw_beam, opt->ac_scale_given != 0, opt->ac_scale, opt->vit != 0);
+    StageTimers tm;
+    tm.on = getenv("AASR_RECIPE_TIMING") != nullptr;
     const int S = aasr_gmm_num_states(gmm);
     const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
     NetworkCache net_cache(topo, S);
@@ -153,78 +139,32 @@ aasr_status aasr_run_logl_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
     while (next < infos.size()) {
       double t = now_s();
       const size_t group_first = next;
-      std::vector<std::vector<int16_t>> audio;
-      std::vector<int32_t> start, rows;
-      std::vector<const aasr_hmmnet *> group_nets;
-      int64_t rows_total = 0;
-      while (next < infos.size() && audio.size() < 1024 &&
-             (audio.empty() || (rows_total < LOGL_GROUP_FRAMES && rows_total * S < LOGL_GROUP_SCORES))) {
+      NetworkGroup g;
+      while (next < infos.size() && g.size() < 1024 &&
+             (g.size() == 0 || (g.rows_total < NETWORK_GROUP_FRAMES && g.rows_total * S < NETWORK_GROUP_SCORES))) {
         const RecipeInfo &u = infos[next++];
-        audio.push_back(load_utterance_input(feat, u));
-        // Recipe::Info::init_hmmnet_files (Recipe.cc:198-231)
-        if (!opt->den_hmmnet && u.hmmnet_path.empty())
-          raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
-        const std::string &path = opt->den_hmmnet ? u.den_hmmnet_path : u.hmmnet_path;
-        group_nets.push_back(net_cache.get(path));
-        int first, n;
-        network_frame_range(u, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), &first, &n);
-        start.push_back(first);
-        rows.push_back(n);
-        rows_total += n;
+        g.add(feat, net_cache, u, opt->den_hmmnet ? u.den_hmmnet_path : u.hmmnet_path, fr);
       }
-      t_host += now_s() - t;
+      tm.host += now_s() - t;
       t = now_s();
-      stager.stage(audio, start, rows, [&](size_t i) { set_speaker(spk, infos[group_first + i]); });
-      if (timing) AASR_HIP(hipStreamSynchronize(stream));
-      t_feat += now_s() - t;
-      t = now_s();
+      stager.stage(g.audio, g.start, g.rows, [&](size_t i) { apply_speaker(spk, infos[group_first + i]); });
+      if (tm.on) AASR_HIP(hipStreamSynchronize(stream));
+      tm.feat += now_s() - t;
       check_stats_model(gmm, "logl");
-      const void *d_rows = scores.score(gmm, stager.d_x.p, rows_total, f64, stream);
-      if (timing) AASR_HIP(hipStreamSynchronize(stream));
-      t_score += now_s() - t;
-      t = now_s();
-      aasr_fb_batch *b = nullptr;
-      if (aasr_fb_batch_create(&fo, (int32_t)group_nets.size(), group_nets.data(), rows.data(), &b) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      std::unique_ptr<aasr_fb_batch, void (*)(aasr_fb_batch *)> bguard(b, aasr_fb_batch_destroy);
-      std::vector<int64_t> row0;
-      int64_t at = 0;
-      for (int32_t r : rows) {
-        row0.push_back(at);
-        at += r;
-      }
-      // logl.cc:183-199: a failed backward pass is run again with 2x, 3x, ... 5x the backward beam -- new launches over
-      // the failed utterances only
-      int32_t failed = 0;
-      for (int attempt = 1; attempt <= fo.max_attempts; attempt++) {
-        if (aasr_fb_batch_dev(b, d_rows, S, rows_total, f64 ? 1 : 0, row0.data(), attempt, stream) != AASR_OK ||
-            aasr_fb_batch_sync(b, stream, &failed) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        if (failed == 0) break;
-      }
-      t_fb += now_s() - t;
-      for (size_t i = 0; i < group_nets.size(); i++) {
+      const void *d_scores = nullptr;
+      const FbBatchPtr b = run_network_group(fo, gmm, stager, g, scores, f64, &d_scores, &tm);
+      for (size_t i = 0; i < g.size(); i++) {
         const RecipeInfo &u = infos[group_first + i];
-        int32_t status = 0, attempts = 0;
         double fw = 0;
-        if (aasr_fb_batch_result(b, (int32_t)i, &status, nullptr, &fw, &attempts, nullptr, nullptr) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        for (int k = 2; k <= attempts; k++)
-          fprintf(stderr, "Warning: Backward phase failed, increasing beam to %.1f\n", k * fo.bw_beam);
-        if (status == FB_FAILED_BACKWARD) {
-          fprintf(stderr, "Could not run Baum-Welch for file %s\n", u.audio_path.c_str());
-          fprintf(stderr, "The HMM network may be incorrect or initial beam too low.\n");
-          continue;
-        }
-        if (status != FB_OK) raise(AASR_ERR_INVALID, "No paths survived to the end of the network!");
+        if (!report_network_outcome(b.get(), i, fo, RetryMessages::BAUM_WELCH, u, &fw)) continue;
         print_file_line(u, opt->info, fw);
         total += fw;
       }
-      num_frames += rows_total;
+      num_frames += g.rows_total;
     }
-    if (timing)
+    if (tm.on)
       fprintf(stderr, "logl timing: input and networks %.3f s, features %.3f s, scoring %.3f s, forward-backward %.3f s\n",
-              t_host, t_feat, t_score, t_fb);
+              tm.host, tm.feat, tm.score, tm.fb);
     *total_log_likelihood = total;
     fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
   });

@@ -2,7 +2,7 @@
 // device accumulation (mllr_accum.hip), the host solver of MllTrainerComponent::calculate_transform /
 // calculate_alpha (MllrTrainer.cc:165-253) in double with its own LU, and the mllr main loop over a recipe
 // (aasr_run_mllr_recipe, mllr.cc:54-71, 126-145, 213-332), over .phn files or, with aasr_run_mllr_networks_recipe, over
-// the recipe's HMM networks (mllr.cc:73-104: hmmnet_fb.hip, fb_frame_entries.hip, mllr_entries.hip).
+// the recipe's HMM networks (mllr.cc:73-104: network_pass.h, fb_frame_entries.hip, mllr_entries.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,10 +19,9 @@
 #include "common.h"
 #include "feat.h"
 #include "gmm.h"
-#include "hmmnet.h"
-#include "hmmnet_fb.h"
 #include "mllr.h"
 #include "mllt.h"
+#include "network_pass.h"
 #include "recipe_pass.h"
 
 using namespace aasr;
@@ -409,6 +408,173 @@ void aasr_mllr_default_options(aasr_mllr_options *o) {
 
 // ---- the mllr main loop over a recipe ----------------------------------------------------------
 
+namespace {
+
+constexpr int64_t PHN_GROUP_FRAMES = (int64_t)1 << 18;
+
+// What the loop carries from group to group and from speaker to speaker
+struct MllrRun {
+  aasr_feat *feat = nullptr;
+  aasr_gmm *gmm = nullptr;
+  const aasr_topo *topo = nullptr;
+  const aasr_mllr_options *opt = nullptr;
+  aasr_mllr *h = nullptr;
+  GroupStager *stager = nullptr;
+  std::vector<RecipeInfo> infos;
+  FeatModule *ltm = nullptr;  // -M: the lin_transform module that takes the transform; null: the model's cmllr block
+  std::string module;
+  std::vector<double> G, k, W;
+  std::string cur_speaker;  // empty: no trainer yet
+  int64_t num_frames = 0;
+  // the network mode (aasr_run_mllr_networks_recipe)
+  aasr_fb_options fo;
+  NetworkCache net_cache;
+  GroupScores scores;
+  double total_ll = 0, max_dev = 0;  // the forward totals; max |1 - s_t| over the run
+  int64_t entries = 0;
+  MllrRun(const aasr_topo *topo_, int32_t num_states) : topo(topo_), net_cache(topo_, num_states) {}
+};
+
+// calculate_transform (aku/mllr.cc:39-52) for cur_speaker
+void finish_speaker(MllrRun &r) {
+  const int D = aasr_gmm_dim(r.gmm);
+  const hipStream_t stream = r.stager->stream;
+  aasr_spkc *spk = r.opt->speakers;
+  if (r.opt->info > 0) {
+    printf("%s: ", r.cur_speaker.c_str());
+    fflush(stdout);
+    fprintf(stderr, "Calculating transform for %s\n", r.cur_speaker.c_str());
+  }
+  double beta = 0;
+  if (aasr_mllr_fetch(r.h, stream) != AASR_OK || aasr_mllr_get(r.h, r.G.data(), r.k.data(), &beta) != AASR_OK)
+    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  try {
+    mllr_solve(D, r.G.data(), r.k.data(), beta, r.W.data());
+  } catch (Error &e) {
+    raise(e.code, "speaker %s: %s", r.cur_speaker.c_str(), e.msg.c_str());
+  }
+  if (r.ltm) {
+    FeatModule *ltm = r.ltm;
+    std::vector<float> Af((size_t)D * D), bf((size_t)D);
+    const bool defined = ltm->matrix_defined && ltm->bias_defined;  // LinTransformModule::is_defined
+    mllr_compose(D, r.W.data(), defined ? ltm->matrix.data() : nullptr, defined ? ltm->bias.data() : nullptr, Af.data(),
+                 bf.data());
+    spkc_feature_rewritten(spk, r.module);  // (the stream is idle: the fetch waited)
+    ltm->matrix = Af;
+    ltm->bias = bf;
+    ltm->matrix_defined = ltm->bias_defined = true;
+    ltm->d_matrix.upload(ltm->matrix.data(), ltm->matrix.size());
+    ltm->d_bias.upload(ltm->bias.data(), ltm->bias.size());
+  } else {
+    spkc_cmllr_add_global_transform(spk, r.W);
+    if (r.opt->info > 0) {  // MllrTrainer.cc:78-80: an ostream's default formatting of a double
+      std::ostringstream os;
+      os << beta << " frames, " << 1 << " transform matrices";
+      printf("%s\n", os.str().c_str());
+      fflush(stdout);
+    }
+  }
+  if (aasr_mllr_reset(r.h, stream) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  r.cur_speaker.clear();
+}
+
+// more lines of cur_speaker for a group that holds `lines` of them and rows_total frames
+bool group_takes_more(const MllrRun &r, size_t next, size_t lines, int64_t rows_total, int64_t max_frames) {
+  return next < r.infos.size() && r.infos[next].speaker_id == r.cur_speaker && lines < 1024 && rows_total < max_frames;
+}
+
+// the frames carry the speaker's CURRENT transform, as the reference's feature generator does
+void stage_group(MllrRun &r, size_t group_first, const std::vector<std::vector<int16_t>> &audio,
+                 const std::vector<int32_t> &start, const std::vector<int32_t> &rows) {
+  r.stager->stage(audio, start, rows, [&](size_t i) {
+    // set_utterance per line (aku/mllr.cc:289-290); a parameter change waits for the queued features
+    const RecipeInfo &u = r.infos[group_first + i];
+    if (!u.utterance_id.empty() && aasr_spkc_set_utterance(r.opt->speakers, u.utterance_id.c_str()) != AASR_OK)
+      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  });
+}
+
+// A group over .phn files: utterances of cur_speaker from *next on, their frames in one device buffer, one accumulation.
+// -> the group's frames
+int64_t phn_group(MllrRun &r, const TopoTables &tt, size_t *next) {
+  const float fr = aasr_feat_frame_rate(r.feat);
+  const hipStream_t stream = r.stager->stream;
+  const size_t group_first = *next;
+  std::vector<std::vector<int16_t>> audio;
+  std::vector<int32_t> start, rows, pdfs;
+  int64_t rows_total = 0;
+  while (group_takes_more(r, *next, audio.size(), rows_total, PHN_GROUP_FRAMES)) {
+    const RecipeInfo &u = r.infos[(*next)++];
+    announce(u, r.opt->info, (int)(*next - 1), (int)r.infos.size());
+    audio.push_back(load_utterance_input(r.feat, u));
+    // train_mllr hands the segmentator's PDF index to model.state() and takes that state's emission_pdf
+    // (aku/mllr.cc:136-140): a double lookup.  In the .ph files this engine reads a state's emission pdf is the
+    // state's own index (HmmSet::read_ph, legacy format) and the engine takes state == pdf throughout, so
+    // both lookups are the identity here and the segmentation's index is used as it is.
+    const Segmentation seg = read_state_sequence(r.topo, tt, u, r.opt->ophn != 0, fr,
+                                                 aasr_feat_eof_frame(r.feat, (int64_t)audio.back().size()));
+    if (!seg.initialized) audio.back().clear();
+    start.push_back(seg.start_frame);
+    rows.push_back((int32_t)seg.pdf.size());
+    pdfs.insert(pdfs.end(), seg.pdf.begin(), seg.pdf.end());
+    rows_total += (int64_t)seg.pdf.size();
+  }
+  stage_group(r, group_first, audio, start, rows);
+  if (rows_total > 0) {
+    if (aasr_mllr_accumulate_dev(r.h, r.stager->d_x.p, rows_total, pdfs.data(), stream) != AASR_OK)
+      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+    AASR_HIP(hipStreamSynchronize(stream));  // the group's host audio and pdfs go out of scope
+  }
+  return rows_total;
+}
+
+// A group over HMM networks (get_segmentator and train_mllr, aku/mllr.cc:73-104, 126-145): utterances of cur_speaker
+// from *next on, the network step (network_pass.h), the frame-major entries, the weighted accumulation.
+// -> the frames of the utterances that ran
+int64_t network_group(MllrRun &r, size_t *next) {
+  const float fr = aasr_feat_frame_rate(r.feat);
+  const hipStream_t stream = r.stager->stream;
+  const int S = aasr_gmm_num_states(r.gmm);
+  const size_t group_first = *next;
+  NetworkGroup g;
+  while (group_takes_more(r, *next, g.size(), g.rows_total, NETWORK_GROUP_FRAMES)) {
+    const RecipeInfo &u = r.infos[(*next)++];
+    announce(u, r.opt->info, (int)(*next - 1), (int)r.infos.size());
+    g.add(r.feat, r.net_cache, u, u.hmmnet_path, fr);
+  }
+  stage_group(r, group_first, g.audio, g.start, g.rows);
+  // in model mode the model is the unadapted one the statistics are collected on (loading is disabled)
+  const bool f64 = aasr_gmm_get_precision(r.gmm) == AASR_PREC_F64;
+  const void *d_scores = nullptr;
+  const FbBatchPtr batch = run_network_group(r.fo, r.gmm, *r.stager, g, r.scores, f64, &d_scores);
+  aasr_fb_batch *b = batch.get();
+  int64_t n_entries = 0;
+  const int64_t *d_off = nullptr;
+  const int32_t *d_pdf = nullptr;
+  const double *d_weight = nullptr;
+  if (aasr_fb_batch_frame_entries_dev(b, S, g.row0.data(), g.rows_total, stream, &n_entries, &d_off, &d_pdf, &d_weight) != AASR_OK)
+    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  r.entries += n_entries;
+  // the messages in recipe order, and the frame sums
+  int64_t frames = 0;
+  for (size_t i = 0; i < g.size(); i++) {
+    const RecipeInfo &u = r.infos[group_first + i];
+    double fw = 0;
+    if (!report_network_outcome(b, i, r.fo, RetryMessages::BAUM_WELCH, u, &fw)) continue;
+    check_frame_sums(b, i, g, u, &r.max_dev);
+    r.total_ll += fw;  // train_mllr: get_total_log_likelihood (aku/mllr.cc:143-144)
+    frames += g.rows[i];
+  }
+  if (n_entries > 0 &&
+      aasr_mllr_accumulate_weighted_dev(r.h, r.stager->d_x.p, g.rows_total, d_off, d_pdf, d_weight, n_entries, stream) != AASR_OK)
+    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  // the batch owns the entries that the accumulation reads: it goes when the stream is done with them
+  AASR_HIP(hipStreamSynchronize(stream));
+  return frames;
+}
+
+}  // namespace
+
 // nopt: the network mode (aasr_run_mllr_networks_recipe), or NULL for the .phn files
 static aasr_status run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
                                    const aasr_mllr_options *opt, const aasr_mllr_network_options *nopt,
@@ -420,250 +586,72 @@ static aasr_status run_mllr_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_to
       raise(AASR_ERR_UNSUPPORTED, "mllr: -O is not supported with --networks (a network line has no segmentation to choose)");
     const auto t0 = std::chrono::steady_clock::now();
     aasr_spkc *spk = opt->speakers;
+    MllrRun r(topo, aasr_gmm_num_states(gmm));
+    r.feat = feat;
+    r.gmm = gmm;
+    r.opt = opt;
     // Recipe::read with cluster_speakers = true, then sort_infos (aku/mllr.cc:213-216)
-    std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, true);
-    std::stable_sort(infos.begin(), infos.end(),
+    r.infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, true);
+    std::stable_sort(r.infos.begin(), r.infos.end(),
                      [](const RecipeInfo &a, const RecipeInfo &b) { return a.speaker_id < b.speaker_id; });
+    const std::vector<RecipeInfo> &infos = r.infos;
     refuse_line_limits(infos, "mllr");
     const int D = aasr_gmm_dim(gmm);
     check_feature_dim(gmm, feat);
-    const bool global_transform = opt->module && opt->module[0];
-    FeatModule *ltm = nullptr;
-    std::string module;
-    if (global_transform) {
-      module = opt->module;
-      auto it = feat->by_name.find(module);
-      if (it == feat->by_name.end()) raise(AASR_ERR_INVALID, "unknown module requested: %s", module.c_str());
-      ltm = &feat->mods[(size_t)it->second];
-      if (ltm->type != MOD_LIN_TRANSFORM || ltm->dim != D || ltm->src_dim != D)
-        raise(AASR_ERR_INVALID, "mllr: -M %s is not a lin_transform module of %d x %d", module.c_str(), D, D);
+    if (opt->module && opt->module[0]) {
+      r.module = opt->module;
+      auto it = feat->by_name.find(r.module);
+      if (it == feat->by_name.end()) raise(AASR_ERR_INVALID, "unknown module requested: %s", r.module.c_str());
+      r.ltm = &feat->mods[(size_t)it->second];
+      if (r.ltm->type != MOD_LIN_TRANSFORM || r.ltm->dim != D || r.ltm->src_dim != D)
+        raise(AASR_ERR_INVALID, "mllr: -M %s is not a lin_transform module of %d x %d", r.module.c_str(), D, D);
     } else {
       if (aasr_spkc_set_model(spk, gmm) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       spkc_cmllr_disable_loading(spk);  // the statistics are collected on the unadapted model (aku/mllr.cc:263-266)
     }
-    aasr_mllr *h = nullptr;
     {
-      const aasr_status cs = aasr_mllr_create(gmm, &h);
+      const aasr_status cs = aasr_mllr_create(gmm, &r.h);
       if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
     }
-    std::unique_ptr<aasr_mllr, void (*)(aasr_mllr *)> hguard(h, aasr_mllr_destroy);
+    std::unique_ptr<aasr_mllr, void (*)(aasr_mllr *)> hguard(r.h, aasr_mllr_destroy);
     const TopoTables tt(topo);
-    const float fr = aasr_feat_frame_rate(feat);
     GroupStager stager(feat, spk);
-    const hipStream_t stream = stager.stream;
-    const int64_t max_group_frames = (int64_t)1 << 18;
-    std::set<std::string> updated;
-    std::string cur_speaker;
-    bool have_trainer = false;
-    int64_t num_frames = 0;
+    r.stager = &stager;
     const int E = D + 1;
-    std::vector<double> G((size_t)D * E * E), k((size_t)D * E), W((size_t)D * E);
-
-    // calculate_transform (aku/mllr.cc:39-52) for cur_speaker
-    auto finish_speaker = [&]() {
-      if (opt->info > 0) {
-        printf("%s: ", cur_speaker.c_str());
-        fflush(stdout);
-        fprintf(stderr, "Calculating transform for %s\n", cur_speaker.c_str());
-      }
-      double beta = 0;
-      if (aasr_mllr_fetch(h, stream) != AASR_OK || aasr_mllr_get(h, G.data(), k.data(), &beta) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      try {
-        mllr_solve(D, G.data(), k.data(), beta, W.data());
-      } catch (Error &e) {
-        raise(e.code, "speaker %s: %s", cur_speaker.c_str(), e.msg.c_str());
-      }
-      if (global_transform) {
-        std::vector<float> Af((size_t)D * D), bf((size_t)D);
-        const bool defined = ltm->matrix_defined && ltm->bias_defined;  // LinTransformModule::is_defined
-        mllr_compose(D, W.data(), defined ? ltm->matrix.data() : nullptr, defined ? ltm->bias.data() : nullptr, Af.data(),
-                     bf.data());
-        spkc_feature_rewritten(spk, module);  // (the stream is idle: the fetch waited)
-        ltm->matrix = Af;
-        ltm->bias = bf;
-        ltm->matrix_defined = ltm->bias_defined = true;
-        ltm->d_matrix.upload(ltm->matrix.data(), ltm->matrix.size());
-        ltm->d_bias.upload(ltm->bias.data(), ltm->bias.size());
-      } else {
-        spkc_cmllr_add_global_transform(spk, W);
-        if (opt->info > 0) {  // MllrTrainer.cc:78-80: an ostream's default formatting of a double
-          std::ostringstream os;
-          os << beta << " frames, " << 1 << " transform matrices";
-          printf("%s\n", os.str().c_str());
-          fflush(stdout);
-        }
-      }
-      if (aasr_mllr_reset(h, stream) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      have_trainer = false;
-    };
-
-    // The network mode's step for a staged group (get_segmentator and train_mllr, aku/mllr.cc:73-104, 126-145): state
-    // scores, one forward-backward batch with its retries, the frame-major entries, the weighted accumulation.
-    // -> the frames of the utterances that ran
-    aasr_fb_options fo;
-    aasr_fb_default_options(&fo);
-    if (nopt) {
-      if (nopt->fw_beam > 0) fo.fw_beam = nopt->fw_beam;  // set_pruning_thresholds: 0 keeps the default
-      if (nopt->bw_beam > 0) fo.bw_beam = nopt->bw_beam;
-      fo.mode = nopt->viterbi ? AASR_FB_VITERBI : AASR_FB_BAUM_WELCH;
-    }
-    fo.want_pdf_occ = 1;
-    fo.device_occ = 1;
-    fo.max_attempts = 5;  // (counter >= 5, aku/mllr.cc:90)
-    const int S = aasr_gmm_num_states(gmm);
-    NetworkCache net_cache(topo, S);
-    GroupScores scores;
-    std::vector<double> sums;
-    double total_ll = 0, max_dev = 0;  // the forward totals; max |1 - s_t| over the run
-    int64_t entries = 0;
-    auto networks_group = [&](const std::vector<RecipeInfo> &infos, size_t group_first,
-                              const std::vector<const aasr_hmmnet *> &group_nets, const std::vector<int32_t> &start,
-                              const std::vector<int32_t> &rows, int64_t rows_total) -> int64_t {
-      if (group_nets.empty() || rows_total <= 0) return 0;
-      // in model mode the model is the unadapted one the statistics are collected on (loading is disabled above)
-      const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
-      const void *d_scores = scores.score(gmm, stager.d_x.p, rows_total, f64, stream);
-      aasr_fb_batch *b = nullptr;
-      if (aasr_fb_batch_create(&fo, (int32_t)group_nets.size(), group_nets.data(), rows.data(), &b) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      std::unique_ptr<aasr_fb_batch, void (*)(aasr_fb_batch *)> bguard(b, aasr_fb_batch_destroy);
-      std::vector<int64_t> row0;
-      int64_t at = 0;
-      for (int32_t r : rows) {
-        row0.push_back(at);
-        at += r;
-      }
-      // aku/mllr.cc:87-102: a failed backward pass is run again with 2x ... 5x the original backward beam, the forward
-      // beam as it stands -- new launches over the failed utterances only
-      int32_t failed = 0;
-      for (int attempt = 1; attempt <= fo.max_attempts; attempt++) {
-        if (aasr_fb_batch_dev(b, d_scores, S, rows_total, f64 ? 1 : 0, row0.data(), attempt, stream) != AASR_OK ||
-            aasr_fb_batch_sync(b, stream, &failed) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        if (failed == 0) break;
-      }
-      int64_t n_entries = 0;
-      const int64_t *d_off = nullptr;
-      const int32_t *d_pdf = nullptr;
-      const double *d_weight = nullptr;
-      if (aasr_fb_batch_frame_entries_dev(b, S, row0.data(), rows_total, stream, &n_entries, &d_off, &d_pdf, &d_weight) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      entries += n_entries;
-      // the messages in recipe order, and the frame sums: HmmNetBaumWelch::next_frame's sanity check (:772-779)
-      int64_t frames = 0;
-      for (size_t i = 0; i < group_nets.size(); i++) {
-        const RecipeInfo &u = infos[group_first + i];
-        int32_t status = 0, attempts = 0;
-        double fw = 0;
-        if (aasr_fb_batch_result(b, (int32_t)i, &status, nullptr, &fw, &attempts, nullptr, nullptr) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        for (int k = 2; k <= attempts; k++) fprintf(stderr, "Warning: Backward phase failed, increasing beam to %.1f\n", k * fo.bw_beam);
-        if (status == FB_FAILED_BACKWARD) {
-          fprintf(stderr, "Could not run Baum-Welch for file %s\n", u.audio_path.c_str());
-          fprintf(stderr, "The HMM network may be incorrect or initial beam too low.\n");
-          continue;
-        }
-        if (status != FB_OK) raise(AASR_ERR_INVALID, "No paths survived to the end of the network!");
-        sums.resize((size_t)rows[i]);
-        if (aasr_fb_batch_frame_sums(b, (int32_t)i, sums.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        for (int32_t f = 0; f < rows[i]; f++) {
-          const double dev = std::fabs(1 - sums[(size_t)f]);
-          if (dev > 0.02) {
-            fprintf(stderr, "Warning: Sum of PDF probabilities is %g at frame %i\n", sums[(size_t)f], start[i] + f);
-            if (sums[(size_t)f] < 0.01)  // (the reference exits here)
-              raise(AASR_ERR_INVALID, "HmmNetBaumWelch: the sum of PDF probabilities is %g at frame %d of %s", sums[(size_t)f],
-                    start[i] + f, u.audio_path.c_str());
-          }
-          max_dev = std::max(max_dev, dev);
-        }
-        total_ll += fw;  // train_mllr: get_total_log_likelihood (aku/mllr.cc:143-144)
-        frames += rows[i];
-      }
-      if (n_entries > 0 &&
-          aasr_mllr_accumulate_weighted_dev(h, stager.d_x.p, rows_total, d_off, d_pdf, d_weight, n_entries, stream) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      // the batch owns the entries that the accumulation reads: it goes when the stream is done with them
-      AASR_HIP(hipStreamSynchronize(stream));
-      return frames;
-    };
+    r.G.resize((size_t)D * E * E);
+    r.k.resize((size_t)D * E);
+    r.W.resize((size_t)D * E);
+    network_fb_options(&r.fo, nopt ? nopt->fw_beam : 0, nopt ? nopt->bw_beam : 0, false, 1, nopt && nopt->viterbi);
+    r.fo.want_pdf_occ = 1;
+    r.fo.device_occ = 1;
+    r.fo.max_attempts = 5;  // (counter >= 5, aku/mllr.cc:90)
+    std::set<std::string> updated;
 
     size_t next = 0;
     while (next < infos.size()) {
       if (infos[next].speaker_id.empty()) raise(AASR_ERR_INVALID, "Speaker ID is missing");
       // set_speaker (aku/mllr.cc:54-71): the previous speaker's transform first
-      if (infos[next].speaker_id != cur_speaker) {
-        if (have_trainer) finish_speaker();
-        cur_speaker = infos[next].speaker_id;
-        updated.insert(cur_speaker);
-        have_trainer = true;
-        if (aasr_spkc_set_speaker(spk, cur_speaker.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      if (infos[next].speaker_id != r.cur_speaker) {
+        if (!r.cur_speaker.empty()) finish_speaker(r);
+        r.cur_speaker = infos[next].speaker_id;
+        updated.insert(r.cur_speaker);
+        if (aasr_spkc_set_speaker(spk, r.cur_speaker.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
       }
-      // a group: utterances of this speaker, their frames in one device buffer, one accumulation
-      const size_t group_first = next;
-      std::vector<std::vector<int16_t>> audio;
-      std::vector<int32_t> start, rows, pdfs;
-      std::vector<const aasr_hmmnet *> group_nets;
-      int64_t rows_total = 0;
-      while (next < infos.size() && infos[next].speaker_id == cur_speaker && audio.size() < 1024 &&
-             rows_total < max_group_frames) {
-        const RecipeInfo &u = infos[next];
-        announce(u, opt->info, (int)next, (int)infos.size());
-        audio.push_back(load_utterance_input(feat, u));
-        if (nopt) {  // Recipe::Info::init_hmmnet_files (Recipe.cc:198-231)
-          if (u.hmmnet_path.empty()) raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
-          group_nets.push_back(net_cache.get(u.hmmnet_path));
-          int first, n;
-          network_frame_range(u, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), &first, &n);
-          start.push_back(first);
-          rows.push_back(n);
-          rows_total += n;
-          next++;
-          continue;
-        }
-        // train_mllr hands the segmentator's PDF index to model.state() and takes that state's emission_pdf
-        // (aku/mllr.cc:136-140): a double lookup.  In the .ph files this engine reads a state's emission pdf is the
-        // state's own index (HmmSet::read_ph, legacy format) and the engine takes state == pdf throughout, so
-        // both lookups are the identity here and the segmentation's index is used as it is.
-        const Segmentation seg =
-            read_state_sequence(topo, tt, u, opt->ophn != 0, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()));
-        if (!seg.initialized) audio.back().clear();
-        start.push_back(seg.start_frame);
-        rows.push_back((int32_t)seg.pdf.size());
-        pdfs.insert(pdfs.end(), seg.pdf.begin(), seg.pdf.end());
-        rows_total += (int64_t)seg.pdf.size();
-        next++;
-      }
-      // the frames carry the speaker's CURRENT transform, as the reference's feature generator does
-      stager.stage(audio, start, rows, [&](size_t i) {
-        // set_utterance per line (aku/mllr.cc:289-290); a parameter change waits for the queued features
-        const RecipeInfo &u = infos[group_first + i];
-        if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      });
-      if (nopt) {
-        num_frames += networks_group(infos, group_first, group_nets, start, rows, rows_total);
-        continue;
-      }
-      if (rows_total > 0) {
-        if (aasr_mllr_accumulate_dev(h, stager.d_x.p, rows_total, pdfs.data(), stream) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        AASR_HIP(hipStreamSynchronize(stream));  // the group's host audio and pdfs go out of scope
-      }
-      num_frames += rows_total;
+      r.num_frames += nopt ? network_group(r, &next) : phn_group(r, tt, &next);
     }
-    if (have_trainer) finish_speaker();
+    if (!r.cur_speaker.empty()) finish_speaker(r);
     if (nopt && opt->info > 0) {
-      fprintf(stderr, "Largest |1 - sum of PDF probabilities| of a frame: %g\n", max_dev);
-      fprintf(stderr, "Weighted entries: %lld over %lld frames\n", (long long)entries, (long long)num_frames);
+      fprintf(stderr, "Largest |1 - sum of PDF probabilities| of a frame: %g\n", r.max_dev);
+      fprintf(stderr, "Weighted entries: %lld over %lld frames\n", (long long)r.entries, (long long)r.num_frames);
     }
 
     // the new speaker configuration (aku/mllr.cc:318-332)
     if (opt->out) write_speaker_file_for_batch(spk, updated, opt->num_batches, opt->batch_index, opt->out);
-    if (opt->info > 0 && total_ll != 0) fprintf(stderr, "Total log likelihood: %f\n", total_ll);  // aku/mllr.cc:334-336
-    fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
+    if (opt->info > 0 && r.total_ll != 0) fprintf(stderr, "Total log likelihood: %f\n", r.total_ll);  // aku/mllr.cc:334-336
+    fill_run_stats(stats, (int64_t)infos.size(), r.num_frames, t0, 0);
   });
 }
+
 
 extern "C" {
 

@@ -9,7 +9,6 @@
 
 #include "feat.h"
 #include "gmm.h"
-#include "hmmnet.h"
 #include "phn_line.h"
 
 namespace aasr {
@@ -180,6 +179,13 @@ Segmentation read_state_sequence(const aasr_topo *topo, const TopoTables &tt, co
   return seg;
 }
 
+void apply_speaker(aasr_spkc *spk, const RecipeInfo &u, bool utterance) {
+  if (!spk) return;
+  if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  if (utterance && !u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
+    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+}
+
 GroupStager::GroupStager(aasr_feat *feat_, aasr_spkc *speakers_, int target_)
     : feat(feat_), speakers(speakers_), target(target_),
       dim(target_ < 0 ? aasr_feat_dim(feat_) : feat_->mods[(size_t)target_].dim), stream_guard(nullptr, [](void *s) {
@@ -270,51 +276,6 @@ void write_text_file(const char *path, const char *data, size_t len) {
   if (!of) raise(AASR_ERR_IO, "could not open %s for writing", path);
   of.write(data, (std::streamsize)len);
   if (!of) raise(AASR_ERR_IO, "write error on %s", path);
-}
-
-const aasr_hmmnet *NetworkCache::get(const std::string &path) {
-  auto it = nets.find(path);
-  if (it == nets.end()) {
-    aasr_hmmnet *net = nullptr;
-    const aasr_status rs = aasr_hmmnet_read(topo, path.c_str(), &net);
-    if (rs != AASR_OK) raise(rs, "%s", last_error().c_str());
-    it = nets.emplace(path, std::unique_ptr<aasr_hmmnet, void (*)(aasr_hmmnet *)>(net, aasr_hmmnet_destroy)).first;
-  }
-  for (int32_t pdf : it->second->pdfs)
-    if (pdf >= num_states)
-      raise(AASR_ERR_INVALID, "%s: state %d is not below the model's %d states", path.c_str(), pdf, num_states);
-  return it->second.get();
-}
-
-void network_frame_range(const RecipeInfo &info, float frame_rate, int eof_frame, int *first, int *rows) {
-  int last;
-  frame_range(info, frame_rate, first, &last);
-  const int end = last > 0 ? std::min(last, eof_frame) : eof_frame;
-  if (end - *first < 1)
-    raise(AASR_ERR_INVALID, "HmmNetBaumWelch: no frames for %s (frames %d to %d)", info.audio_path.c_str(), *first, end);
-  if (end - *first == 1) fprintf(stderr, "HmmNetBaumWelch: Warning: Single frame utterance\n");
-  *rows = end - *first;
-}
-
-const void *GroupScores::score(aasr_gmm *gmm, const double *d_x, int64_t n_rows, bool f64, hipStream_t stream) {
-  const int S = aasr_gmm_num_states(gmm), D = aasr_gmm_dim(gmm);
-  if (f64) {
-    d_scores64.ensure((size_t)n_rows * S);
-    if (aasr_gmm_score_f64_dev(gmm, d_x, n_rows, d_scores64.p, stream) != AASR_OK)
-      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-    return d_scores64.p;
-  }
-  // the scoring entry of the default mode takes float frames
-  x64.resize((size_t)n_rows * D);
-  AASR_HIP(hipMemcpyAsync(x64.data(), d_x, x64.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  AASR_HIP(hipStreamSynchronize(stream));
-  x32.assign(x64.begin(), x64.end());
-  d_x32.ensure(x32.size());
-  d_scores32.ensure((size_t)n_rows * S);
-  AASR_HIP(hipMemcpyAsync(d_x32.p, x32.data(), x32.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-  if (aasr_gmm_score_dev(gmm, d_x32.p, n_rows, d_scores32.p, stream) != AASR_OK)
-    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-  return d_scores32.p;
 }
 
 }  // namespace aasr

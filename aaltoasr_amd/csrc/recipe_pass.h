@@ -62,6 +62,10 @@ Segmentation read_segmentation(const aasr_topo *topo, const TopoTables &tt, cons
 Segmentation read_state_sequence(const aasr_topo *topo, const TopoTables &tt, const RecipeInfo &info, bool ophn,
                                  float frame_rate, int eof_frame);
 
+// A line's speaker and, when asked for, its utterance (where it has an id) in the speaker configuration, as the tools
+// do per line before its features are made; nothing without a configuration
+void apply_speaker(aasr_spkc *spk, const RecipeInfo &u, bool utterance = true);
+
 // The frames of a group of utterances in one device buffer: the stream, the group's input and its frames [rows x dim]
 // of module `target` (< 0: the chain's output).  With a speaker configuration, a change that rewrites feature
 // parameters waits for the features queued with the old ones; utterances whose settings stay the same stay in flight
@@ -81,31 +85,6 @@ struct GroupStager {
   // The group's audio stays the caller's until the stream has been waited for.  -> the group's rows
   int64_t stage(const std::vector<std::vector<int16_t>> &audio, const std::vector<int32_t> &start,
                 const std::vector<int32_t> &rows, const std::function<void(size_t)> &before_utterance);
-};
-
-// The recipe's HMM networks (hmmnet.h), each file read once: Recipe::Info::init_hmmnet_files (Recipe.cc:198-231) as the
-// network drivers use it (logl.cc, stats.cc).  A network with a state the model does not have is refused.
-struct NetworkCache {
-  const aasr_topo *topo;
-  int32_t num_states;
-  std::map<std::string, std::unique_ptr<aasr_hmmnet, void (*)(aasr_hmmnet *)>> nets;
-  NetworkCache(const aasr_topo *topo_, int32_t num_states_) : topo(topo_), num_states(num_states_) {}
-  const aasr_hmmnet *get(const std::string &path);
-};
-
-// The frames of a network line (Recipe.cc:223-228, HmmNetBaumWelch::generate_features): first .. last, or to the last
-// frame of the audio; a limit past the audio is cut to it.  No frames is an error, one frame the reference's warning.
-void network_frame_range(const RecipeInfo &info, float frame_rate, int eof_frame, int *first, int *rows);
-
-// State log-likelihood rows of a staged group from the model's scoring entry in the model's precision mode: double
-// rows under AASR_PREC_F64, float rows (from float frames, as that entry takes them) otherwise.
-struct GroupScores {
-  DevBuf<double> d_scores64;
-  DevBuf<float> d_scores32, d_x32;
-  std::vector<double> x64;
-  std::vector<float> x32;
-  // -> the rows [n_rows x states] on the device, queued on `stream`
-  const void *score(aasr_gmm *gmm, const double *d_x, int64_t n_rows, bool f64, hipStream_t stream);
 };
 
 // The speaker file an adaptation tool writes (aku/mllr.cc:318-332, vtln.cc:269-286): every entry of the configuration,

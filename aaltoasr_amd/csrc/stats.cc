@@ -1,78 +1,22 @@
-// stats.cc -- ML statistics collection (aku/stats.cc with --ml over .phn segmentations): the statistics
-// handle that drives the device accumulation (stats_accum.hip), the dump writers of
-// HmmSet::dump_statistics and the stats main loop over a recipe (aasr_run_stats_recipe,
-// stats.cc:73-170, 540-620, 740-795) over .phn segmentations, or with aasr_run_stats_networks_recipe Baum-Welch over
-// the recipe's HMM networks (hmmnet_fb.hip, fb_entries.hip, stats_weighted.hip).  The segmentation reader is
-// recipe_pass.cc's.  A handle made by aasr_stats_create_full also collects the full second moments
-// (stats_full_accum.hip) and dumps mode 3.
+// stats.cc -- ML statistics collection (aku/stats.cc with --ml): the statistics handle that drives the device
+// accumulation (stats_accum.hip, stats_weighted.hip) -- create, accumulate, fetch and the getters.  The dump writers
+// are in stats_files.cc, the stats main loop over a recipe in stats_recipe.cc.  A handle made by
+// aasr_stats_create_full also collects the full second moments (stats_full_accum.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <fstream>
 #include <memory>
-#include <string>
 #include <vector>
 
 #include "common.h"
 #include "gmm.h"
-#include "hmmnet.h"
-#include "hmmnet_fb.h"
 #include "recipe_pass.h"
 #include "stats.h"
 #include "stats_full.h"
 
 using namespace aasr;
-
-namespace aasr {
-
-static double safe_log(double x) { return x < 1e-50 ? std::log(1e-50) : std::log(x); }
-
-}  // namespace aasr
-
-// ---- the statistics handle ---------------------------------------------------------------------
-
-struct aasr_stats {
-  aasr_gmm *gmm = nullptr;
-  int D = 0, S = 0, G = 0, K = 0, W = 0, dimp = 0, rec = 0, max_comps = 0;
-  std::vector<int32_t> mix_off, mix_idx;
-  std::vector<int32_t> tr_source, tr_offset;
-  std::vector<double> tr_count;
-  DevBuf<double> racc, pacc, gacc, slab;
-  DevBuf<int32_t> d_rows, d_pdfs, d_item_begin, g_off, g_rec, rec_pdf;
-  DevBuf<StatsItem> d_items;
-  // host staging of the last accumulate call, kept until its uploads are done
-  std::vector<int32_t> h_rows, h_pdfs, h_item_begin;
-  std::vector<StatsItem> h_items;
-  hipEvent_t staged = nullptr;
-  bool staged_pending = false;
-  // shape of the last launch of the item kernel (aasr_debug_stats_shape): dimp, block, lds_recs, max_comps, items
-  int32_t last_shape[5] = {0, 0, 0, 0, 0};
-  // host copies after aasr_stats_fetch
-  bool fetched = false;
-  std::vector<double> h_racc, h_pacc, h_gacc;
-  // full second moments (aasr_stats_create_full): per pool Gaussian the tiles of sum gamma xi xi^T (stats_full.h)
-  bool full = false;
-  int64_t TS = 0;  // doubles of a Gaussian's accumulator and of a unit's slab
-  int64_t full_slab_bytes = STATS_FULL_SLAB_BYTES;
-  DevBuf<double> facc, fslab, fgam, fpacked;
-  DevBuf<FullItem> d_fitems;
-  DevBuf<FullUnit> d_funits;
-  DevBuf<FullGroup> d_fgroups;
-  DevBuf<int32_t> d_fentries;
-  std::vector<FullItem> h_fitems;
-  std::vector<FullUnit> h_funits;
-  std::vector<FullGroup> h_fgroups;
-  std::vector<int32_t> h_fentries;
-  int32_t full_shape[4] = {0, 0, 0, 0};  // PB, work items, launches, units of the last call (aasr_debug_stats_full_shape)
-  std::vector<double> h_full;            // after a fetch: [G x dim (dim + 1) / 2]
-  ~aasr_stats() {
-    if (staged) (void)hipEventDestroy(staged);
-  }
-};
 
 namespace aasr {
 
@@ -232,6 +176,11 @@ static void stats_full_pass(aasr_stats *h, const double *d_frames, const std::ve
   for (const FullLaunch &L : launches)  // (the launches of a call follow each other on the stream and share the buffers)
     stats_full_launch(p, L.item0, L.n_items, L.unit0, L.n_units, h->d_fgroups.p + L.group0, L.n_groups, h->d_fentries.p,
                       h->facc.p, st);
+}
+
+void require_fetched(const aasr_stats *h, const char *what) {
+  if (!h) raise(AASR_ERR_INVALID, "%s: null argument", what);
+  if (!h->fetched) raise(AASR_ERR_INVALID, "%s: call aasr_stats_fetch after the last accumulation", what);
 }
 
 }  // namespace aasr
@@ -469,11 +418,6 @@ aasr_status aasr_stats_fetch(aasr_stats *h, void *stream) {
   });
 }
 
-static void require_fetched(const aasr_stats *h, const char *what) {
-  if (!h) raise(AASR_ERR_INVALID, "%s: null argument", what);
-  if (!h->fetched) raise(AASR_ERR_INVALID, "%s: call aasr_stats_fetch after the last accumulation", what);
-}
-
 aasr_status aasr_stats_gaussians(const aasr_stats *h, int64_t *feacount, double *gamma, double *aux_gamma,
                                  double *sum_x, double *sum_xx) {
   return guarded([&] {
@@ -536,577 +480,4 @@ aasr_status aasr_stats_transitions(const aasr_stats *h, int32_t *source, int32_t
     }
   });
 }
-
-// ---- dump writers (HmmSet::dump_statistics, HmmSet.cc:546-625) --------------------------------
-
-aasr_status aasr_stats_write_gks(const char *path, int32_t pool_size, int32_t dim, int32_t mode, const int64_t *feacount,
-                                 const double *gamma, const double *aux_gamma, const double *sum_x, const double *sum_xx) {
-  return guarded([&] {
-    if (!path || pool_size < 0 || dim < 0 || (pool_size > 0 && (!feacount || !gamma || !aux_gamma || !sum_x || !sum_xx)))
-      raise(AASR_ERR_INVALID, "aasr_stats_write_gks: bad argument");
-    std::ofstream gks(path, std::ofstream::binary);
-    if (!gks) raise(AASR_ERR_IO, "HmmSet::dump_gk_statistics(): could not open %s", path);
-    gks.write((const char *)&pool_size, sizeof(int));
-    gks.write((const char *)&dim, sizeof(int));
-    gks.write((const char *)&mode, sizeof(int));
-    const int zero = 0, end = -1;
-    for (int g = 0; gks && g < pool_size; g++) {
-      gks.write((const char *)&g, sizeof(int));
-      if (feacount[g] > 0) {  // Gaussian::dump_statistics: the ML buffer, when it was accumulated
-        gks.write((const char *)&zero, sizeof(int));
-        const int fc = (int)feacount[g];
-        gks.write((const char *)&fc, sizeof(int));
-        gks.write((const char *)&gamma[g], sizeof(double));
-        gks.write((const char *)&aux_gamma[g], sizeof(double));
-        for (int d = 0; d < dim; d++) {
-          const float t = (float)sum_x[(size_t)g * dim + d];
-          gks.write((const char *)&t, sizeof(float));
-        }
-        for (int d = 0; d < dim; d++) {
-          const float t = (float)sum_xx[(size_t)g * dim + d];
-          gks.write((const char *)&t, sizeof(float));
-        }
-      }
-      gks.write((const char *)&end, sizeof(int));
-    }
-    if (!gks) raise(AASR_ERR_IO, "write error on %s", path);
-  });
-}
-
-// FullStatisticsAccumulator::dump_statistics (Distributions.cc:42-60) under HmmSet::dump_gk_statistics
-aasr_status aasr_stats_write_gks_full(const char *path, int32_t pool_size, int32_t dim, const int64_t *feacount,
-                                      const double *gamma, const double *aux_gamma, const double *sum_x,
-                                      const double *sum_xx_packed) {
-  return guarded([&] {
-    if (!path || pool_size < 0 || dim < 0 || (pool_size > 0 && (!feacount || !gamma || !aux_gamma || !sum_x || !sum_xx_packed)))
-      raise(AASR_ERR_INVALID, "aasr_stats_write_gks_full: bad argument");
-    std::ofstream gks(path, std::ofstream::binary);
-    if (!gks) raise(AASR_ERR_IO, "HmmSet::dump_gk_statistics(): could not open %s", path);
-    const int mode = 3;  // PDF_ML_STATS | PDF_ML_FULL_STATS
-    gks.write((const char *)&pool_size, sizeof(int));
-    gks.write((const char *)&dim, sizeof(int));
-    gks.write((const char *)&mode, sizeof(int));
-    const int zero = 0, end = -1;
-    const size_t tri = (size_t)dim * (dim + 1) / 2;
-    std::vector<float> t((size_t)dim + tri);
-    for (int g = 0; gks && g < pool_size; g++) {
-      gks.write((const char *)&g, sizeof(int));
-      if (feacount[g] > 0) {
-        gks.write((const char *)&zero, sizeof(int));
-        const int fc = (int)feacount[g];
-        gks.write((const char *)&fc, sizeof(int));
-        gks.write((const char *)&gamma[g], sizeof(double));
-        gks.write((const char *)&aux_gamma[g], sizeof(double));
-        for (int d = 0; d < dim; d++) t[(size_t)d] = (float)sum_x[(size_t)g * dim + d];
-        for (size_t e = 0; e < tri; e++) t[(size_t)dim + e] = (float)sum_xx_packed[(size_t)g * tri + e];  // row by row, j <= i
-        gks.write((const char *)t.data(), (std::streamsize)(t.size() * sizeof(float)));
-      }
-      gks.write((const char *)&end, sizeof(int));
-    }
-    if (!gks) raise(AASR_ERR_IO, "write error on %s", path);
-  });
-}
-
-aasr_status aasr_stats_write_mcs(const char *path, int32_t num_pdfs, int32_t mode, const int32_t *mix_off,
-                                 const int32_t *mix_idx, const int64_t *count, const double *gamma,
-                                 const double *aux_gamma, const double *mixture_ll) {
-  return guarded([&] {
-    if (!path || num_pdfs < 0 || (num_pdfs > 0 && (!mix_off || !mix_idx || !count || !gamma || !mixture_ll)))
-      raise(AASR_ERR_INVALID, "aasr_stats_write_mcs: bad argument");
-    std::ofstream mcs(path);
-    if (!mcs) raise(AASR_ERR_IO, "HmmSet::dump_mc_statistics(): could not open %s", path);
-    mcs << num_pdfs << std::endl;
-    mcs << mode << std::endl;
-    for (int i = 0; i < num_pdfs; i++) {
-      mcs << i << std::endl;
-      // Mixture::dump_statistics (Distributions.cc:2192-2208)
-      mcs.precision(10);
-      if (count[i] > 0) {
-        const int n = mix_off[i + 1] - mix_off[i];
-        mcs << 0 << " " << n;
-        for (int k = 0; k < n; k++) mcs << " " << mix_idx[mix_off[i] + k] << " " << gamma[mix_off[i] + k];
-        mcs << " " << (aux_gamma ? aux_gamma[i] : 0.0) << " " << mixture_ll[i];
-        mcs << std::endl;
-      }
-      mcs << "-1" << std::endl;
-    }
-    if (!mcs) raise(AASR_ERR_IO, "write error on %s", path);
-  });
-}
-
-aasr_status aasr_stats_write_phs(const char *path, int32_t num_transitions, const int32_t *source,
-                                 const int32_t *target_offset, const double *count) {
-  return guarded([&] {
-    if (!path || num_transitions < 0 || (num_transitions > 0 && (!source || !target_offset || !count)))
-      raise(AASR_ERR_INVALID, "aasr_stats_write_phs: bad argument");
-    if (num_transitions == 0) return;  // dump_ph_statistics writes nothing without transitions
-    std::ofstream phs(path);
-    if (!phs) raise(AASR_ERR_IO, "HmmSet::dump_ph_statistics(): could not open %s", path);
-    phs << num_transitions << std::endl;
-    for (int t = 0; t < num_transitions; t++)
-      if (count[t] > 0) {
-        phs << source[t] << " ";
-        phs << target_offset[t] << " ";
-        phs << count[t] << std::endl;
-      }
-    if (!phs) raise(AASR_ERR_IO, "write error on %s", path);
-  });
-}
-
-aasr_status aasr_stats_write_lls(const char *path, double loglik, int64_t frames) {
-  return guarded([&] {
-    if (!path) raise(AASR_ERR_INVALID, "aasr_stats_write_lls: null argument");
-    std::ofstream lls(path);
-    if (!lls) return;  // stats.cc:779: no file, no message
-    lls.precision(12);
-    lls << "Numerator loglikelihood: " << loglik << std::endl;
-    lls << "Number of frames: " << frames << std::endl;
-  });
-}
-
-aasr_status aasr_stats_write(const aasr_stats *h, const char *base) {
-  return guarded([&] {
-    require_fetched(h, "aasr_stats_write");
-    if (!base) raise(AASR_ERR_INVALID, "aasr_stats_write: null argument");
-    const std::string b(base);
-    auto ok = [](aasr_status s) {
-      if (s != AASR_OK) raise(s, "%s", last_error().c_str());
-    };
-    ok(aasr_stats_write_phs((b + ".phs").c_str(), (int32_t)h->tr_source.size(), h->tr_source.data(), h->tr_offset.data(),
-                            h->tr_count.data()));
-    std::vector<int64_t> count((size_t)std::max(1, h->S));
-    std::vector<double> gamma((size_t)std::max(1, h->K)), mll((size_t)std::max(1, h->S)), aux((size_t)std::max(1, h->S), 0.0);
-    ok(aasr_stats_mixtures(h, count.data(), gamma.data(), mll.data()));
-    ok(aasr_stats_write_mcs((b + ".mcs").c_str(), h->S, h->full ? 3 : 1, h->mix_off.data(), h->mix_idx.data(), count.data(),
-                            gamma.data(), aux.data(), mll.data()));
-    const size_t G1 = (size_t)std::max(1, h->G);
-    std::vector<int64_t> fc(G1);
-    std::vector<double> gg(G1), ga(G1), sx(G1 * h->D + 1), sxx(G1 * h->D + 1);
-    ok(aasr_stats_gaussians(h, fc.data(), gg.data(), ga.data(), sx.data(), sxx.data()));
-    if (h->full)
-      ok(aasr_stats_write_gks_full((b + ".gks").c_str(), h->G, h->D, fc.data(), gg.data(), ga.data(), sx.data(), h->h_full.data()));
-    else
-      ok(aasr_stats_write_gks((b + ".gks").c_str(), h->G, h->D, 1, fc.data(), gg.data(), ga.data(), sx.data(), sxx.data()));
-  });
-}
-
-// ---- host-only segmentation reader ---------------------------------------------------------------
-
-static aasr_status read_segmentation_call(const char *what, const aasr_topo *topo, const char *path, float frame_rate,
-                                          int32_t first_frame, int32_t last_frame, int32_t eof_frame, int32_t flags,
-                                          int32_t transitions, int32_t *start_frame, int32_t **pdf, int32_t **transition,
-                                          int32_t *n_frames) {
-  return guarded([&] {
-    if (!topo || !path || !start_frame || !pdf || !transition || !n_frames) raise(AASR_ERR_INVALID, "%s: null argument", what);
-    *pdf = nullptr;
-    *transition = nullptr;
-    if (flags & ~(AASR_PHN_STATE_NUM_LABELS | AASR_PHN_RELATIVE_SAMPLES)) raise(AASR_ERR_INVALID, "%s: unknown flags %d", what, flags);
-    TopoTables tt(topo);
-    Segmentation seg = read_segmentation(topo, tt, path, frame_rate, first_frame, last_frame, eof_frame, transitions != 0, flags);
-    const size_t n = seg.pdf.size();
-    *pdf = (int32_t *)malloc(std::max<size_t>(1, n) * sizeof(int32_t));
-    *transition = (int32_t *)malloc(std::max<size_t>(1, n) * sizeof(int32_t));
-    if (!*pdf || !*transition) {
-      free(*pdf);
-      free(*transition);
-      *pdf = *transition = nullptr;
-      raise(AASR_ERR_INVALID, "out of memory");
-    }
-    std::copy(seg.pdf.begin(), seg.pdf.end(), *pdf);
-    std::fill(*transition, *transition + n, -1);  // (what the reader leaves out when no transitions are asked for)
-    std::copy(seg.tr.begin(), seg.tr.end(), *transition);
-    *start_frame = seg.start_frame;
-    *n_frames = seg.initialized ? (int32_t)n : -1;
-  });
-}
-
-aasr_status aasr_stats_read_segmentation(const aasr_topo *topo, const char *path, float frame_rate, int32_t first_frame,
-                                         int32_t last_frame, int32_t eof_frame, int32_t transitions,
-                                         int32_t *start_frame, int32_t **pdf, int32_t **transition, int32_t *n_frames) {
-  return read_segmentation_call("aasr_stats_read_segmentation", topo, path, frame_rate, first_frame, last_frame, eof_frame, 0,
-                                transitions, start_frame, pdf, transition, n_frames);
-}
-
-aasr_status aasr_phn_read_segmentation(const aasr_topo *topo, const char *path, float frame_rate, int32_t first_frame,
-                                       int32_t last_frame, int32_t eof_frame, int32_t flags, int32_t transitions,
-                                       int32_t *start_frame, int32_t **pdf, int32_t **transition, int32_t *n_frames) {
-  return read_segmentation_call("aasr_phn_read_segmentation", topo, path, frame_rate, first_frame, last_frame, eof_frame,
-                                flags, transitions, start_frame, pdf, transition, n_frames);
-}
-
-void aasr_stats_default_options(aasr_stats_options *o) {
-  if (o) memset(o, 0, sizeof *o);
-}
-
-}  // extern "C"
-
-// ---- the stats main loop over a recipe ---------------------------------------------------------
-
-// ---- Baum-Welch over the recipe's HMM networks (aku/stats.cc with -H) ----------------------------
-
-namespace {
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// HmmNetBaumWelch::next_frame's label of an emitting arc (:763-768): the arc's label without its '#' end marks
-// (LatticeLabel::remove_end_marks) -- the transition index, then the ";..." part the reader kept -- and, where that
-// splits at ';' into three or more fields (mixture;state;phone;...), "phone.state"
-std::string alignment_label(const aasr_hmmnet &net, int32_t arc) {
-  std::string label = std::to_string(net.em_tr[(size_t)arc]);
-  for (char c : net.em_label[(size_t)arc])
-    if (c != '#') label += c;
-  std::vector<std::string> fields;
-  size_t at = 0;
-  for (;;) {
-    const size_t stop = label.find(';', at);
-    fields.push_back(label.substr(at, stop == std::string::npos ? std::string::npos : stop - at));
-    if (stop == std::string::npos) break;
-    at = stop + 1;
-  }
-  return fields.size() >= 3 ? fields[2] + "." + fields[1] : label;
-}
-
-// The alignment file of one utterance as simple_train writes it (aku/stats.cc:116-131, 179-188): runs of one label text,
-// "start end label" in samples; the last line ends one frame past the range (the reference's own "+1": next_frame has
-// stepped once more before it returned false).  cache: the network's labels, filled as they are asked for.
-std::string alignment_text(const aasr_hmmnet &net, std::vector<std::string> &cache, const std::vector<int32_t> &path, int first_frame,
-                           int frame_mult) {
-  cache.resize(net.em_src.size());
-  std::string text;
-  char head[64];
-  int cur_start = -1;
-  const std::string *cur = nullptr;
-  auto put = [&](int end) {
-    snprintf(head, sizeof head, "%d %d ", cur_start * frame_mult, end * frame_mult);
-    text += head;
-    text += *cur;
-    text += '\n';
-  };
-  for (size_t t = 0; t < path.size(); t++) {
-    std::string &label = cache[(size_t)path[t]];
-    if (label.empty()) label = alignment_label(net, path[t]);
-    const int frame = first_frame + (int)t;
-    if (cur_start < 0) {
-      cur_start = frame;
-      cur = &label;
-    } else if (*cur != label) {
-      put(frame);
-      cur_start = frame;
-      cur = &label;
-    }
-  }
-  if (cur_start >= 0) put(first_frame + (int)path.size() + 1);
-  return text;
-}
-
-// The network mode of aasr_run_stats_recipe: per group the steps of logl.cc's network branch, then the occupancies as
-// weighted entries into the accumulation.  -> total_ll, num_frames of the utterances that ran
-void run_stats_networks(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const std::vector<RecipeInfo> &infos,
-                        const aasr_stats_options *opt, const aasr_stats_network_options *nopt, aasr_stats *h,
-                        GroupStager &stager, double *total_ll, int64_t *num_frames) {
-  const hipStream_t stream = stager.stream;
-  const bool accumulate = !opt->no_train, transitions = opt->transitions != 0;
-  const bool timing = getenv("AASR_RECIPE_TIMING") != nullptr;
-  double t_host = 0, t_feat = 0, t_score = 0, t_fb = 0, t_acc = 0;
-  aasr_fb_options fo;
-  aasr_fb_default_options(&fo);
-  if (nopt->fw_beam > 0) fo.fw_beam = nopt->fw_beam;  // set_pruning_thresholds: 0 keeps the default
-  if (nopt->bw_beam > 0) fo.bw_beam = nopt->bw_beam;
-  if (nopt->ac_scale_given) fo.ac_scale = nopt->ac_scale;
-  fo.mode = nopt->viterbi ? AASR_FB_VITERBI : AASR_FB_BAUM_WELCH;
-  fo.want_pdf_occ = 1;
-  fo.device_occ = 1;
-  fo.want_tr_occ = transitions ? 1 : 0;
-  fo.want_path = nopt->alignment ? 1 : 0;
-  std::map<const aasr_hmmnet *, std::vector<std::string>> labels;  // per network, per emitting arc ("" until asked for)
-  std::vector<int32_t> path;
-  const int frame_mult = (int)(16000 / aasr_feat_frame_rate(feat));  // print_alignment_line (aku/stats.cc:59-70)
-  const int S = aasr_gmm_num_states(gmm);
-  const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
-  const float fr = aasr_feat_frame_rate(feat);
-  constexpr int64_t group_frames = (int64_t)1 << 18, group_scores = (int64_t)1 << 27;  // as logl.cc cuts its groups
-  NetworkCache net_cache(topo, S);
-  GroupScores scores;
-  std::vector<int64_t> cnt((size_t)S + 1);
-  std::vector<double> sums, tr_occ;
-  double max_dev = 0;  // max |1 - s_t| over the run
-  int64_t entries = 0;
-  size_t next = 0;
-  while (next < infos.size()) {
-    double t = now_s();
-    const size_t group_first = next;
-    std::vector<std::vector<int16_t>> audio;
-    std::vector<int32_t> start, rows;
-    std::vector<const aasr_hmmnet *> group_nets;
-    std::vector<char> align_open;  // with -a: the utterance's alignment file could be opened
-    int64_t rows_total = 0;
-    while (next < infos.size() && audio.size() < 1024 &&
-           (audio.empty() || (rows_total < group_frames && rows_total * S < group_scores))) {
-      const RecipeInfo &u = infos[next++];
-      announce(u, opt->info);
-      if (nopt->alignment) {  // aku/stats.cc:565-572: the file exists, empty, before the utterance is looked at
-        FILE *af = fopen(u.alignment_path.c_str(), "w");
-        if (!af) fprintf(stderr, "Could not open alignment file %s\n", u.alignment_path.c_str());
-        else fclose(af);
-        align_open.push_back(af != nullptr);
-      }
-      audio.push_back(load_utterance_input(feat, u));
-      // Recipe::Info::init_hmmnet_files (Recipe.cc:198-231)
-      if (u.hmmnet_path.empty()) raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
-      group_nets.push_back(net_cache.get(u.hmmnet_path));
-      int first, n;
-      network_frame_range(u, fr, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), &first, &n);
-      start.push_back(first);
-      rows.push_back(n);
-      rows_total += n;
-    }
-    t_host += now_s() - t;
-    t = now_s();
-    stager.stage(audio, start, rows, [&](size_t i) {
-      if (!opt->speakers) return;
-      const RecipeInfo &u = infos[group_first + i];
-      if (aasr_spkc_set_speaker(opt->speakers, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      if (opt->uttadap && !u.utterance_id.empty() && aasr_spkc_set_utterance(opt->speakers, u.utterance_id.c_str()) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      check_stats_model(gmm);
-    });
-    if (timing) AASR_HIP(hipStreamSynchronize(stream));
-    t_feat += now_s() - t;
-    t = now_s();
-    const void *d_scores = scores.score(gmm, stager.d_x.p, rows_total, f64, stream);
-    if (timing) AASR_HIP(hipStreamSynchronize(stream));
-    t_score += now_s() - t;
-    t = now_s();
-    aasr_fb_batch *b = nullptr;
-    if (aasr_fb_batch_create(&fo, (int32_t)group_nets.size(), group_nets.data(), rows.data(), &b) != AASR_OK)
-      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-    std::unique_ptr<aasr_fb_batch, void (*)(aasr_fb_batch *)> bguard(b, aasr_fb_batch_destroy);
-    std::vector<int64_t> row0;
-    int64_t at = 0;
-    for (int32_t r : rows) {
-      row0.push_back(at);
-      at += r;
-    }
-    // simple_train (aku/stats.cc:79-102): a failed initialisation is run again with 2x ... 5x the backward beam -- new
-    // launches over the failed utterances only
-    int32_t failed = 0;
-    for (int attempt = 1; attempt <= fo.max_attempts; attempt++) {
-      if (aasr_fb_batch_dev(b, d_scores, S, rows_total, f64 ? 1 : 0, row0.data(), attempt, stream) != AASR_OK ||
-          aasr_fb_batch_sync(b, stream, &failed) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      if (failed == 0) break;
-    }
-    const int32_t *d_rows = nullptr;
-    const double *d_weights = nullptr;
-    if (aasr_fb_batch_entries_dev(b, S, row0.data(), stream, cnt.data(), &d_rows, &d_weights) != AASR_OK)
-      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-    entries += cnt[(size_t)S];
-    t_fb += now_s() - t;
-    t = now_s();
-    // the messages in recipe order, and the frame sums: HmmNetBaumWelch::next_frame's sanity check (:772-779)
-    std::vector<char> ran(group_nets.size(), 0);
-    for (size_t i = 0; i < group_nets.size(); i++) {
-      int32_t status = 0, attempts = 0;
-      if (aasr_fb_batch_result(b, (int32_t)i, &status, nullptr, nullptr, &attempts, nullptr, nullptr) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      if (attempts > 1 || status == FB_FAILED_BACKWARD) fprintf(stderr, "Could not initialize the utterance segmentation.\n");
-      for (int k = 2; k <= attempts; k++) fprintf(stderr, "Increasing beam to %.1f\n", k * fo.bw_beam);
-      if (status == FB_FAILED_BACKWARD) {
-        fprintf(stderr, "Giving up for this file\n");
-        continue;
-      }
-      if (status != FB_OK) raise(AASR_ERR_INVALID, "No paths survived to the end of the network!");
-      ran[i] = 1;
-      sums.resize((size_t)rows[i]);
-      if (aasr_fb_batch_frame_sums(b, (int32_t)i, sums.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      for (int32_t f = 0; f < rows[i]; f++) {
-        const double dev = std::fabs(1 - sums[(size_t)f]);
-        if (dev > 0.02) {
-          fprintf(stderr, "Warning: Sum of PDF probabilities is %g at frame %i\n", sums[(size_t)f], start[i] + f);
-          if (sums[(size_t)f] < 0.01)  // (the reference exits here)
-            raise(AASR_ERR_INVALID, "HmmNetBaumWelch: the sum of PDF probabilities is %g at frame %d of %s", sums[(size_t)f],
-                  start[i] + f, infos[group_first + i].audio_path.c_str());
-        }
-        max_dev = std::max(max_dev, dev);
-      }
-      if (nopt->alignment && align_open[i]) {
-        path.resize((size_t)rows[i]);
-        if (aasr_fb_batch_path(b, (int32_t)i, path.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        const std::string text = alignment_text(*group_nets[i], labels[group_nets[i]], path, start[i], frame_mult);
-        write_text_file(infos[group_first + i].alignment_path.c_str(), text.data(), text.size());
-      }
-    }
-    if (accumulate && cnt[(size_t)S] > 0 &&
-        aasr_stats_accumulate_weighted_dev(h, stager.d_x.p, rows_total, cnt.data(), d_rows, d_weights, stream) != AASR_OK)
-      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-    for (size_t i = 0; i < group_nets.size(); i++) {
-      if (!ran[i]) continue;
-      const aasr_hmmnet &net = *group_nets[i];
-      double fw = 0;
-      tr_occ.assign(std::max<size_t>(1, net.trs.size()), 0.0);
-      if (aasr_fb_batch_result(b, (int32_t)i, nullptr, nullptr, &fw, nullptr, nullptr, transitions ? tr_occ.data() : nullptr) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      if (accumulate && transitions)
-        for (size_t k = 0; k < net.trs.size(); k++) {
-          if (net.trs[k] < 0 || (size_t)net.trs[k] >= h->tr_count.size())
-            raise(AASR_ERR_INVALID, "%s: transition %d is not one of the model's %zu", infos[group_first + i].hmmnet_path.c_str(),
-                  net.trs[k], h->tr_count.size());
-          h->tr_count[(size_t)net.trs[k]] += tr_occ[k];
-        }
-      fprintf(stderr, "  %g\n", fw);  // simple_train: the segmentator's total log-likelihood
-      *total_ll += fw;
-      *num_frames += rows[i];
-    }
-    // the batch owns the entries that the accumulation reads: it goes when the stream is done with them
-    AASR_HIP(hipStreamSynchronize(stream));
-    t_acc += now_s() - t;
-  }
-  if (opt->info > 0) {
-    fprintf(stderr, "Largest |1 - sum of PDF probabilities| of a frame: %g\n", max_dev);
-    fprintf(stderr, "Weighted entries: %lld over %lld frames\n", (long long)entries, (long long)*num_frames);
-  }
-  if (timing)
-    fprintf(stderr,
-            "stats timing: input and networks %.3f s, features %.3f s, scoring %.3f s, forward-backward and entries %.3f s, "
-            "accumulation %.3f s\n",
-            t_host, t_feat, t_score, t_fb, t_acc);
-}
-
-}  // namespace
-
-static aasr_status run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
-                                    const aasr_stats_options *opt, const aasr_stats_network_options *nopt,
-                                    aasr_run_stats *stats) {
-  return guarded([&] {
-    if (!feat || !gmm || !topo || !recipe_path || !opt || (!opt->no_train && !opt->out))
-      raise(AASR_ERR_INVALID, "%s: null argument", nopt ? "aasr_run_stats_networks_recipe" : "aasr_run_stats_recipe");
-    const auto t0 = std::chrono::steady_clock::now();
-    check_feature_dim(gmm, feat);
-    if (nopt && opt->full_stats)
-      raise(AASR_ERR_UNSUPPORTED, "stats: --full-stats is not supported with --networks (full second moments are collected over .phn files only)");
-    if (nopt && nopt->alignment && opt->ophn) raise(AASR_ERR_INVALID, "Can not read and write to output PHNs");  // aku/stats.cc:516-517
-    if (nopt && nopt->alignment && !nopt->viterbi)
-      raise(AASR_ERR_UNSUPPORTED, "stats: alignment output needs the Viterbi mode (-M vit): under Baum-Welch no single arc belongs to a frame");
-    if (nopt && opt->ophn)
-      raise(AASR_ERR_UNSUPPORTED, "stats: -O is not supported with --networks (a network line has no segmentation to choose)");
-    // stats reads its recipe with cluster_speakers = false (aku/stats.cc:422-424)
-    const std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, false);
-    refuse_line_limits(infos, "stats");
-    aasr_stats *h = nullptr;
-    {  // (a model the accumulation kernel has no shape for keeps its AASR_ERR_UNSUPPORTED)
-      const aasr_status cs = opt->full_stats && !opt->no_train ? aasr_stats_create_full(gmm, topo, &h) : aasr_stats_create(gmm, topo, &h);
-      if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
-    }
-    std::unique_ptr<aasr_stats, void (*)(aasr_stats *)> hguard(h, aasr_stats_destroy);
-    const TopoTables tt(topo);
-    const float fr = aasr_feat_frame_rate(feat);
-    const bool accumulate = !opt->no_train, transitions = opt->transitions != 0;
-    GroupStager stager(feat, opt->speakers);
-    const hipStream_t stream = stager.stream;
-    DevBuf<double> d_ll;
-    double total_ll = 0;
-    int64_t num_frames = 0;
-    // groups of utterances accumulated in one launch; their frames stay on the device
-    const int64_t max_group_frames = (int64_t)1 << 20;
-    size_t next = 0;
-    if (nopt) {
-      run_stats_networks(feat, gmm, topo, infos, opt, nopt, h, stager, &total_ll, &num_frames);
-      next = infos.size();
-    }
-    while (next < infos.size()) {
-      // host side first: audio and segmentation, the -i messages in recipe order
-      const size_t group_first = next;
-      std::vector<std::vector<int16_t>> audio;
-      std::vector<Segmentation> segs;
-      std::vector<int32_t> start, rows, pdfs;
-      int64_t rows_total = 0;
-      while (next < infos.size() && audio.size() < 1024 && rows_total < max_group_frames) {
-        const RecipeInfo &u = infos[next++];
-        announce(u, opt->info);
-        audio.push_back(load_utterance_input(feat, u));
-        int first, last;
-        frame_range(u, fr, &first, &last);
-        segs.push_back(read_segmentation(topo, tt, (opt->ophn ? u.alignment_path : u.transcript_path).c_str(), fr, first,
-                                         last, aasr_feat_eof_frame(feat, (int64_t)audio.back().size()), transitions));
-        const Segmentation &seg = segs.back();
-        if (!seg.initialized) {
-          fprintf(stderr, "Could not initialize the utterance segmentation.\n");
-          fprintf(stderr, "Giving up for this file\n");
-          audio.back().clear();  // no frames; kept in the group for its speaker settings (stats.cc:560-565 run first)
-        }
-        start.push_back(seg.start_frame);
-        rows.push_back((int32_t)seg.pdf.size());
-        pdfs.insert(pdfs.end(), seg.pdf.begin(), seg.pdf.end());
-        rows_total += (int64_t)seg.pdf.size();
-      }
-      d_ll.ensure((size_t)std::max<int64_t>(1, rows_total));
-      // features of the group into one device buffer, speaker configuration per utterance
-      stager.stage(audio, start, rows, [&](size_t i) {
-        if (!opt->speakers) return;
-        const RecipeInfo &u = infos[group_first + i];
-        if (aasr_spkc_set_speaker(opt->speakers, u.speaker_id.c_str()) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        if (opt->uttadap && !u.utterance_id.empty() &&
-            aasr_spkc_set_utterance(opt->speakers, u.utterance_id.c_str()) != AASR_OK)
-          raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-        check_stats_model(gmm);
-      });
-      if (accumulate && transitions)
-        for (const Segmentation &seg : segs)
-          if (aasr_stats_add_transitions(h, seg.tr.data(), (int64_t)seg.tr.size()) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      if (rows_total == 0) continue;
-      if (aasr_stats_accumulate_dev(h, stager.d_x.p, rows_total, pdfs.data(), d_ll.p, stream) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      // the .lls figure in frame order: state likelihoods, then the transition taken (stats.cc:130-160)
-      std::vector<double> ll((size_t)rows_total);
-      AASR_HIP(hipMemcpyAsync(ll.data(), d_ll.p, ll.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-      AASR_HIP(hipStreamSynchronize(stream));
-      size_t row = 0;
-      for (const Segmentation &seg : segs)
-        for (size_t f = 0; f < seg.pdf.size(); f++) {
-          total_ll += ll[row++];  // safe_log(1.0 * state_likelihood): the kernel's safe_log(total)
-          if (!(transitions && accumulate) || seg.tr[f] < 0) continue;
-          const int t = seg.tr[f], s = h->tr_source[(size_t)t];
-          total_ll += safe_log(1.0 * tt.probs[(size_t)s][(size_t)(t - tt.tr_base[(size_t)s])]);
-        }
-      num_frames += rows_total;
-    }
-    if (opt->info > 0) {
-      fprintf(stderr, "Finished collecting statistics (%i/%i)\n", opt->batch_index, opt->num_batches);
-      fprintf(stderr, "Total num log likelihood: %g\n", total_ll);
-    }
-    const std::string out = opt->out ? opt->out : "";
-    if (accumulate) {
-      if (aasr_stats_fetch(h, stream) != AASR_OK || aasr_stats_write(h, out.c_str()) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-    }
-    if (opt->out) {
-      const aasr_status st = aasr_stats_write_lls((out + ".lls").c_str(), total_ll, num_frames);
-      if (st != AASR_OK) raise(st, "%s", last_error().c_str());
-    }
-    fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, 0);
-  });
-}
-
-extern "C" {
-
-aasr_status aasr_run_stats_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
-                                  const aasr_stats_options *opt, aasr_run_stats *stats) {
-  return run_stats_recipe(feat, gmm, topo, recipe_path, opt, nullptr, stats);
-}
-
-void aasr_stats_network_default_options(aasr_stats_network_options *o) {
-  if (o) memset(o, 0, sizeof *o);
-  if (o) o->ac_scale = 1;
-}
-
-aasr_status aasr_run_stats_networks_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo *topo, const char *recipe_path,
-                                           const aasr_stats_options *opt, const aasr_stats_network_options *net,
-                                           aasr_run_stats *stats) {
-  aasr_stats_network_options defaults;
-  aasr_stats_network_default_options(&defaults);
-  return run_stats_recipe(feat, gmm, topo, recipe_path, opt, net ? net : &defaults, stats);
-}
-
 }  // extern "C"

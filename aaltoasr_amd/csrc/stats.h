@@ -1,5 +1,6 @@
 // stats.h -- device layout of ML statistics accumulation (stats_accum.hip), shared with its host
-// driver (stats.cc).
+// driver (stats.cc), and the statistics handle as its writers (stats_files.cc) and the recipe driver
+// (stats_recipe.cc) see it.
 //
 // Frames are grouped by pdf on the host: a compressed row list of the frames of every pdf, cut into
 // work items of at most STATS_CHUNK frames.  An item's workgroup writes one slab of partial sums:
@@ -12,6 +13,9 @@
 
 #include <cstdint>
 #include <vector>
+
+#include "common.h"
+#include "stats_full.h"
 
 struct aasr_gmm;
 
@@ -67,5 +71,53 @@ void stats_pdf_reduce_launch(const int32_t *pdfs, const int32_t *item_begin, int
 // g_rec[g_off[g] .. g_off[g+1]) (rec_pdf: the pdf of every record)
 void stats_gauss_reduce_launch(const double *racc, const double *pacc, const int32_t *g_off, const int32_t *g_rec,
                                const int32_t *rec_pdf, int n_gauss, int dim, double *gacc, hipStream_t stream);
+
+}  // namespace aasr
+
+// ---- the statistics handle ---------------------------------------------------------------------
+
+struct aasr_stats {
+  aasr_gmm *gmm = nullptr;
+  int D = 0, S = 0, G = 0, K = 0, W = 0, dimp = 0, rec = 0, max_comps = 0;
+  std::vector<int32_t> mix_off, mix_idx;
+  std::vector<int32_t> tr_source, tr_offset;
+  std::vector<double> tr_count;
+  aasr::DevBuf<double> racc, pacc, gacc, slab;
+  aasr::DevBuf<int32_t> d_rows, d_pdfs, d_item_begin, g_off, g_rec, rec_pdf;
+  aasr::DevBuf<aasr::StatsItem> d_items;
+  // host staging of the last accumulate call, kept until its uploads are done
+  std::vector<int32_t> h_rows, h_pdfs, h_item_begin;
+  std::vector<aasr::StatsItem> h_items;
+  hipEvent_t staged = nullptr;
+  bool staged_pending = false;
+  // shape of the last launch of the item kernel (aasr_debug_stats_shape): dimp, block, lds_recs, max_comps, items
+  int32_t last_shape[5] = {0, 0, 0, 0, 0};
+  // host copies after aasr_stats_fetch
+  bool fetched = false;
+  std::vector<double> h_racc, h_pacc, h_gacc;
+  // full second moments (aasr_stats_create_full): per pool Gaussian the tiles of sum gamma xi xi^T (stats_full.h)
+  bool full = false;
+  int64_t TS = 0;  // doubles of a Gaussian's accumulator and of a unit's slab
+  int64_t full_slab_bytes = aasr::STATS_FULL_SLAB_BYTES;
+  aasr::DevBuf<double> facc, fslab, fgam, fpacked;
+  aasr::DevBuf<aasr::FullItem> d_fitems;
+  aasr::DevBuf<aasr::FullUnit> d_funits;
+  aasr::DevBuf<aasr::FullGroup> d_fgroups;
+  aasr::DevBuf<int32_t> d_fentries;
+  std::vector<aasr::FullItem> h_fitems;
+  std::vector<aasr::FullUnit> h_funits;
+  std::vector<aasr::FullGroup> h_fgroups;
+  std::vector<int32_t> h_fentries;
+  int32_t full_shape[4] = {0, 0, 0, 0};  // PB, work items, launches, units of the last call (aasr_debug_stats_full_shape)
+  std::vector<double> h_full;            // after a fetch: [G x dim (dim + 1) / 2]
+  ~aasr_stats() {
+    if (staged) (void)hipEventDestroy(staged);
+  }
+};
+
+namespace aasr {
+
+// "<what>: null argument" / "<what>: call aasr_stats_fetch after the last accumulation"
+void require_fetched(const aasr_stats *h, const char *what);
 
 }  // namespace aasr

@@ -1238,11 +1238,7 @@ extern "C" aasr_status aasr_run_tie_recipe(const char *feat_cfg_text, const char
         }
         stager.stage(audio, start, rows, [&](size_t i) {
           if (i == 0) AASR_HIP(hipEventRecord(ev[0], stream));
-          if (!spk) return;
-          const RecipeInfo &u = infos[group_first + i];  // tie.cc:207-212
-          if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-          if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
-            raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+          apply_speaker(spk, infos[group_first + i]);  // tie.cc:207-212
         });
         AASR_HIP(hipEventRecord(ev[1], stream));
         if (rows_total > 0 && aasr_scatter_accumulate_dev(sc, stager.d_x.p, rows_total, cls.data(), nullptr, stream) != AASR_OK)

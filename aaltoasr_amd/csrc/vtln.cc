@@ -159,9 +159,7 @@ aasr_status aasr_run_vtln_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_topo
 
     // set_speaker (aku/vtln.cc:47-86) -> the index of the grid point's warp factor in the speaker's list
     auto set_speaker = [&](const RecipeInfo &u, int grid_iter) -> int {
-      if (aasr_spkc_set_speaker(spk, u.speaker_id.c_str()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      if (!u.utterance_id.empty() && aasr_spkc_set_utterance(spk, u.utterance_id.c_str()) != AASR_OK)
-        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      apply_speaker(spk, u);
       check_stats_model(gmm, "vtln");  // (a speaker's cmllr block would have reached the model by now)
       auto it = speaker_stats.find(u.speaker_id);
       if (it == speaker_stats.end()) {
