@@ -42,18 +42,9 @@ int main(int argc, char *argv[]) {
   const int device = config["device"].get_int();
   if (device >= 0 && aasr_set_device(device) != AASR_OK) die(aasr_last_error());
 
-  const std::string cfg = config["config"].get_str();
-  std::ifstream cin_(cfg);
-  if (!cin_) die("could not open " + cfg);
-  std::stringstream ss;
-  ss << cin_.rdbuf();
-  aasr_feat *feat = nullptr;
-  aasr_gmm *gmm = nullptr;
+  // the topology and the options need no device: an empty batch checks the options before any model is loaded
   aasr_topo *topo = nullptr;
-  if (aasr_feat_create(ss.str().c_str(), &feat) != AASR_OK) die(aasr_last_error());
-  if (aasr_gmm_create_from_files(gk.c_str(), mc.c_str(), ph.c_str(), &gmm) != AASR_OK) die(aasr_last_error());
   if (aasr_topo_create_from_ph(ph.c_str(), &topo) != AASR_OK) die(aasr_last_error());
-
   aasr_align_options opt;
   aasr_align_default_options(&opt);
   opt.swins = config["swins"].get_int();
@@ -66,6 +57,23 @@ int main(int argc, char *argv[]) {
   opt.info = config["info"].get_int();
   opt.num_batches = config["batch"].get_int();
   opt.batch_index = config["bindex"].get_int();
+  {
+    aasr_align_batch *none = nullptr;
+    if (aasr_align_batch_create(topo, &opt, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &none) != AASR_OK)
+      die(aasr_last_error());
+    aasr_align_batch_destroy(none);
+  }
+
+  const std::string cfg = config["config"].get_str();
+  std::ifstream cin_(cfg);
+  if (!cin_) die("could not open " + cfg);
+  std::stringstream ss;
+  ss << cin_.rdbuf();
+  aasr_feat *feat = nullptr;
+  aasr_gmm *gmm = nullptr;
+  if (aasr_feat_create(ss.str().c_str(), &feat) != AASR_OK) die(aasr_last_error());
+  if (aasr_gmm_create_from_files(gk.c_str(), mc.c_str(), ph.c_str(), &gmm) != AASR_OK) die(aasr_last_error());
+
   aasr_spkc *spk = nullptr;
   if (config["speakers"].specified) {
     if (aasr_spkc_create(feat, gmm, &spk) != AASR_OK) die(aasr_last_error());

@@ -331,6 +331,17 @@ aasr_status aasr_align_batch_create(const aasr_topo *topo, const aasr_align_opti
     // a beam that doubling cannot raise past maxbeam would retry without end
     if (!(opt->beam > 0) || !std::isfinite(opt->beam) || !std::isfinite(opt->maxbeam) || opt->sbeam < 0)
       raise(AASR_ERR_INVALID, "aasr_align_batch_create: beam must be positive and finite, maxbeam finite, sbeam >= 0");
+    // a window commits its first `target` frames and moves to path[target]: the path has swins entries, so the
+    // target must stay below swins (overlap > 0) and leave a frame to commit (overlap < 1)
+    if (!std::isfinite(opt->overlap))
+      raise(AASR_ERR_INVALID, "aasr_align_batch_create: overlap must be finite");
+    const float kept = 1 - opt->overlap;
+    const float commit = opt->swins * kept;  // compared as a float: a wild overlap does not fit an int
+    if (!(commit >= 1)) raise(AASR_ERR_INVALID, "aasr_align_batch_create: overlap leaves no frame to commit");
+    if ((double)commit >= (double)opt->swins)
+      raise(AASR_ERR_INVALID, "aasr_align_batch_create: overlap must be positive (a window of %d frames would commit all)",
+            opt->swins);
+    const int target = (int)commit;
     if (topo->max_off > 255) raise(AASR_ERR_INVALID, "aasr_align_batch_create: transition offset over 255");
     require_device();
     std::unique_ptr<aasr_align_batch> b(new aasr_align_batch());
@@ -340,9 +351,7 @@ aasr_status aasr_align_batch_create(const aasr_topo *topo, const aasr_align_opti
     b->width = align_width(*opt, topo->max_off);
     if (b->width > 5000)  // LDS: two frames of cells and the new frame's likelihoods
       raise(AASR_ERR_INVALID, "aasr_align_batch_create: lattice width %d (swins / sbeam) exceeds 5000", b->width);
-    const float overlap = 1 - opt->overlap;
-    b->target = (int)(opt->swins * overlap);
-    if (b->target < 1) raise(AASR_ERR_INVALID, "aasr_align_batch_create: overlap leaves no frame to commit");
+    b->target = target;
     // transcriptions: per position the HMM state
     std::vector<int32_t> tr_state, lines;
     b->utt.resize((size_t)n_utt);

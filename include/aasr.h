@@ -632,7 +632,9 @@ typedef struct aasr_align_options {
   double beam;           /* --beam: log-probability beam (100)                         */
   int32_t sbeam;         /* --sbeam: state beam (100)                                  */
   double maxbeam;        /* --maxbeam: retries double the beams up to this (1600)      */
-  float overlap;         /* --overlap: window overlap (0.4)                            */
+  float overlap;         /* --overlap: window overlap (0.4); a window commits          */
+                         /* (int)(swins * (1 - overlap)) frames, which must be         */
+                         /* 1 .. swins - 1: overlap <= 0, >= 1 or not finite is invalid */
   int32_t no_force_end;  /* --no-force-end                                             */
   int32_t phoseg;        /* --phoseg: phone segmentation instead of states             */
   int32_t info;          /* -i                                                         */

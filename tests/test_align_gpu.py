@@ -6,10 +6,13 @@
    linked with the engine), over windows and moves, --phoseg, --no-force-end, start/end times, -S, a
    topology with skip transitions and unequal probabilities, and beams tight enough to retry;
 3. 300 utterances in one batch equal 300 single-utterance searches and the plain Viterbi;
-4. edge cases: a one-frame utterance and a transcript longer than the utterance."""
+4. edge cases: a one-frame utterance and a transcript longer than the utterance.
+The windowed search itself -- ring wraps, moves, both beams, retries, ties, float64 rows -- is compared with a plain
+restatement at the kernel's interface in tests/test_align_windows_gpu.py."""
 import os
 import re
 import subprocess
+import sys
 import wave
 
 import numpy as np
@@ -18,6 +21,8 @@ import pytest
 from aaltoasr_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from viterbi_restate import global_viterbi  # noqa: E402
 BIN = os.path.join(ROOT, "aaltoasr_amd", "lib", "bin")
 REFBIN = os.path.join(ROOT, "oracle", "_ref")
 
@@ -63,32 +68,6 @@ def topo_tables(topo, n_states):
     for s in range(n_states):
         out.append([(o, np.float32(np.log(p))) for o, p in topo.transitions(s)])
     return out
-
-
-def global_viterbi(ll, states, trans, force_end=True):
-    """Plain DP over positions: V[t, p] = max_q V[t-1, q] + log a(q -> p) + ll[t, p], V[0, 0] = 0."""
-    T, P = ll.shape[0], len(states)
-    V = np.full(P, -np.inf)
-    V[0] = 0.0
-    back = np.zeros((T, P), np.int64)
-    for t in range(1, T):
-        best = np.full(P, -np.inf)
-        arg = np.zeros(P, np.int64)
-        for q in range(P):
-            if V[q] == -np.inf:
-                continue
-            for off, lp in trans[states[q]]:
-                p = q + off
-                if p < P and V[q] + lp > best[p]:
-                    best[p] = V[q] + lp
-                    arg[p] = q
-        V = best + ll[t, states]
-        back[t] = arg
-    pos = np.zeros(T, np.int64)
-    pos[-1] = P - 1 if force_end else int(np.argmax(V))
-    for t in range(T - 1, 0, -1):
-        pos[t - 1] = back[t, pos[t]]
-    return pos
 
 
 @pytest.fixture(scope="module")

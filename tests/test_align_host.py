@@ -189,3 +189,43 @@ def test_beams_that_would_retry_without_end_are_refused(topo, kw):
     st = A.lib().aasr_align_batch_create(topo.handle, C.byref(opts), 1, one, zero, zero, zero, one, C.byref(b))
     assert st == A.AASR_ERR_INVALID
     assert "beam" in A.lib().aasr_last_error().decode()
+
+
+@pytest.mark.parametrize("overlap", [0.0, -0.5, float("nan"), 1.0, float("inf"), -1e30])
+def test_overlaps_that_commit_a_whole_window_or_nothing_are_refused(topo, overlap):
+    """overlap <= 0 commits all swins frames of a window and then moves to path[swins], one past the path;
+    overlap >= 1 commits none.  Both are refused before any device is asked for."""
+    opts = A.AlignOptions.defaults(overlap=overlap)
+    one = (C.c_int32 * 2)(0, 1)
+    zero = (C.c_int32 * 1)(0)
+    b = C.c_void_p()
+    st = A.lib().aasr_align_batch_create(topo.handle, C.byref(opts), 1, one, zero, zero, zero, one, C.byref(b))
+    assert st == A.AASR_ERR_INVALID
+    assert "overlap" in A.lib().aasr_last_error().decode()
+
+
+def test_smallest_and_largest_overlap_pass_the_option_checks(topo):
+    """swins 10: overlap 0.1 commits 9 frames, 0.9 commits 1 (the float product rounds up to 1.0)-- neither is
+    refused for its overlap (what comes next needs a device, or succeeds on one)"""
+    for overlap in (0.1, 0.9, 0.4):
+        opts = A.AlignOptions.defaults(overlap=overlap, swins=10)
+        one = (C.c_int32 * 2)(0, 1)
+        zero = (C.c_int32 * 1)(0)
+        b = C.c_void_p()
+        st = A.lib().aasr_align_batch_create(topo.handle, C.byref(opts), 1, one, zero, zero, zero, one, C.byref(b))
+        if st == A.AASR_OK:
+            A.lib().aasr_align_batch_destroy(b)
+        else:
+            assert "overlap" not in A.lib().aasr_last_error().decode()
+
+
+def test_align_tool_refuses_overlap_zero(lib, tmp_path):
+    """the tool checks its options before it loads a model or asks for a device"""
+    ph = tmp_path / "m.ph"
+    ph.write_text(PH)
+    exe = os.path.join(BIN, "align")
+    r = subprocess.run([exe, "-g", str(tmp_path / "m.gk"), "-m", str(tmp_path / "m.mc"), "-p", str(ph),
+                        "-c", str(tmp_path / "f.cfg"), "-r", str(tmp_path / "r.recipe"), "--overlap", "0"],
+                       capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0
+    assert "overlap" in r.stderr and "must be positive" in r.stderr
