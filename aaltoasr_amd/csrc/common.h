@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "../../include/aasr.h"
 
@@ -108,5 +109,22 @@ struct DevBuf {
 };
 
 void require_device();
+
+// Kernel instances chosen by a run-time value: f(std::integral_constant<int, N>()) for the N among Ns that equals v.
+// false: v is none of them (the caller raises its own message).
+template <int... Ns, class F>
+bool dispatch_among(int v, F &&f) {
+  return ((v == Ns && (f(std::integral_constant<int, Ns>()), true)) || ...);
+}
+// the padded dimensions the statistics item kernels are instantiated for
+template <class F>
+bool dispatch_dimp(int dimp, F &&f) {
+  return dispatch_among<8, 16, 24, 32, 40, 48, 64, 96, 128, 192>(dimp, f);
+}
+// the 16-blocks of a padded [1, x] row the triangular tile kernels are instantiated for (d <= 127)
+template <class F>
+bool dispatch_pb(int pb, F &&f) {
+  return dispatch_among<1, 2, 3, 4, 5, 6, 7, 8>(pb, f);
+}
 
 }  // namespace aasr

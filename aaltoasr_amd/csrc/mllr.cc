@@ -53,6 +53,38 @@ static void check_mllr_model(const aasr_gmm *g) {
     raise(AASR_ERR_UNSUPPORTED, "mllr: the statistics are collected on the unadapted model (a model transform is loaded)");
 }
 
+// The launches of a call, each of at most MLLR_CHUNK MLLR_MAX_CHUNKS frames: they follow each other on the stream and
+// share w, u, ok and the slab.  Per launch pass1(p, f0), which launches pass 1 for the frames from f0 on (p.x and p.n are
+// set; it adds what its kernel reads of the frames), then the rank pass.
+template <class Pass1>
+static void mllr_launches(aasr_mllr *h, const double *d_frames, int64_t n_frames, hipStream_t st, Pass1 pass1) {
+  const int64_t launch = (int64_t)MLLR_CHUNK * MLLR_MAX_CHUNKS;
+  const int64_t cap = std::min(launch, n_frames);
+  h->w.ensure((size_t)cap * h->D);
+  h->u.ensure((size_t)cap * (h->D + 1));
+  h->ok.ensure((size_t)cap);
+  h->slab.ensure((size_t)((cap + MLLR_CHUNK - 1) / MLLR_CHUNK) * h->SL);
+  MllrParams p{};
+  p.dim = h->D;
+  p.recs = h->gmm->f64_recs.p;
+  p.dimp = h->gmm->f64_dimp;
+  p.rec = 2 * p.dimp + 2;
+  p.state_off = h->gmm->f64_state_off.p;
+  p.inv_var = h->inv_var.p;
+  p.mean_var = h->mean_var.p;
+  p.max_comps = h->max_comps;
+  p.w = h->w.p;
+  p.u = h->u.p;
+  p.ok = h->ok.p;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += launch) {
+    p.x = d_frames + (size_t)f0 * h->D;
+    p.n = (int32_t)std::min(launch, n_frames - f0);
+    pass1(p, f0);
+    mllr_rank_launch(p, h->slab.p, h->acc.p, st);
+  }
+  h->fetched = false;
+}
+
 }  // namespace aasr
 
 extern "C" {
@@ -127,32 +159,10 @@ aasr_status aasr_mllr_accumulate_dev(aasr_mllr *h, const double *d_frames, int64
     AASR_HIP(hipMemcpyAsync(h->d_pdf.p, h->h_pdf.data(), (size_t)n_frames * sizeof(int32_t), hipMemcpyHostToDevice, st));
     AASR_HIP(hipEventRecord(h->staged, st));
     h->staged_pending = true;
-    const int64_t launch = (int64_t)MLLR_CHUNK * MLLR_MAX_CHUNKS;
-    const int64_t cap = std::min(launch, n_frames);
-    h->w.ensure((size_t)cap * h->D);
-    h->u.ensure((size_t)cap * (h->D + 1));
-    h->ok.ensure((size_t)cap);
-    h->slab.ensure((size_t)((cap + MLLR_CHUNK - 1) / MLLR_CHUNK) * h->SL);
-    MllrParams p{};
-    p.dim = h->D;
-    p.recs = h->gmm->f64_recs.p;
-    p.dimp = h->gmm->f64_dimp;
-    p.rec = 2 * p.dimp + 2;
-    p.state_off = h->gmm->f64_state_off.p;
-    p.inv_var = h->inv_var.p;
-    p.mean_var = h->mean_var.p;
-    p.max_comps = h->max_comps;
-    p.w = h->w.p;
-    p.u = h->u.p;
-    p.ok = h->ok.p;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += launch) {  // (the launches of a call follow each other on the stream)
-      p.x = d_frames + (size_t)f0 * h->D;
+    mllr_launches(h, d_frames, n_frames, st, [&](MllrParams &p, int64_t f0) {
       p.pdf = h->d_pdf.p + f0;
-      p.n = (int32_t)std::min(launch, n_frames - f0);
       mllr_weights_launch(p, st);
-      mllr_rank_launch(p, h->slab.p, h->acc.p, st);
-    }
-    h->fetched = false;
+    });
   });
 }
 
@@ -165,38 +175,16 @@ aasr_status aasr_mllr_accumulate_weighted_dev(aasr_mllr *h, const double *d_fram
     if (n_frames == 0) return;
     check_mllr_model(h->gmm);
     const hipStream_t st = (hipStream_t)stream;
-    // the cuts of aasr_mllr_accumulate_dev: launches of MLLR_CHUNK MLLR_MAX_CHUNKS frames
-    const int64_t launch = (int64_t)MLLR_CHUNK * MLLR_MAX_CHUNKS;
-    const int64_t cap = std::min(launch, n_frames);
-    h->w.ensure((size_t)cap * h->D);
-    h->u.ensure((size_t)cap * (h->D + 1));
-    h->ok.ensure((size_t)cap);
-    h->slab.ensure((size_t)((cap + MLLR_CHUNK - 1) / MLLR_CHUNK) * h->SL);
     MllrEntryParams q{};
-    MllrParams &p = q.p;
-    p.dim = h->D;
-    p.recs = h->gmm->f64_recs.p;
-    p.dimp = h->gmm->f64_dimp;
-    p.rec = 2 * p.dimp + 2;
-    p.state_off = h->gmm->f64_state_off.p;
-    p.inv_var = h->inv_var.p;
-    p.mean_var = h->mean_var.p;
-    p.max_comps = h->max_comps;
-    p.w = h->w.p;
-    p.u = h->u.p;
-    p.ok = h->ok.p;
     q.pdf = d_pdf;
     q.weight = d_weight;
     q.n_entries = n_entries;
     q.n_states = h->S;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += launch) {
-      p.x = d_frames + (size_t)f0 * h->D;
+    mllr_launches(h, d_frames, n_frames, st, [&](MllrParams &p, int64_t f0) {
+      q.p = p;
       q.off = d_off + f0;
-      p.n = (int32_t)std::min(launch, n_frames - f0);
       mllr_entry_weights_launch(q, st);
-      mllr_rank_launch(p, h->slab.p, h->acc.p, st);
-    }
-    h->fetched = false;
+    });
   });
 }
 

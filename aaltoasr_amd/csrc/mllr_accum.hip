@@ -14,10 +14,10 @@
 
 #include "common.h"
 #include "mllr.h"
+#include "mllr_pass1.h"
+#include "tri_scatter.h"
 
 namespace aasr {
-
-typedef double mllr_f64x4 __attribute__((ext_vector_type(4)));
 
 size_t mllr_weights_lds_bytes(int dim, int max_comps) {
   return (size_t)MLLR_P1_FRAMES * ((dim | 1) + max_comps + 1) * sizeof(double) + (size_t)2 * MLLR_P1_FRAMES * sizeof(int32_t);
@@ -26,7 +26,7 @@ size_t mllr_weights_lds_bytes(int dim, int max_comps) {
 // LDS: [frames: 64 x (dim | 1)][posteriors: 64 x max_comps][beta share: 64][first record: 64][components: 64]
 __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_weights(MllrParams p) {
   extern __shared__ double lds[];
-  const int D = p.dim, XS = D | 1, MC = p.max_comps, REC = p.rec, DP = p.dimp, B = MLLR_P1_FRAMES;
+  const int D = p.dim, XS = D | 1, MC = p.max_comps, B = MLLR_P1_FRAMES;
   double *xs = lds;
   double *lg = xs + B * XS;
   double *lbeta = lg + B * MC;
@@ -47,31 +47,8 @@ __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_weights(MllrParams p) {
       r0 = p.state_off[pdf];
       M = p.state_off[pdf + 1] - r0;
     }
-    const double *x = xs + t * XS;
-    double sum = 0;
-    for (int k = 0; k < M; k++) {
-      const double *rec = p.recs + (size_t)(r0 + k) * REC;
-      double ll = 0;
-      for (int d = 0; d < D; d++) {
-        const double df = x[d] - rec[d];
-        ll += df * df * rec[DP + d];
-      }
-      ll *= -0.5;
-      ll += rec[2 * DP];
-      const double lik = exp(ll);
-      lg[t * MC + k] = lik;
-      sum += lik;
-    }
-    // the posteriors ignore the mixture weights (MllrTrainer.cc:40-49): prior * lik / sum with the .phn
-    // segmentation's prior of 1; a component whose value is not > 0 adds nothing (MllrTrainer.cc:153), so a frame
-    // whose sum is 0 or not finite adds nothing at all
-    double beta = 0;
-    for (int k = 0; k < M; k++) {
-      double pr = 1.0 * lg[t * MC + k] / sum;
-      if (!(pr > 0)) pr = 0;
-      lg[t * MC + k] = pr;
-      beta += pr;
-    }
+    // the .phn segmentation's prior of 1
+    const double beta = mllr_posteriors(p, xs + t * XS, r0, M, 1.0, lg + t * MC, 0.0);
     lbeta[t] = beta;
     lr0[t] = r0;
     lm[t] = M;
@@ -98,8 +75,6 @@ __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_weights(MllrParams p) {
   }
 }
 
-// f64 16x16x4: lane l holds A[row l % 16][k l / 16] and B[k l / 16][col l % 16]; result register r of lane l is
-// D[row l / 16 + 4 r][col l % 16] (not the f32 shapes' 4 (l / 16) + r).
 template <int PB>
 __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_rank(MllrParams p, double *__restrict__ slab) {
   constexpr int NT = PB * (PB + 1) / 2;
@@ -111,9 +86,9 @@ __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_rank(MllrParams p, double
   const int t0 = blockIdx.x * MLLR_CHUNK, t1 = min(p.n, t0 + MLLR_CHUNK);
   const bool is_g = job < D;
   const int krow = (job - D) * 16 + r16;  // k jobs: the lane's row of U^T
-  mllr_f64x4 acc[NT];
+  tile_f64x4 acc[NT];
 #pragma unroll
-  for (int i = 0; i < NT; i++) acc[i] = mllr_f64x4{0, 0, 0, 0};
+  for (int i = 0; i < NT; i++) acc[i] = tile_f64x4{0, 0, 0, 0};
   // the lane's operands of the step at frame t: xi per block and the weight of its A side
   auto load = [&](int t, double (&xi)[PB], double &wt) {
     const bool v = t < t1 && p.ok[t] != 0;
@@ -149,14 +124,7 @@ __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_rank(MllrParams p, double
   }
   const size_t SL = ((size_t)D * NT + PB * PB) * 256;
   double *out = slab + (size_t)blockIdx.x * SL + (is_g ? (size_t)job * NT : (size_t)D * NT + (size_t)(job - D) * PB) * 256;
-  const int nt = is_g ? NT : PB;
-#pragma unroll
-  for (int i = 0; i < NT; i++) {
-    if (i < nt) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) out[i * 256 + (kq + 4 * r) * 16 + r16] = acc[i][r];
-    }
-  }
+  tri_tiles_store(out, acc, (is_g ? NT : PB) - 1);
 }
 
 __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_slab_add(const double *__restrict__ slab, int n_chunks, int64_t SL,
@@ -181,19 +149,10 @@ void mllr_rank_launch(const MllrParams &p, double *slab, double *acc, hipStream_
   const int chunks = (p.n + MLLR_CHUNK - 1) / MLLR_CHUNK;
   if (chunks > MLLR_MAX_CHUNKS) raise(AASR_ERR_INVALID, "mllr: %d frames in one launch", p.n);
   const dim3 grid((unsigned)chunks, (unsigned)((p.dim + pb + MLLR_THREADS / 64 - 1) / (MLLR_THREADS / 64)));
-#define AASR_CASE(N)                                                                          \
-  case N:                                                                                     \
-    hipLaunchKernelGGL(k_mllr_rank<N>, grid, dim3(MLLR_THREADS), 0, stream, p, slab); \
-    break;
-  switch (pb) {
-    AASR_CASE(1)
-    AASR_CASE(2)
-    AASR_CASE(3)
-    AASR_CASE(4)
-    default:
-      raise(AASR_ERR_UNSUPPORTED, "mllr: no accumulation kernel for dimension %d", p.dim);
-  }
-#undef AASR_CASE
+  const bool launched = dispatch_among<1, 2, 3, 4>(pb, [&](auto n) {
+    hipLaunchKernelGGL(k_mllr_rank<n()>, grid, dim3(MLLR_THREADS), 0, stream, p, slab);
+  });
+  if (!launched) raise(AASR_ERR_UNSUPPORTED, "mllr: no accumulation kernel for dimension %d", p.dim);
   AASR_HIP(hipGetLastError());
   const int64_t SL = mllr_slab_doubles(p.dim);
   hipLaunchKernelGGL(k_mllr_slab_add, dim3((unsigned)((SL + MLLR_THREADS - 1) / MLLR_THREADS)), dim3(MLLR_THREADS), 0,

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "mllr.h"
+#include "mllr_pass1.h"
 
 namespace aasr {
 
@@ -27,7 +28,7 @@ size_t mllr_entry_weights_lds_bytes(int dim, int max_comps) {
 __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_entry_pass1(MllrEntryParams q) {
   extern __shared__ double lds[];
   const MllrParams &p = q.p;
-  const int D = p.dim, XS = D | 1, MC = p.max_comps, REC = p.rec, DP = p.dimp, B = MLLR_P1_FRAMES;
+  const int D = p.dim, XS = D | 1, MC = p.max_comps, B = MLLR_P1_FRAMES;
   double *xs = lds;
   double *lg = xs + B * XS;
   double *lbeta = lg + B * MC;
@@ -71,29 +72,8 @@ __global__ __launch_bounds__(MLLR_THREADS) void k_mllr_entry_pass1(MllrEntryPara
           M = p.state_off[pdf + 1] - r0;
         }
       }
-      const double *x = xs + t * XS;
-      double sum = 0;
-      for (int k = 0; k < M; k++) {
-        const double *rec = p.recs + (size_t)(r0 + k) * REC;
-        double ll = 0;
-        for (int d = 0; d < D; d++) {
-          const double df = x[d] - rec[d];
-          ll += df * df * rec[DP + d];
-        }
-        ll *= -0.5;
-        ll += rec[2 * DP];
-        const double lik = exp(ll);
-        lg[t * MC + k] = lik;
-        sum += lik;
-      }
-      // prior * lik / sum with the entry's probability as the prior (MllrTrainer.cc:40-49); what is not > 0 adds
-      // nothing (MllrTrainer.cc:153), so an entry whose sum is 0 or not finite adds nothing at all
-      for (int k = 0; k < M; k++) {
-        double pr = pw * lg[t * MC + k] / sum;
-        if (!(pr > 0)) pr = 0;
-        lg[t * MC + k] = pr;
-        beta += pr;
-      }
+      // the entry's probability as the prior
+      beta = mllr_posteriors(p, xs + t * XS, r0, M, pw, lg + t * MC, beta);
       lr0[t] = r0;
       lm[t] = M;
     }

@@ -17,10 +17,9 @@
 
 #include "common.h"
 #include "moments.h"
+#include "tri_scatter.h"
 
 namespace aasr {
-
-typedef double moments_f64x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(MOMENTS_DIAG_THREADS) void k_moments_diag(const double *__restrict__ x,
                                                                       const MomentsItem *__restrict__ items, int item0, int D,
@@ -59,20 +58,17 @@ __global__ __launch_bounds__(MOMENTS_DIAG_THREADS) void k_moments_diag(const dou
   if (tid == 0 && blockIdx.y == 0) out[0] = (double)it.len;
 }
 
-// f64 16x16x4: lane l holds A[row l % 16][k l / 16] and B[k l / 16][col l % 16]; result register r of lane l is
-// D[row l / 16 + 4 r][col l % 16] (mllr_accum.hip).
 template <int PB>
 __global__ __launch_bounds__(64 * PB) void k_moments_full(const double *__restrict__ x, const MomentsItem *__restrict__ items,
                                                           int item0, int D, double *__restrict__ slab) {
-  constexpr int NT = PB * (PB + 1) / 2;
   const MomentsItem it = items[item0 + blockIdx.x];
   const int tid = threadIdx.x;
   const int lane = tid & 63, R = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, kq = lane >> 4;
   const double *base = x + (size_t)it.first * D;
-  moments_f64x4 acc[PB];
+  tile_f64x4 acc[PB];
 #pragma unroll
-  for (int i = 0; i < PB; i++) acc[i] = moments_f64x4{0, 0, 0, 0};
+  for (int i = 0; i < PB; i++) acc[i] = tile_f64x4{0, 0, 0, 0};
   for (int t = 0; t < it.len; t += 4) {
     const int row = t + kq;
     const bool live = row < it.len;
@@ -96,14 +92,7 @@ __global__ __launch_bounds__(64 * PB) void k_moments_full(const double *__restri
     for (int C = 0; C < PB; C++)
       if (C <= R) acc[C] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[C], acc[C], 0, 0, 0);
   }
-  double *out = slab + ((size_t)blockIdx.x * NT + (size_t)R * (R + 1) / 2) * 256;
-#pragma unroll
-  for (int C = 0; C < PB; C++) {
-    if (C <= R) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) out[C * 256 + (kq + 4 * r) * 16 + r16] = acc[C][r];
-    }
-  }
+  tri_tiles_store(slab + ((size_t)blockIdx.x * (PB * (PB + 1) / 2) + (size_t)R * (R + 1) / 2) * 256, acc, R);
 }
 
 // a thread per value of a segment's sums; block row g: the items of one segment in this launch
@@ -124,23 +113,10 @@ void moments_launch(const double *x, int dim, bool full, const MomentsItem *item
     hipLaunchKernelGGL(k_moments_diag, dim3((unsigned)n_items, (unsigned)((dim + MOMENTS_DIAG_THREADS - 1) / MOMENTS_DIAG_THREADS)),
                        dim3(MOMENTS_DIAG_THREADS), 0, stream, x, items, item0, dim, slab);
   } else {
-#define AASR_CASE(N)                                                                                                  \
-  case N:                                                                                                             \
-    hipLaunchKernelGGL(k_moments_full<N>, dim3((unsigned)n_items), dim3(64 * N), 0, stream, x, items, item0, dim, slab); \
-    break;
-    switch (scatter_pb(dim)) {
-      AASR_CASE(1)
-      AASR_CASE(2)
-      AASR_CASE(3)
-      AASR_CASE(4)
-      AASR_CASE(5)
-      AASR_CASE(6)
-      AASR_CASE(7)
-      AASR_CASE(8)
-      default:
-        raise(AASR_ERR_UNSUPPORTED, "moments: no full-mode kernel for dimension %d", dim);
-    }
-#undef AASR_CASE
+    const bool launched = dispatch_pb(scatter_pb(dim), [&](auto n) {
+      hipLaunchKernelGGL(k_moments_full<n()>, dim3((unsigned)n_items), dim3(64 * n()), 0, stream, x, items, item0, dim, slab);
+    });
+    if (!launched) raise(AASR_ERR_UNSUPPORTED, "moments: no full-mode kernel for dimension %d", dim);
   }
   AASR_HIP(hipGetLastError());
   const int64_t TS = moments_doubles(dim, full);

@@ -178,6 +178,42 @@ static void stats_full_pass(aasr_stats *h, const double *d_frames, const std::ve
                       h->facc.p, st);
 }
 
+// The item and pdf passes of a call once stats_build_items has filled h_items, h_pdfs and h_item_begin (the caller has
+// waited for the previous call's staging before): their uploads, the launch shape and its record, the item kernel over
+// the device row list d_rows -- every entry with gamma 1, or with d_weights, where an entry may name a row outside
+// 0 .. n_frames (stats.h) -- and the pdf reduce.
+static void stats_items_step(aasr_stats *h, const double *d_frames, int64_t n_frames, int64_t slab_total, const int32_t *d_rows,
+                             const double *d_weights, double *d_frame_ll, hipStream_t st) {
+  StatsParams p{};
+  p.max_comps = h->max_comps;
+  p.rec = h->rec;
+  stats_launch_shape(p.max_comps, p.rec, &p.block, &p.lds_recs);
+  h->d_items.ensure(h->h_items.size());
+  h->d_pdfs.ensure(h->h_pdfs.size());
+  h->d_item_begin.ensure(h->h_item_begin.size());
+  h->slab.ensure((size_t)slab_total);
+  AASR_HIP(hipMemcpyAsync(h->d_items.p, h->h_items.data(), h->h_items.size() * sizeof(StatsItem), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipMemcpyAsync(h->d_pdfs.p, h->h_pdfs.data(), h->h_pdfs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipMemcpyAsync(h->d_item_begin.p, h->h_item_begin.data(), h->h_item_begin.size() * sizeof(int32_t),
+                          hipMemcpyHostToDevice, st));
+  AASR_HIP(hipEventRecord(h->staged, st));
+  h->staged_pending = true;
+  p.x = d_frames;
+  p.dim = h->D;
+  p.rows = d_rows;
+  p.items = h->d_items.p;
+  p.recs = h->gmm->f64_recs.p;
+  p.state_off = h->gmm->f64_state_off.p;
+  p.slab = h->slab.p;
+  p.frame_ll = d_frame_ll;
+  const int32_t shape[5] = {h->dimp, p.block, p.lds_recs, p.max_comps, (int32_t)h->h_items.size()};
+  std::copy(shape, shape + 5, h->last_shape);
+  if (d_weights) stats_items_w_launch(p, d_weights, n_frames, h->dimp, (int)h->h_items.size(), st);
+  else stats_items_launch(p, h->dimp, (int)h->h_items.size(), st);
+  stats_pdf_reduce_launch(h->d_pdfs.p, h->d_item_begin.p, (int)h->h_pdfs.size(), h->d_items.p, h->slab.p,
+                          h->gmm->f64_state_off.p, h->D, h->racc.p, h->pacc.p, st);
+}
+
 void require_fetched(const aasr_stats *h, const char *what) {
   if (!h) raise(AASR_ERR_INVALID, "%s: null argument", what);
   if (!h->fetched) raise(AASR_ERR_INVALID, "%s: call aasr_stats_fetch after the last accumulation", what);
@@ -295,36 +331,9 @@ aasr_status aasr_stats_accumulate_dev(aasr_stats *h, const double *d_frames, int
     if (h->h_items.empty()) return;
     std::vector<FullLaunch> full_launches;
     if (h->full) full_launches = stats_full_prepare(h, cnt);
-    StatsParams p{};
-    p.max_comps = h->max_comps;
-    p.rec = h->rec;
-    stats_launch_shape(p.max_comps, p.rec, &p.block, &p.lds_recs);
     h->d_rows.ensure(h->h_rows.size());
-    h->d_items.ensure(h->h_items.size());
-    h->d_pdfs.ensure(h->h_pdfs.size());
-    h->d_item_begin.ensure(h->h_item_begin.size());
-    h->slab.ensure((size_t)slab_total);
     AASR_HIP(hipMemcpyAsync(h->d_rows.p, h->h_rows.data(), h->h_rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    AASR_HIP(hipMemcpyAsync(h->d_items.p, h->h_items.data(), h->h_items.size() * sizeof(StatsItem),
-                            hipMemcpyHostToDevice, st));
-    AASR_HIP(hipMemcpyAsync(h->d_pdfs.p, h->h_pdfs.data(), h->h_pdfs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    AASR_HIP(hipMemcpyAsync(h->d_item_begin.p, h->h_item_begin.data(), h->h_item_begin.size() * sizeof(int32_t),
-                            hipMemcpyHostToDevice, st));
-    AASR_HIP(hipEventRecord(h->staged, st));
-    h->staged_pending = true;
-    p.x = d_frames;
-    p.dim = h->D;
-    p.rows = h->d_rows.p;
-    p.items = h->d_items.p;
-    p.recs = h->gmm->f64_recs.p;
-    p.state_off = h->gmm->f64_state_off.p;
-    p.slab = h->slab.p;
-    p.frame_ll = d_frame_ll;
-    const int32_t shape[5] = {h->dimp, p.block, p.lds_recs, p.max_comps, (int32_t)h->h_items.size()};
-    std::copy(shape, shape + 5, h->last_shape);
-    stats_items_launch(p, h->dimp, (int)h->h_items.size(), st);
-    stats_pdf_reduce_launch(h->d_pdfs.p, h->d_item_begin.p, (int)h->h_pdfs.size(), h->d_items.p, h->slab.p,
-                            h->gmm->f64_state_off.p, h->D, h->racc.p, h->pacc.p, st);
+    stats_items_step(h, d_frames, n_frames, slab_total, h->d_rows.p, nullptr, d_frame_ll, st);
     if (h->full) stats_full_pass(h, d_frames, full_launches, st);
     h->fetched = false;
   });
@@ -351,33 +360,7 @@ aasr_status aasr_stats_accumulate_weighted_dev(aasr_stats *h, const double *d_fr
     h->staged_pending = false;
     const int64_t slab_total = stats_build_items(h, std::vector<int64_t>(cnt, cnt + h->S + 1));
     if (h->h_items.empty()) return;
-    StatsParams p{};
-    p.max_comps = h->max_comps;
-    p.rec = h->rec;
-    stats_launch_shape(p.max_comps, p.rec, &p.block, &p.lds_recs);
-    h->d_items.ensure(h->h_items.size());
-    h->d_pdfs.ensure(h->h_pdfs.size());
-    h->d_item_begin.ensure(h->h_item_begin.size());
-    h->slab.ensure((size_t)slab_total);
-    AASR_HIP(hipMemcpyAsync(h->d_items.p, h->h_items.data(), h->h_items.size() * sizeof(StatsItem), hipMemcpyHostToDevice, st));
-    AASR_HIP(hipMemcpyAsync(h->d_pdfs.p, h->h_pdfs.data(), h->h_pdfs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    AASR_HIP(hipMemcpyAsync(h->d_item_begin.p, h->h_item_begin.data(), h->h_item_begin.size() * sizeof(int32_t),
-                            hipMemcpyHostToDevice, st));
-    AASR_HIP(hipEventRecord(h->staged, st));
-    h->staged_pending = true;
-    p.x = d_frames;
-    p.dim = h->D;
-    p.rows = d_rows;
-    p.items = h->d_items.p;
-    p.recs = h->gmm->f64_recs.p;
-    p.state_off = h->gmm->f64_state_off.p;
-    p.slab = h->slab.p;
-    p.frame_ll = nullptr;
-    const int32_t shape[5] = {h->dimp, p.block, p.lds_recs, p.max_comps, (int32_t)h->h_items.size()};
-    std::copy(shape, shape + 5, h->last_shape);
-    stats_items_w_launch(p, d_weights, n_frames, h->dimp, (int)h->h_items.size(), st);
-    stats_pdf_reduce_launch(h->d_pdfs.p, h->d_item_begin.p, (int)h->h_pdfs.size(), h->d_items.p, h->slab.p,
-                            h->gmm->f64_state_off.p, h->D, h->racc.p, h->pacc.p, st);
+    stats_items_step(h, d_frames, n_frames, slab_total, d_rows, d_weights, nullptr, st);
     h->fetched = false;
   });
 }
