@@ -233,6 +233,7 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_scatter_destroy.argtypes = [vp]
     L.aasr_scatter_destroy.restype = None
     L.aasr_scatter_accumulate_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.aasr_scatter_accumulate_weighted_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.aasr_scatter_fetch.argtypes = [vp, vp]
     L.aasr_scatter_get.argtypes = [vp, vp, vp, vp]
     L.aasr_debug_scatter_shape.argtypes = [vp, vp]
@@ -243,6 +244,10 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_lda_default_options.argtypes = [vp]
     L.aasr_lda_default_options.restype = None
     L.aasr_run_lda_recipe.argtypes = [cp, vp, cp, vp, vp]
+    L.aasr_lda_network_default_options.argtypes = [vp]
+    L.aasr_lda_network_default_options.restype = None
+    L.aasr_lda_networks_check.argtypes = [cp, vp, cp, vp]
+    L.aasr_run_lda_networks_recipe.argtypes = [cp, vp, vp, cp, vp, vp, vp]
     # Gaussian-pool clustering
     L.aasr_gcluster_assign.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
     L.aasr_gcluster_centres.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -2018,6 +2023,17 @@ class Scatter:
         check(lib().aasr_scatter_accumulate_dev(self._h, _ptr(d_frames), len(c), _ptr(c), _ptr(d_weight),
                                                 _stream_handle(stream)))
 
+    def accumulate_weighted_dev(self, d_frames, cnt, d_rows, d_weights, stream=None) -> None:
+        """Weighted entries, class run after class run: cnt host int64 [C + 1] (cnt[c]: the first entry of class c);
+        d_rows: an int32 device tensor of frame rows, d_weights: a float64 device tensor, cnt[C] elements each (None
+        passes a null array).  A frame may stand under several classes; an entry of weight 0 does not read its row."""
+        c = np.ascontiguousarray(cnt, np.int64)
+        if len(c) != self.C + 1:
+            raise ValueError("cnt must hold n_classes + 1 values")
+        n = int(d_frames.shape[0]) if d_frames is not None else 0
+        check(lib().aasr_scatter_accumulate_weighted_dev(self._h, _ptr(d_frames), n, _ptr(c), _ptr(d_rows), _ptr(d_weights),
+                                                         _stream_handle(stream)))
+
     def set_slab_bytes(self, nbytes: int) -> None:
         """Diagnostic: the bound on a launch's slab memory."""
         check(lib().aasr_debug_scatter_set_slab_bytes(self._h, nbytes))
@@ -2086,6 +2102,38 @@ def run_lda_recipe(cfg_text: str, topo: Topology, recipe_path: str, module: str,
     opts.state_gamma = sg.ctypes.data
     st = RunStats()
     check(lib().aasr_run_lda_recipe(cfg_text.encode(), topo.handle, recipe_path.encode(), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total,
+            "seconds_scatter": opts.seconds_scatter, "seconds_features": opts.seconds_features, "state_gamma": sg}
+
+
+class LdaNetworkOptions(C.Structure):
+    """aasr_lda_network_options: what lda --networks adds (--segmode vit, -F, -W, -A)."""
+    _fields_ = [("networks", C.c_int32), ("viterbi", C.c_int32), ("fw_beam", C.c_double), ("bw_beam", C.c_double),
+                ("ac_scale_given", C.c_int32), ("ac_scale", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "LdaNetworkOptions":
+        o = cls()
+        lib().aasr_lda_network_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_lda_networks_recipe(cfg_text: str, gmm: "Gmm", topo: Topology, recipe_path: str, module: str, target_dim: int,
+                            out: Optional[str] = None, speakers: Optional[str] = None, opts: Optional[LdaOptions] = None,
+                            networks: Optional[LdaNetworkOptions] = None) -> dict:
+    """lda over the recipe's hmmnet= networks (lda --networks); `networks` None: Baum-Welch with the default beams.
+    -> as run_lda_recipe; "state_gamma" holds every state's summed posterior."""
+    opts = opts or LdaOptions.defaults()
+    networks = networks or LdaNetworkOptions.defaults(networks=1)
+    mb, ob, sb = module.encode(), (out.encode() if out else None), (speakers.encode() if speakers else None)
+    opts.module, opts.out, opts.speakers, opts.target_dim = mb, ob, sb, target_dim
+    sg = np.zeros(topo.num_states())
+    opts.state_gamma = sg.ctypes.data
+    st = RunStats()
+    check(lib().aasr_run_lda_networks_recipe(cfg_text.encode(), gmm._h if gmm is not None else None, topo.handle,
+                                             recipe_path.encode(), C.byref(opts), C.byref(networks), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total,
             "seconds_scatter": opts.seconds_scatter, "seconds_features": opts.seconds_features, "state_gamma": sg}
 

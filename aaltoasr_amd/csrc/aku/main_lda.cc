@@ -5,10 +5,18 @@
 //
 //   lda -p PH -c CFG -r RECIPE -M MODULE [-d DIM] [-w OUT.cfg] [-O] [-S SPKC] [-m MB] [--mingamma G] [--maxgamma G]
 //       [--no-silence] [-i level]
+//       [--networks (-b BASE | -g GK --mc MC -p PH) [-F fw] [-W bw] [-A scale] [--segmode bw|vit]]
 //
-// Refused before anything is read: -H, --mpv, --vit (HMM networks).  Refused before the device is opened: recipe
-// start-line / end-line, speaker files with model transforms, -d other than the module's dimension, a model
-// without the _ or __ HMM.
+// --networks is the reference's -H under a spelling of its own: the states' sums from the Baum-Welch posteriors (or with
+// --segmode vit the best paths) of the recipe's hmmnet= networks, scored with the model -b (or -g, --mc and -p; -m is
+// this tool's --maxmem) names on the output of the whole feature chain (aasr_run_lda_networks_recipe), one pass, the
+// selection made on the summed gamma.  -F, -W and -A are honoured with it; --segmode mpv and -O are refused with it, a
+// recipe line without hmmnet= is the reference's error, and the module must have a matrix already.  The reference's
+// own -H cannot run (it has no Gaussians to score with), so there is no binary to compare with.
+//
+// Refused before anything is read: -H, --mpv, --vit (HMM networks; use --networks), --segmode without --networks.
+// Refused before the device is opened: recipe start-line / end-line, speaker files with model transforms, -d other
+// than the module's dimension, a model without the _ or __ HMM, and with --networks non-diagonal pools.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +30,9 @@ int main(int argc, char *argv[]) {
   aku::conf::Config config;
   config("usage: lda [OPTION...]\n")
     ('h', "help", "", "", "display help")
+    ('b', "base=BASENAME", "arg", "", "base filename for model files (with --networks)")
+    ('g', "gk=FILE", "arg", "", "Mixture base distributions (with --networks)")
+    ('\0', "mc=FILE", "arg", "", "Mixture coefficients for the states (with --networks)")
     ('p', "ph=FILE", "arg", "", "HMM definitions")
     ('c', "config=FILE", "arg must", "", "feature configuration")
     ('w', "write-config=FILE", "arg", "", "write feature configuration")
@@ -41,7 +52,9 @@ int main(int argc, char *argv[]) {
     ('\0', "maxgamma=FLOAT", "arg", "1000000", "gamma values will be ceiled to maxgamma (default 1 000 000)")
     ('\0', "no-silence", "", "", "don't use silence states in estimation")
     ('i', "info=INT", "arg", "0", "info level")
-    ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)");
+    ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)")
+    ('\0', "networks", "", "", "segment with the recipe's hmmnet= networks; the reference's -H")
+    ('\0', "segmode=MODE", "arg", "bw", "Segmentation mode with --networks: bw(default)/vit");
   config.default_parse(argc, argv);
 
   // what this build does not do, refused before anything is read
@@ -51,9 +64,25 @@ int main(int argc, char *argv[]) {
   for (const auto &r : refused)
     if (config[r[0]].specified) die(std::string("lda: ") + r[1] + " is not supported; only .phn segmentations are");
 
-  if (!config["ph"].specified) die("Must give --ph");
+  const bool networks = config["networks"].specified;
+  const std::string segmode = config["segmode"].get_str();
+  if (!networks && config["segmode"].specified)
+    die("lda: --segmode is not supported without --networks; only .phn segmentations are");
+  std::string gk, mc, ph;
+  if (networks) {
+    if (segmode == "mpv")
+      die("lda: --segmode mpv (multipath Viterbi) is not supported with --networks; use --segmode bw or --segmode vit");
+    if (segmode != "bw" && segmode != "vit") die("Invalid segmentation mode " + segmode);
+    if (config["ophn"].specified) die("lda: -O (output phns) is not supported with --networks");
+    resolve_model_files(config, &gk, &mc, &ph);
+    check_pool(gk, "lda");
+    check_recipe_hmmnets(config["recipe"].get_str(), 1, 1, true);
+  } else {
+    if (!config["ph"].specified) die("Must give --ph");
+    ph = config["ph"].get_str();
+  }
   aasr_topo *topo = nullptr;
-  if (aasr_topo_create_from_ph(config["ph"].get_str().c_str(), &topo) != AASR_OK) die(aasr_last_error());
+  if (aasr_topo_create_from_ph(ph.c_str(), &topo) != AASR_OK) die(aasr_last_error());
   if (config["speakers"].specified) check_speakers(config["speakers"].get_str(), "lda");
 
   const std::string cfg = config["config"].get_str();
@@ -81,6 +110,26 @@ int main(int argc, char *argv[]) {
   opt.out = config["write-config"].specified ? out.c_str() : nullptr;
   aasr_run_stats st;
   memset(&st, 0, sizeof st);
+  if (networks) {
+    // the remaining host-side refusals, before the model takes the device
+    if (aasr_lda_networks_check(ss.str().c_str(), topo, config["recipe"].get_str().c_str(), &opt) != AASR_OK)
+      die(aasr_last_error());
+    aasr_gmm *gmm = nullptr;
+    if (aasr_gmm_create_from_files(gk.c_str(), mc.c_str(), ph.c_str(), &gmm) != AASR_OK) die(aasr_last_error());
+    aasr_lda_network_options nopt;
+    aasr_lda_network_default_options(&nopt);
+    nopt.networks = 1;
+    nopt.viterbi = segmode == "vit";
+    nopt.fw_beam = config["fw-beam"].get_float();
+    nopt.bw_beam = config["bw-beam"].get_float();
+    nopt.ac_scale_given = config["ac-scale"].specified;
+    nopt.ac_scale = config["ac-scale"].get_float();
+    if (aasr_run_lda_networks_recipe(ss.str().c_str(), gmm, topo, config["recipe"].get_str().c_str(), &opt, &nopt, &st) != AASR_OK)
+      die(aasr_last_error());
+    aasr_gmm_destroy(gmm);
+    aasr_topo_destroy(topo);
+    return 0;
+  }
   // the remaining host-side refusals (-d against the module, the silence HMMs, recipe line limits) come first in there
   if (aasr_run_lda_recipe(ss.str().c_str(), topo, config["recipe"].get_str().c_str(), &opt, &st) != AASR_OK)
     die(aasr_last_error());

@@ -1,7 +1,8 @@
 // lda.cc -- LDA estimation (aku/lda.cc): the class-scatter handle that drives the device accumulation
 // (scatter_accum.hip), the host solver of lda.cc:380-446 in double without LAPACK (Cholesky reduction, cyclic
 // Jacobi), the state selection (lda.cc:113-115, 247-263) and the lda main loop over a recipe (aasr_run_lda_recipe,
-// lda.cc:143-372, 448-462).
+// lda.cc:143-372, 448-462), over .phn segmentations or (aasr_run_lda_networks_recipe) with the posteriors of the
+// recipe's HMM networks as weighted entries (network_pass.h, scatter_entries.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <numeric>
 #include <string>
@@ -16,7 +18,10 @@
 
 #include "common.h"
 #include "feat.h"
+#include "gmm.h"
+#include "hmmnet.h"
 #include "jacobi.h"
+#include "network_pass.h"
 #include "recipe_pass.h"
 #include "scatter.h"
 
@@ -45,6 +50,55 @@ struct aasr_scatter {
     if (staged) (void)hipEventDestroy(staged);
   }
 };
+
+// The launches of h->h_items, at most max_items items each (scatter.h); within a launch the items of a class are one
+// group.  Uploads the items and the groups and queues the launches: by_entry, rows / weight are an entry list and its
+// weights (k_scatter_entries), otherwise the compressed row list and the frames' weights or null (k_scatter_items).
+static void scatter_queue_items(aasr_scatter *h, const double *d_frames, const int32_t *d_rows, const double *d_weight,
+                                bool by_entry, hipStream_t st) {
+  const int64_t NI = (int64_t)h->h_items.size();
+  const int64_t max_items =
+      std::max<int64_t>(1, std::min<int64_t>(SCATTER_MAX_ITEMS, h->slab_bytes / (h->TS * (int64_t)sizeof(double))));
+  struct Launch {
+    int item0, n_items, group0, n_groups;
+  };
+  std::vector<Launch> launches;
+  h->h_groups.clear();
+  for (int64_t i0 = 0; i0 < NI; i0 += max_items) {
+    const int n = (int)std::min(max_items, NI - i0);
+    Launch L{(int)i0, n, (int)h->h_groups.size(), 0};
+    for (int i = 0; i < n; i++) {
+      const int32_t c = h->h_items[(size_t)(i0 + i)].cls;
+      if (L.n_groups > 0 && h->h_groups.back().cls == c) h->h_groups.back().count++;
+      else {
+        h->h_groups.push_back(ScatterGroup{c, i, 1, 0});
+        L.n_groups++;
+      }
+    }
+    launches.push_back(L);
+  }
+  h->d_items.ensure(h->h_items.size());
+  h->d_groups.ensure(h->h_groups.size());
+  h->slab.ensure((size_t)std::min(NI, max_items) * h->TS);
+  AASR_HIP(hipMemcpyAsync(h->d_items.p, h->h_items.data(), h->h_items.size() * sizeof(ScatterItem), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipMemcpyAsync(h->d_groups.p, h->h_groups.data(), h->h_groups.size() * sizeof(ScatterGroup), hipMemcpyHostToDevice, st));
+  AASR_HIP(hipEventRecord(h->staged, st));
+  h->staged_pending = true;
+  ScatterParams p{};
+  p.x = d_frames;
+  p.weight = d_weight;
+  p.rows = d_rows;
+  p.items = h->d_items.p;
+  p.dim = h->D;
+  for (const Launch &L : launches) {  // (the launches of a call follow each other on the stream and share the slab)
+    if (by_entry) scatter_entries_launch(p, L.item0, L.n_items, h->d_groups.p + L.group0, L.n_groups, h->slab.p, h->acc.p, st);
+    else scatter_launch(p, L.item0, L.n_items, h->d_groups.p + L.group0, L.n_groups, h->slab.p, h->acc.p, st);
+  }
+  h->shape[0] = h->PB;
+  h->shape[1] = (int32_t)NI;
+  h->shape[2] = (int32_t)launches.size();
+  h->fetched = false;
+}
 
 extern "C" {
 
@@ -101,49 +155,34 @@ aasr_status aasr_scatter_accumulate_dev(aasr_scatter *h, const double *d_frames,
       for (int64_t f = 0; f < n_frames; f++)
         if (cls[f] >= 0) h->h_rows[(size_t)at[(size_t)cls[f]]++] = (int32_t)f;
     }
-    // launches of at most max_items items (scatter.h); within a launch the items of a class are one group
-    const int64_t NI = (int64_t)h->h_items.size();
-    const int64_t max_items =
-        std::max<int64_t>(1, std::min<int64_t>(SCATTER_MAX_ITEMS, h->slab_bytes / (h->TS * (int64_t)sizeof(double))));
-    struct Launch {
-      int item0, n_items, group0, n_groups;
-    };
-    std::vector<Launch> launches;
-    h->h_groups.clear();
-    for (int64_t i0 = 0; i0 < NI; i0 += max_items) {
-      const int n = (int)std::min(max_items, NI - i0);
-      Launch L{(int)i0, n, (int)h->h_groups.size(), 0};
-      for (int i = 0; i < n; i++) {
-        const int32_t c = h->h_items[(size_t)(i0 + i)].cls;
-        if (L.n_groups > 0 && h->h_groups.back().cls == c) h->h_groups.back().count++;
-        else {
-          h->h_groups.push_back(ScatterGroup{c, i, 1, 0});
-          L.n_groups++;
-        }
-      }
-      launches.push_back(L);
-    }
     h->d_rows.ensure(h->h_rows.size());
-    h->d_items.ensure(h->h_items.size());
-    h->d_groups.ensure(h->h_groups.size());
-    h->slab.ensure((size_t)std::min(NI, max_items) * h->TS);
     AASR_HIP(hipMemcpyAsync(h->d_rows.p, h->h_rows.data(), h->h_rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    AASR_HIP(hipMemcpyAsync(h->d_items.p, h->h_items.data(), h->h_items.size() * sizeof(ScatterItem), hipMemcpyHostToDevice, st));
-    AASR_HIP(hipMemcpyAsync(h->d_groups.p, h->h_groups.data(), h->h_groups.size() * sizeof(ScatterGroup), hipMemcpyHostToDevice, st));
-    AASR_HIP(hipEventRecord(h->staged, st));
-    h->staged_pending = true;
-    ScatterParams p{};
-    p.x = d_frames;
-    p.weight = d_weight;
-    p.rows = h->d_rows.p;
-    p.items = h->d_items.p;
-    p.dim = h->D;
-    for (const Launch &L : launches)  // (the launches of a call follow each other on the stream and share the slab)
-      scatter_launch(p, L.item0, L.n_items, h->d_groups.p + L.group0, L.n_groups, h->slab.p, h->acc.p, st);
-    h->shape[0] = h->PB;
-    h->shape[1] = (int32_t)NI;
-    h->shape[2] = (int32_t)launches.size();
-    h->fetched = false;
+    scatter_queue_items(h, d_frames, h->d_rows.p, d_weight, false, st);
+  });
+}
+
+aasr_status aasr_scatter_accumulate_weighted_dev(aasr_scatter *h, const double *d_frames, int64_t n_frames, const int64_t *cnt,
+                                                 const int32_t *d_rows, const double *d_weights, void *stream) {
+  return guarded([&] {
+    if (!h || n_frames < 0 || !cnt) raise(AASR_ERR_INVALID, "aasr_scatter_accumulate_weighted_dev: bad argument");
+    if (n_frames > INT32_MAX) raise(AASR_ERR_INVALID, "aasr_scatter_accumulate_weighted_dev: more than 2^31 frames in one call");
+    if (cnt[0] != 0) raise(AASR_ERR_INVALID, "aasr_scatter_accumulate_weighted_dev: cnt[0] is %lld, not 0", (long long)cnt[0]);
+    for (int c = 0; c < h->C; c++)
+      if (cnt[c + 1] < cnt[c]) raise(AASR_ERR_INVALID, "aasr_scatter_accumulate_weighted_dev: cnt decreases at class %d", c);
+    const int64_t entries = cnt[h->C];
+    if (entries > INT32_MAX) raise(AASR_ERR_INVALID, "aasr_scatter_accumulate_weighted_dev: more than 2^31 entries in one call");
+    if (entries == 0) return;
+    if (!d_frames || !d_rows || !d_weights || n_frames == 0)
+      raise(AASR_ERR_INVALID, "aasr_scatter_accumulate_weighted_dev: %lld entries without frames, rows or weights", (long long)entries);
+    const hipStream_t st = (hipStream_t)stream;
+    if (h->staged_pending) AASR_HIP(hipEventSynchronize(h->staged));
+    h->staged_pending = false;
+    // every class's run of the entry list cut into items; the list itself stays where it is
+    h->h_items.clear();
+    for (int c = 0; c < h->C; c++)
+      for (int64_t s = cnt[c]; s < cnt[c + 1]; s += SCATTER_ITEM)
+        h->h_items.push_back(ScatterItem{(int32_t)s, (int32_t)std::min<int64_t>(SCATTER_ITEM, cnt[c + 1] - s), c, 0});
+    scatter_queue_items(h, d_frames, d_rows, d_weights, true, st);
   });
 }
 
@@ -397,8 +436,9 @@ static void lda_select(int n_states, const double *count, double mingamma, int m
   }
 }
 
-// the lin_transform module `name` of a configuration text, host only: its configured dim (0: none given)
-static int configured_transform_dim(const std::string &text, const std::string &name) {
+// the lin_transform module `name` of a configuration text, host only: its configured dim (0: none given); *matrix_len:
+// the length of its configured matrix (0: none given)
+static int configured_transform_dim(const std::string &text, const std::string &name, size_t *matrix_len = nullptr) {
   size_t pos = 0;
   while (pos < text.size()) {
     size_t e = text.find('\n', pos);
@@ -416,9 +456,60 @@ static int configured_transform_dim(const std::string &text, const std::string &
     if (type != "lin_transform") raise(AASR_ERR_INVALID, "Module %s is not a transform module", name.c_str());
     int dim = 0;
     cfg.get("dim", dim);
+    if (matrix_len) {
+      std::vector<float> m;
+      cfg.get("matrix", m);
+      *matrix_len = m.size();
+    }
     return dim;
   }
   raise(AASR_ERR_INVALID, "unknown module requested: %s", name.c_str());
+}
+
+// the states of the silence HMMs _ and __ (lda.cc:84-90); model.hmm() throws for an unknown label
+static std::vector<int32_t> silence_states(const aasr_topo *topo) {
+  std::vector<int32_t> silence;
+  for (const char *label : {"_", "__"}) {
+    const int32_t hi = aasr_topo_hmm_index(topo, label);
+    if (hi < 0) raise(AASR_ERR_INVALID, "lda: no HMM %s in the model", label);
+    std::vector<int32_t> st((size_t)aasr_topo_hmm_num_states(topo, hi));
+    if (aasr_topo_hmm_states(topo, hi, st.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+    silence.insert(silence.end(), st.begin(), st.end());
+  }
+  return silence;
+}
+
+// The LDA of the handle's sums (lda.cc:375-462): fetch, the matrix from the selected classes, the module's new
+// transformation, the configuration file.  gamma: the fetched class weights, for a caller that selected by them
+static void solve_and_write(aasr_feat *feat, FeatModule *ltm, aasr_scatter *h, hipStream_t stream, int S, int D, int td,
+                            const aasr_lda_options *opt, std::vector<int32_t> &selected,
+                            const std::function<void(const std::vector<double> &)> &select) {
+  const size_t tri = (size_t)D * (D + 1) / 2;
+  std::vector<double> gamma((size_t)S), sx((size_t)S * D), sxx((size_t)S * tri), lda((size_t)td * D);
+  if (aasr_scatter_fetch(h, stream) != AASR_OK || aasr_scatter_get(h, gamma.data(), sx.data(), sxx.data()) != AASR_OK)
+    raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+  if (opt->state_gamma) std::copy(gamma.begin(), gamma.end(), opt->state_gamma);
+  if (select) select(gamma);
+  if (opt->info > 0) {
+    printf("Compute the LDA\n");
+    fflush(stdout);
+  }
+  // a selected state whose frames all lay past the feature end has no accumulator worth the name: it adds
+  // nothing to B and W in the reference (gamma 0); leave it out
+  for (int s = 0; s < S; s++)
+    if (selected[(size_t)s] && !(gamma[(size_t)s] > 0)) selected[(size_t)s] = 0;
+  lda_solve(S, D, gamma.data(), sx.data(), sxx.data(), selected.data(), opt->maxgamma, td, lda.data());
+  // LinTransformModule::set_transformation_matrix (FeatureModules.cc:1273-1296): the working and the
+  // configured matrix both, in float
+  std::vector<float> tr(lda.begin(), lda.end());
+  ltm->matrix = tr;
+  ltm->orig_matrix = tr;
+  ltm->matrix_defined = true;
+  ltm->d_matrix.upload(ltm->matrix.data(), ltm->matrix.size());
+  if (opt->out) {
+    const std::string text = feat_write_configuration(feat);
+    write_text_file(opt->out, text.data(), text.size());
+  }
 }
 
 }  // namespace aasr
@@ -473,15 +564,7 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
       if (cd > 0 && cd != td)
         raise(AASR_ERR_INVALID, "lda: -d %d but module %s has dimension %d", td, module.c_str(), cd);
     }
-    // the silence states (lda.cc:84-90); model.hmm() throws for an unknown label
-    std::vector<int32_t> silence;
-    for (const char *label : {"_", "__"}) {
-      const int32_t hi = aasr_topo_hmm_index(topo, label);
-      if (hi < 0) raise(AASR_ERR_INVALID, "lda: no HMM %s in the model", label);
-      std::vector<int32_t> st((size_t)aasr_topo_hmm_num_states(topo, hi));
-      if (aasr_topo_hmm_states(topo, hi, st.data()) != AASR_OK) raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-      silence.insert(silence.end(), st.begin(), st.end());
-    }
+    const std::vector<int32_t> silence = silence_states(topo);
     const int S = aasr_topo_num_states(topo);
     const std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, 1, 1, true);  // lda.cc:144
     refuse_line_limits(infos, "lda");
@@ -586,32 +669,223 @@ extern "C" aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr
       num_frames += rows_total;
     }
 
-    // ---- the LDA (lda.cc:375-462)
-    if (opt->info > 0) {
-      printf("Compute the LDA\n");
-      fflush(stdout);
-    }
-    const size_t tri = (size_t)D * (D + 1) / 2;
-    std::vector<double> gamma((size_t)S), sx((size_t)S * D), sxx((size_t)S * tri), lda((size_t)td * D);
-    if (aasr_scatter_fetch(h, stream) != AASR_OK || aasr_scatter_get(h, gamma.data(), sx.data(), sxx.data()) != AASR_OK)
-      raise(AASR_ERR_INVALID, "%s", aasr_last_error());
-    if (opt->state_gamma) std::copy(gamma.begin(), gamma.end(), opt->state_gamma);
-    // a selected state whose frames all lay past the feature end has no accumulator worth the name: it adds
-    // nothing to B and W in the reference (gamma 0); leave it out
-    for (int s = 0; s < S; s++)
-      if (selected[(size_t)s] && !(gamma[(size_t)s] > 0)) selected[(size_t)s] = 0;
-    lda_solve(S, D, gamma.data(), sx.data(), sxx.data(), selected.data(), opt->maxgamma, td, lda.data());
-    // LinTransformModule::set_transformation_matrix (FeatureModules.cc:1273-1296): the working and the
-    // configured matrix both, in float
-    std::vector<float> tr(lda.begin(), lda.end());
-    ltm->matrix = tr;
-    ltm->orig_matrix = tr;
-    ltm->matrix_defined = true;
-    ltm->d_matrix.upload(ltm->matrix.data(), ltm->matrix.size());
-    if (opt->out) {
-      const std::string text = feat_write_configuration(feat.get());
-      write_text_file(opt->out, text.data(), text.size());
-    }
+    solve_and_write(feat.get(), ltm, h, stream, S, D, td, opt, selected, nullptr);
     fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, opt->seconds_scatter + opt->seconds_features);
   });
 }
+
+// ---- the same over the recipe's HMM networks ---------------------------------------------------
+
+namespace {
+
+// what aasr_run_lda_networks_recipe refuses on the host; -> the recipe's lines and the silence states
+void lda_networks_host_checks(const char *feat_cfg_text, const aasr_topo *topo, const char *recipe_path,
+                              const aasr_lda_options *opt, std::vector<RecipeInfo> *infos, std::vector<int32_t> *silence) {
+  if (!feat_cfg_text || !topo || !recipe_path || !opt || !opt->module)
+    raise(AASR_ERR_INVALID, "aasr_run_lda_networks_recipe: null argument");
+  if (opt->ophn)
+    raise(AASR_ERR_UNSUPPORTED, "lda: -O is not supported with --networks (a network line has no segmentation to choose)");
+  const std::string module = opt->module;
+  size_t matrix_len = 0;
+  const int cd = configured_transform_dim(feat_cfg_text, module, &matrix_len);
+  if (cd > 0 && cd != opt->target_dim)
+    raise(AASR_ERR_INVALID, "lda: -d %d but module %s has dimension %d", opt->target_dim, module.c_str(), cd);
+  if (matrix_len == 0)
+    raise(AASR_ERR_INVALID,
+          "lda: --networks scores the output of the whole feature chain, but module %s has no matrix in the configuration",
+          module.c_str());
+  *silence = silence_states(topo);
+  *infos = read_recipe_file(recipe_path, 1, 1, true);  // lda.cc:144
+  refuse_line_limits(*infos, "lda");
+  for (const RecipeInfo &u : *infos)
+    if (u.hmmnet_path.empty()) raise(AASR_ERR_INVALID, "Recipe::Info::init_hmmnet_files: hmmnet not specified in recipe.");
+}
+
+}  // namespace
+
+extern "C" {
+
+void aasr_lda_network_default_options(aasr_lda_network_options *o) {
+  if (o) memset(o, 0, sizeof *o);
+  if (o) o->ac_scale = 1;
+}
+
+aasr_status aasr_lda_networks_check(const char *feat_cfg_text, const aasr_topo *topo, const char *recipe_path,
+                                    const aasr_lda_options *opt) {
+  return guarded([&] {
+    std::vector<RecipeInfo> infos;
+    std::vector<int32_t> silence;
+    lda_networks_host_checks(feat_cfg_text, topo, recipe_path, opt, &infos, &silence);
+  });
+}
+
+aasr_status aasr_run_lda_networks_recipe(const char *feat_cfg_text, aasr_gmm *gmm, const aasr_topo *topo,
+                                         const char *recipe_path, aasr_lda_options *opt,
+                                         const aasr_lda_network_options *nopt, aasr_run_stats *stats) {
+  if (!nopt || !nopt->networks) return aasr_run_lda_recipe(feat_cfg_text, topo, recipe_path, opt, stats);
+  return guarded([&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    // ---- host only, before the device is opened
+    std::vector<RecipeInfo> infos;
+    std::vector<int32_t> silence;
+    lda_networks_host_checks(feat_cfg_text, topo, recipe_path, opt, &infos, &silence);
+    if (!gmm) raise(AASR_ERR_INVALID, "aasr_run_lda_networks_recipe: null argument");
+    opt->seconds_scatter = opt->seconds_features = 0;
+    const std::string module = opt->module;
+    const int td = opt->target_dim;
+    const int S = aasr_topo_num_states(topo);
+
+    // ---- the device
+    std::unique_ptr<aasr_feat> feat(feat_create(feat_cfg_text));
+    FeatModule *ltm = &feat->mods[(size_t)feat->by_name.at(module)];
+    if (ltm->dim != td) raise(AASR_ERR_INVALID, "lda: -d %d but module %s has dimension %d", td, module.c_str(), ltm->dim);
+    const int source = ltm->sources[0];  // lda.cc:105-109: the statistics are those of the module's source
+    const int D = feat->mods[(size_t)source].dim;
+    if (td > D) raise(AASR_ERR_INVALID, "lda: -d %d exceeds the source dimension %d", td, D);
+    if (D > SCATTER_MAX_DIM)
+      raise(AASR_ERR_UNSUPPORTED, "lda: source dimension %d (module %s): 1 ... %d are built", D,
+            feat->mods[(size_t)source].name.c_str(), SCATTER_MAX_DIM);
+    aasr_spkc *spk = nullptr;
+    if (opt->speakers) {
+      if (aasr_spkc_create(feat.get(), nullptr, &spk) != AASR_OK || aasr_spkc_read_file(spk, opt->speakers) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+    }
+    std::unique_ptr<aasr_spkc, void (*)(aasr_spkc *)> spguard(spk, aasr_spkc_destroy);
+    check_feature_dim(gmm, feat.get());
+    if (aasr_gmm_num_states(gmm) != S)
+      raise(AASR_ERR_INVALID, "lda: the model has %d states but the HMM definitions have %d", aasr_gmm_num_states(gmm), S);
+    const float fr = aasr_feat_frame_rate(feat.get());
+    const bool f64 = aasr_gmm_get_precision(gmm) == AASR_PREC_F64;
+
+    {
+      const int maxpos = (int)std::min<double>(((double)opt->maxmem * 1000 * 1000) / ((double)D * D * sizeof(double)), (double)S);
+      if (opt->info) printf("Collecting statistics at maximum for %d states\n", maxpos);
+      if (opt->info > 0) printf("Reserving memory\n");
+      fflush(stdout);
+    }
+    aasr_scatter *h = nullptr;
+    {
+      const aasr_status cs = aasr_scatter_create(S, D, &h);
+      if (cs != AASR_OK) raise(cs, "%s", last_error().c_str());
+    }
+    std::unique_ptr<aasr_scatter, void (*)(aasr_scatter *)> hguard(h, aasr_scatter_destroy);
+    // two stagings per group: the chain's output, which the model scores, and the module's source, which is summed.
+    // Each has a stream of its own; a speaker change that rewrites feature parameters waits for both.
+    GroupStager scored(feat.get(), spk, -1), summed(feat.get(), spk, source);
+    const hipStream_t stream = scored.stream, sum_stream = summed.stream;
+    struct Unhook {
+      aasr_spkc *s;
+      ~Unhook() {
+        if (s) spkc_set_before_change(s, nullptr);
+      }
+    } unhook{spk};
+    if (spk)
+      spkc_set_before_change(spk, [stream, sum_stream]() {
+        AASR_HIP(hipStreamSynchronize(stream));
+        AASR_HIP(hipStreamSynchronize(sum_stream));
+      });
+    hipEvent_t ev[6];
+    for (hipEvent_t &e : ev) AASR_HIP(hipEventCreate(&e));
+    struct EvGuard {
+      hipEvent_t *e;
+      ~EvGuard() {
+        for (int i = 0; i < 6; i++) (void)hipEventDestroy(e[i]);
+      }
+    } evguard{ev};
+    aasr_fb_options fo;
+    network_fb_options(&fo, nopt->fw_beam, nopt->bw_beam, nopt->ac_scale_given != 0, nopt->ac_scale, nopt->viterbi != 0);
+    fo.want_pdf_occ = 1;
+    fo.device_occ = 1;
+    fo.max_attempts = 5;  // (counter >= 5, lda.cc:190)
+    NetworkCache net_cache(topo, S);
+    GroupScores scores;
+    std::vector<int64_t> cnt((size_t)S + 1);
+    double max_dev = 0;
+    int64_t entries = 0, num_frames = 0;
+    StageTimers tm;
+    tm.on = getenv("AASR_RECIPE_TIMING") != nullptr;
+    size_t next = 0;
+    while (next < infos.size()) {
+      double t = now_s();
+      const size_t group_first = next;
+      NetworkGroup g;
+      while (next < infos.size() && g.size() < 1024 &&
+             (g.size() == 0 || (g.rows_total < NETWORK_GROUP_FRAMES && g.rows_total * S < NETWORK_GROUP_SCORES))) {
+        const RecipeInfo &u = infos[next++];
+        announce(u, opt->info);
+        g.add(feat.get(), net_cache, u, u.hmmnet_path, fr);
+      }
+      tm.host += now_s() - t;
+      t = now_s();
+      const auto speaker_of = [&](size_t i) { apply_speaker(spk, infos[group_first + i]); };  // lda.cc:163-168
+      AASR_HIP(hipEventRecord(ev[0], stream));
+      scored.stage(g.audio, g.start, g.rows, speaker_of);
+      AASR_HIP(hipEventRecord(ev[1], stream));
+      if (tm.on) AASR_HIP(hipStreamSynchronize(stream));
+      tm.feat += now_s() - t;
+      const void *d_scores = nullptr;
+      const FbBatchPtr batch = run_network_group(fo, gmm, scored, g, scores, f64, &d_scores, &tm);
+      aasr_fb_batch *b = batch.get();
+      t = now_s();
+      const int32_t *d_rows = nullptr;
+      const double *d_weights = nullptr;
+      if (aasr_fb_batch_entries_dev(b, S, g.row0.data(), stream, cnt.data(), &d_rows, &d_weights) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      AASR_HIP(hipEventRecord(ev[2], stream));  // the entries stand
+      entries += cnt[(size_t)S];
+      tm.fb += now_s() - t;
+      for (size_t i = 0; i < g.size(); i++) {
+        const RecipeInfo &u = infos[group_first + i];
+        if (!report_network_outcome(b, i, fo, RetryMessages::BAUM_WELCH, u)) continue;
+        check_frame_sums(b, i, g, u, &max_dev);
+        num_frames += g.rows[i];
+      }
+      // the same utterances and frame ranges at the module's source: an entry's row number addresses both buffers
+      t = now_s();
+      AASR_HIP(hipEventRecord(ev[3], sum_stream));
+      summed.stage(g.audio, g.start, g.rows, speaker_of);
+      AASR_HIP(hipEventRecord(ev[4], sum_stream));
+      if (tm.on) AASR_HIP(hipStreamSynchronize(sum_stream));
+      tm.feat += now_s() - t;
+      t = now_s();
+      AASR_HIP(hipStreamWaitEvent(sum_stream, ev[2], 0));
+      if (cnt[(size_t)S] > 0 && aasr_scatter_accumulate_weighted_dev(h, summed.d_x.p, g.rows_total, cnt.data(), d_rows,
+                                                                     d_weights, sum_stream) != AASR_OK)
+        raise(AASR_ERR_INVALID, "%s", aasr_last_error());
+      AASR_HIP(hipEventRecord(ev[5], sum_stream));
+      // the batch owns the entries that the accumulation reads, the group its audio: they go when the streams are done
+      AASR_HIP(hipStreamSynchronize(stream));
+      AASR_HIP(hipStreamSynchronize(sum_stream));
+      tm.acc += now_s() - t;
+      float ms = 0;
+      AASR_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      opt->seconds_features += ms * 1e-3;
+      AASR_HIP(hipEventElapsedTime(&ms, ev[3], ev[4]));
+      opt->seconds_features += ms * 1e-3;
+      AASR_HIP(hipEventElapsedTime(&ms, ev[4], ev[5]));
+      opt->seconds_scatter += ms * 1e-3;
+    }
+    if (opt->info > 0) {
+      fprintf(stderr, "Largest |1 - sum of PDF probabilities| of a frame: %g\n", max_dev);
+      fprintf(stderr, "Weighted entries: %lld over %lld frames\n", (long long)entries, (long long)num_frames);
+    }
+    if (tm.on)
+      fprintf(stderr,
+              "lda timing: input and networks %.3f s, features (both stagings) %.3f s, scoring %.3f s, forward-backward and "
+              "entries %.3f s, accumulation %.3f s\n",
+              tm.host, tm.feat, tm.score, tm.fb, tm.acc);
+
+    // ---- the selection on the fetched gamma (lda.cc:247-263), then the LDA
+    std::vector<int32_t> selected((size_t)S, 0);
+    solve_and_write(feat.get(), ltm, h, sum_stream, S, D, td, opt, selected, [&](const std::vector<double> &gamma) {
+      lda_select(S, gamma.data(), opt->mingamma, opt->maxmem, D, silence.data(), opt->no_silence ? (int)silence.size() : 0,
+                 selected.data());
+      if (opt->no_silence && opt->info > 0) printf("Discarding %d silence states\n", (int)silence.size());
+      if (opt->info) printf("Collecting statistics for %d states\n", (int)std::count(selected.begin(), selected.end(), 1));
+      fflush(stdout);
+    });
+    fill_run_stats(stats, (int64_t)infos.size(), num_frames, t0, opt->seconds_scatter + opt->seconds_features);
+  });
+}
+
+}  // extern "C"

@@ -64,6 +64,13 @@ struct ScatterParams {
 // the slabs of items [item0, item0 + n_items), then acc += the slabs of every group in item order
 void scatter_launch(const ScatterParams &p, int item0, int n_items, const ScatterGroup *groups, int n_groups, double *slab,
                     double *acc, hipStream_t stream);
+// the second half of scatter_launch alone: acc += the slabs of every group in item order
+void scatter_slab_add_launch(int dim, const ScatterGroup *groups, int n_groups, const double *slab, double *acc,
+                             hipStream_t stream);
+// scatter_launch over weighted entries (scatter_entries.hip): p.rows are the entries' frame rows, class run after class
+// run, p.weight the entries' weights (indexed as p.rows is, never null); an entry of weight 0 does not read its row
+void scatter_entries_launch(const ScatterParams &p, int item0, int n_items, const ScatterGroup *groups, int n_groups,
+                            double *slab, double *acc, hipStream_t stream);
 
 }  // namespace aasr
 

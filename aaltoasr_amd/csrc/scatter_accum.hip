@@ -41,7 +41,13 @@ void scatter_launch(const ScatterParams &p, int item0, int n_items, const Scatte
   });
   if (!launched) raise(AASR_ERR_UNSUPPORTED, "scatter: no accumulation kernel for dimension %d", p.dim);
   AASR_HIP(hipGetLastError());
-  const int64_t TS = scatter_class_doubles(p.dim);
+  scatter_slab_add_launch(p.dim, groups, n_groups, slab, acc, stream);
+}
+
+void scatter_slab_add_launch(int dim, const ScatterGroup *groups, int n_groups, const double *slab, double *acc,
+                             hipStream_t stream) {
+  if (n_groups <= 0) return;
+  const int64_t TS = scatter_class_doubles(dim);
   hipLaunchKernelGGL(k_scatter_slab_add, dim3((unsigned)((TS + 255) / 256), (unsigned)n_groups), dim3(256), 0, stream, slab,
                      groups, TS, acc);
   AASR_HIP(hipGetLastError());

@@ -1160,12 +1160,14 @@ aasr_status aasr_run_mllr_networks_recipe(aasr_feat *feat, aasr_gmm *gmm, const 
                                           const aasr_mllr_network_options *net, aasr_run_stats *stats);
 
 /* ---------------------------------------------------------------------------
- * LDA estimation: aku/lda.cc over state-segmented .phn files.
+ * LDA estimation: aku/lda.cc over state-segmented .phn files, or (aasr_run_lda_networks_recipe) over the recipe's HMM
+ * networks.
  *
  * The class-scatter accumulator, on the device: FullStatisticsAccumulator::accumulate
  * (aku/Distributions.cc:133-141) per class c over many frames at once,
  *   gamma_c += w_t,  sum_x_c += w_t x_t,  sum_xx_c += w_t x_t x_t^T
- * on the FP64 matrix pipe (csrc/scatter_accum.hip).  1 ... 127 dimensions (AASR_ERR_UNSUPPORTED beyond).
+ * on the FP64 matrix pipe (csrc/scatter_accum.hip; from weighted entries csrc/scatter_entries.hip).  1 ... 127
+ * dimensions (AASR_ERR_UNSUPPORTED beyond).
  * Deterministic: no atomics, fixed summation order; the same calls give the same bytes. */
 typedef struct aasr_scatter aasr_scatter;
 aasr_status aasr_scatter_create(int32_t n_classes, int32_t dim, aasr_scatter **out);
@@ -1175,6 +1177,24 @@ void aasr_scatter_destroy(aasr_scatter *h);
  * doubles; NULL: 1) on `stream`, no host wait.  Calls on one handle go to one stream. */
 aasr_status aasr_scatter_accumulate_dev(aasr_scatter *h, const double *d_frames, int64_t n_frames, const int32_t *cls,
                                         const double *d_weight, void *stream);
+/* The same sums from weighted entries (csrc/scatter_entries.hip), so that a frame may stand under several classes: what
+ * a Baum-Welch segmentation hands to the trainer.  cnt (host, n_classes + 1): cnt[c] is the first entry of class c,
+ * cnt[n_classes] the number of entries -- the layout of aasr_stats_accumulate_weighted_dev and of
+ * aasr_fb_batch_entries_dev.  d_rows / d_weights (device, cnt[n_classes] elements): entry e of class c adds
+ * d_weights[e] xi xi^T for frame row d_rows[e] of d_frames ([n_frames x dim]; the rows must lie in 0 ... n_frames - 1, the
+ * caller's contract: the list is not fetched).  An entry of weight 0 does not read its row: a NaN frame under weight 0
+ * leaves the sums clean.  The host cuts cnt into work items of at most 256 entries of one class and uploads those
+ * lists only; launches are cut by the slab bound exactly as in aasr_scatter_accumulate_dev, and the same input gives the
+ * same bytes whatever the bound cuts the call into.  No host wait; the entry arrays must stay valid until the stream
+ * is done with them.
+ * Byte contract: with one entry per frame in the order of the row list that aasr_scatter_accumulate_dev builds (class
+ * after class, frames ascending within a class) and entry weights equal to that call's per-row weights (or 1.0), the
+ * accumulator has that call's bytes.  Both calls may be mixed on one handle.
+ * AASR_ERR_INVALID, and nothing queued: cnt[0] != 0; a decreasing cnt; more than 2^31 entries or frames; entries
+ * without frames, rows or weights. */
+aasr_status aasr_scatter_accumulate_weighted_dev(aasr_scatter *h, const double *d_frames, int64_t n_frames,
+                                                 const int64_t *cnt, const int32_t *d_rows, const double *d_weights,
+                                                 void *stream);
 /* fetches the sums to the host (waits) */
 aasr_status aasr_scatter_fetch(aasr_scatter *h, void *stream);
 /* after a fetch: gamma [n_classes], sum_x [n_classes x dim], sum_xx [n_classes x dim (dim + 1) / 2] -- the packed
@@ -1182,7 +1202,8 @@ aasr_status aasr_scatter_fetch(aasr_scatter *h, void *stream);
  * may be NULL */
 aasr_status aasr_scatter_get(const aasr_scatter *h, double *gamma, double *sum_x, double *sum_xx);
 /* Diagnostic, read-only: out[0] the kernel's instance PB (16 PB >= dim + 1), out[1] work items and out[2] launches
- * of the last aasr_scatter_accumulate_dev call that had rows to add.  Zeros before the first. */
+ * of the last aasr_scatter_accumulate_dev or aasr_scatter_accumulate_weighted_dev call that had rows or entries to
+ * add.  Zeros before the first. */
 void aasr_debug_scatter_shape(const aasr_scatter *h, int32_t *out);
 /* Diagnostic: the bound on a launch's slab memory in bytes (default 64 MiB, csrc/scatter.h; at least one item's
  * slab is always allowed), so that a test reaches several launches with a few thousand rows. */
@@ -1236,6 +1257,47 @@ void aasr_lda_default_options(aasr_lda_options *opt);
  * the configuration is written to opt->out.  A missing _ or __ HMM is AASR_ERR_INVALID. */
 aasr_status aasr_run_lda_recipe(const char *feat_cfg_text, const aasr_topo *topo, const char *recipe_path,
                                 aasr_lda_options *opt, aasr_run_stats *stats);
+
+/* What the HMM networks add (aasr_run_lda_networks_recipe).  A struct of its own: aasr_lda_options stays as it is for
+ * its callers. */
+typedef struct aasr_lda_network_options {
+  int32_t networks;       /* 1: segment with the recipe's hmmnet= networks; 0: the call is aasr_run_lda_recipe */
+  int32_t viterbi;        /* --segmode vit: the best path instead of Baum-Welch                                 */
+  double fw_beam;         /* -F: 0 keeps the default 15 (set_pruning_thresholds)                                */
+  double bw_beam;         /* -W: 0 keeps the default 200                                                        */
+  int32_t ac_scale_given; /* 1: -A was on the command line                                                      */
+  double ac_scale;        /* -A                                                                                 */
+} aasr_lda_network_options;
+void aasr_lda_network_default_options(aasr_lda_network_options *opt);
+/* The host-side refusals of aasr_run_lda_networks_recipe, without opening the device, for a caller (the lda tool) that
+ * wants them before it builds the model: recipe line limits; a line without hmmnet= (the reference's error); -d against
+ * the module's configured dimension; a missing _ or __ HMM; opt->ophn (AASR_ERR_UNSUPPORTED); a lin_transform module
+ * whose configuration gives no matrix (AASR_ERR_INVALID, the module named): the networks mode runs the whole chain to
+ * score, so the model's input must exist. */
+aasr_status aasr_lda_networks_check(const char *feat_cfg_text, const aasr_topo *topo, const char *recipe_path,
+                                    const aasr_lda_options *opt);
+/* lda over the recipe's hmmnet= networks: what aku/lda.cc:147-372 would compute from HmmNetBaumWelch's pdf_probs() with
+ * -H.  The reference's own -H cannot run (the tool reads only --ph, so it has no Gaussians to score with, and asks an
+ * option it never declares), so parity with the reference binary is unpinned; the yardstick is the restatement in
+ * tools/lda_networks_restate.py.  gmm: the diagonal model that scores the chain's output (its dimension must be the
+ * chain's: check_feature_dim).
+ * aasr_lda_networks_check first.  Then per group of at most 1024 lines, 2^18 frames and 2^27 scores: the frames of the
+ * chain's output; the state rows of the model's scoring entry in the model's precision mode; one forward-backward batch
+ * (aasr_fb_batch_*), a failed backward pass run again up to four times with 2x ... 5x the backward beam (lda.cc:186-202)
+ * with the reference's messages on stderr, an utterance that still fails reported and adding nothing; the frame sums
+ * checked as aasr_run_stats_networks_recipe checks them; the pdf-major entries (aasr_fb_batch_entries_dev); the frames AT
+ * THE MODULE'S SOURCE for the same utterances and frame ranges (the chain is evaluated twice per group), so that the
+ * entries' row numbers address both buffers; one aasr_scatter_accumulate_weighted_dev over all states.
+ * ONE pass, not the reference's two: the handle keeps every state's sums, a state's gamma is entry (0, 0) of them, and
+ * the selection (aasr_lda_select, -m, --mingamma, --no-silence) is made on the fetched gamma.  That halves the
+ * forward-backward work.  Under Baum-Welch a gamma that lies exactly at --mingamma could select differently from a sum
+ * made in frame order; with net->viterbi the weights are 1.0 and gamma is exact.  Then aasr_lda_solve and the
+ * configuration as in aasr_run_lda_recipe.  opt->state_gamma, seconds_scatter and seconds_features are filled as there.
+ * With info > 0 the largest |1 - s_t| and the number of weighted entries on stderr.
+ * net NULL or net->networks 0: aasr_run_lda_recipe (gmm may be NULL then). */
+aasr_status aasr_run_lda_networks_recipe(const char *feat_cfg_text, aasr_gmm *gmm, const aasr_topo *topo,
+                                         const char *recipe_path, aasr_lda_options *opt,
+                                         const aasr_lda_network_options *net, aasr_run_stats *stats);
 
 /* ---------------------------------------------------------------------------
  * Clustering of the Gaussian pool: aku/gcluster.cc in its default (diagonal) mode, one group.
