@@ -1,0 +1,151 @@
+"""FstDecoder -- the reference's Python module of its FST decoder, on the engine.
+
+The reference builds a SWIG module `FstDecoder` over decoder/src/FstSearch.hh; scripts do
+
+    import FstDecoder
+    s = FstDecoder.FstSearch("final.fst", "model.ph", "model.dur")
+    s.set_beam(300); s.lna_open("a.lna", 1024); s.init_search(); s.run()
+    print(s.get_result())
+
+This module keeps the class FstSearch -- same method names, argument order and meaning -- and runs the search on the
+device through the C ABI (include/aasr.h, aasr_fst_batch_*) as a batch of one utterance.  Strings are bytes, as the
+reference's `bytestype`.  The .ph path is opened as the reference opens it (an unreadable file is the reference's
+"FstAcoustics: open error") and otherwise unused: the search never consults the HMM file, the network carries the state
+indices.  hmm_path and dur_path may be None.  The duration tables are indexed as the reference builds them unless
+`dur_by_state` is set (csrc/fst_net.h).  Differences, on purpose: every lna_open starts at the file's first frame (the
+reference never rewinds its frame counter), and a frame without any candidate ends the search with status NO_TOKENS and
+the empty result where the reference indexes an empty vector.  FstConfidence is not built.
+`sys.path.insert(0, ".../aaltoasr_amd"); import FstDecoder` is the drop-in spelling.
+"""
+import os
+import struct
+
+try:
+    from . import capi as _A
+except ImportError:  # imported as a top-level module named FstDecoder
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from aaltoasr_amd import capi as _A
+
+
+def _guard(fn):
+    def wrapped(*args, **kw):
+        try:
+            return fn(*args, **kw)
+        except _A.AasrError as e:
+            raise RuntimeError("Exception: %s" % e.msg) from None
+    wrapped.__name__ = fn.__name__
+    wrapped.__doc__ = fn.__doc__
+    return wrapped
+
+
+def _g(x) -> bytes:
+    return (b"%g" % float(x))      # an ostream's default float format
+
+
+class FstSearch:
+    @_guard
+    def __init__(self, search_fst_fname, hmm_path=None, dur_path=None):
+        if hmm_path is not None:
+            try:
+                open(hmm_path, "rb").close()
+            except OSError:
+                raise RuntimeError("Exception: FstAcoustics: open error") from None
+        self._dur = _A.FstDurations(dur_path) if dur_path is not None else None
+        self._net = _A.FstNet(search_fst_fname)
+        self._opt = _A.FstOptions.defaults()
+        self._lna = None
+        self._result = None
+        self.verbose = 0
+        self.dur_by_state = False
+        self.status = _A.AASR_FST_OK
+
+    def set_duration_scale(self, d):
+        self._opt.duration_scale = d
+
+    def set_beam(self, b):
+        self._opt.beam = b
+
+    def set_token_limit(self, t):
+        self._opt.token_limit = t
+
+    def set_transition_scale(self, t):
+        self._opt.transition_scale = t
+
+    def get_duration_scale(self):
+        return self._opt.duration_scale
+
+    def get_beam(self):
+        return self._opt.beam
+
+    def get_token_limit(self):
+        return self._opt.token_limit
+
+    def get_transition_scale(self):
+        return self._opt.transition_scale
+
+    def lna_open(self, file, size):
+        """LnaReaderCircular::open: the 5-byte header, then the frames; `size` (the reader's buffer) is not needed"""
+        try:
+            data = open(file, "rb").read()
+        except OSError:
+            raise RuntimeError("Exception: LnaReaderCircular::open(): could not open %s" % file) from None
+        if len(data) < 5:
+            raise RuntimeError("Exception: LnaReaderCircular::read_int(): End of file reached.")
+        n_models, lnabytes = struct.unpack(">iB", data[:5])
+        if n_models <= 0:
+            raise RuntimeError("Exception: LnaReaderCircular::open(): invalid number of states %d" % n_models)
+        if lnabytes not in (1, 2, 4):
+            raise RuntimeError("Exception: LnaReaderCircular::open(): invalid LNA byte number %d" % lnabytes)
+        frames = (len(data) - 5) // (n_models * lnabytes)
+        self._lna = (data[5:5 + frames * n_models * lnabytes], n_models, lnabytes, frames)
+
+    def lna_close(self):
+        self._lna = None
+
+    def init_search(self):
+        """one token at the initial node (FstSearch_tmpl.hh:45-51)"""
+        self._result = {"status": _A.AASR_FST_OK, "tokens": [(self._net.initial, 0.0, 0, ())], "words": (), "text": b"",
+                        "logprob": 0.0 if self._net.arrays()["node_end"][self._net.initial] else -1.0, "best_logprob": 0.0,
+                        "best_final_logprob": 0.0 if self._net.arrays()["node_end"][self._net.initial] else -9999999.9}
+
+    @_guard
+    def run(self):
+        if self._lna is None:
+            raise RuntimeError("Exception: LnaReaderCircular::go_to(): file not opened yet")
+        import torch
+        raw, n_models, lnabytes, frames = self._lna
+        d_lna = torch.frombuffer(bytearray(raw + bytes(16)), dtype=torch.uint8).cuda()
+        self._opt.dur_by_state = 1 if self.dur_by_state else 0
+        self._result = _A.fst_batch(self._net, [frames], d_lna, lnabytes, n_models, [0], self._opt, dur=self._dur)[0]
+        self.status = self._result["status"]
+
+    def _need(self):
+        if self._result is None:
+            raise RuntimeError("Exception: init_search() or run() first")
+        return self._result
+
+    def get_result(self):
+        return self._need()["text"]
+
+    def get_result_and_logprob(self):
+        r = self._need()
+        return r["text"], float(r["logprob"])
+
+    def get_best_token_logprob(self):
+        return float(self._need()["best_logprob"])
+
+    def get_best_final_token_logprob(self):
+        return float(self._need()["best_final_logprob"])
+
+    def _token(self, t) -> bytes:
+        node, lp, dur, words = t
+        return b"Token %d %s dur %d '%s '" % (node, _g(lp), dur, b"".join(b" " + self._net.symbols[w] for w in words))
+
+    def tokens_at_final_states(self):
+        end = self._net.arrays()["node_end"]
+        return b"Tokens at final nodes:\n" + b"".join(b"  " + self._token(t) + b"\n" for t in self._need()["tokens"] if end[t[0]])
+
+    def best_tokens(self, n=10):
+        """the reference's loop prints n + 2 tokens at the most (`if (c++ > n) break` after the print)"""
+        return b"Best tokens:\n" + b"".join(b"  " + self._token(t) + b"\n" for t in self._need()["tokens"][:n + 2])

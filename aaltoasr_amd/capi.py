@@ -441,6 +441,38 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_recipe_read_all.argtypes = [cp, i32, i32, i32, C.POINTER(C.c_void_p), C.POINTER(i64)]
     L.aasr_audio_read.argtypes = [vp, cp, C.POINTER(C.POINTER(C.c_int16)), C.POINTER(i64),
                                   C.POINTER(i32)]
+    # FST decoder
+    L.aasr_fstnet_create_from_file.argtypes = [cp, pvp]
+    L.aasr_fstnet_destroy.argtypes = [vp]
+    L.aasr_fstnet_destroy.restype = None
+    for name in ("num_nodes", "num_arcs", "num_symbols", "initial", "max_pdf"):
+        getattr(L, "aasr_fstnet_" + name).argtypes = [vp]
+    L.aasr_fstnet_symbol.argtypes = [vp, i32]
+    L.aasr_fstnet_symbol.restype = cp
+    L.aasr_fstnet_arrays.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.aasr_fst_default_options.argtypes = [vp]
+    L.aasr_fst_default_options.restype = None
+    L.aasr_fst_durations_read.argtypes = [cp, pvp]
+    L.aasr_fst_durations_destroy.argtypes = [vp]
+    L.aasr_fst_durations_destroy.restype = None
+    L.aasr_fst_durations_num_states.argtypes = [vp]
+    L.aasr_fst_durations_logprob.argtypes = [vp, i32, i32, i32]
+    L.aasr_fst_durations_logprob.restype = f
+    L.aasr_fst_batch_create.argtypes = [vp, vp, vp, i32, vp, pvp]
+    L.aasr_fst_batch_destroy.argtypes = [vp]
+    L.aasr_fst_batch_destroy.restype = None
+    L.aasr_fst_batch_device_bytes.argtypes = [vp]
+    L.aasr_fst_batch_device_bytes.restype = i64
+    L.aasr_fst_batch_options.argtypes = [vp, vp]
+    L.aasr_fst_batch_options.restype = None
+    L.aasr_fst_batch_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp]
+    L.aasr_fst_batch_sync.argtypes = [vp, vp, C.POINTER(i32)]
+    L.aasr_fst_batch_result.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(f), C.POINTER(f), C.POINTER(f), C.POINTER(i32),
+                                        vp, i32, C.POINTER(i32)]
+    L.aasr_fst_batch_tokens.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp]
+    L.aasr_fst_decode_default_options.argtypes = [vp]
+    L.aasr_fst_decode_default_options.restype = None
+    L.aasr_run_fst_decode_recipe.argtypes = [vp, vp, vp, vp, cp, vp, vp]
 
 
 def check(status: int) -> None:
@@ -2722,3 +2754,175 @@ def dur_est_fit_gamma(hist) -> Optional[tuple]:
     h = np.ascontiguousarray(hist, np.int32)
     a, b = C.c_double(), C.c_double()
     return (a.value, b.value) if lib().aasr_dur_est_fit_gamma(_ptr(h), len(h), C.byref(a), C.byref(b)) else None
+
+
+# ---- FST decoder (token passing over a search network) -------------------------------------------
+
+AASR_FST_OK, AASR_FST_NO_TOKENS, AASR_FST_OVERFLOW_CANDIDATES, AASR_FST_OVERFLOW_RECOMB, AASR_FST_OVERFLOW_HISTORY = range(5)
+FST_STATUS_NAMES = ("OK", "NO_TOKENS", "OVERFLOW_CANDIDATES", "OVERFLOW_RECOMB", "OVERFLOW_HISTORY")
+
+
+class FstOptions(C.Structure):
+    """aasr_fst_options"""
+    _fields_ = [("beam", C.c_float), ("token_limit", C.c_int32), ("duration_scale", C.c_float),
+                ("transition_scale", C.c_float), ("dur_by_state", C.c_int32), ("cap_candidates", C.c_int32),
+                ("cap_recomb", C.c_int32), ("cap_history", C.c_int32)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "FstOptions":
+        o = cls()
+        lib().aasr_fst_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+class FstNet:
+    """aasr_fstnet: a "#FSTBasic MaxPlus" search network (Fst::read).  Host only."""
+
+    def __init__(self, path: str):
+        self._h = C.c_void_p()
+        check(lib().aasr_fstnet_create_from_file(os.fsencode(path), C.byref(self._h)))
+        L = lib()
+        self.num_nodes, self.num_arcs = L.aasr_fstnet_num_nodes(self._h), L.aasr_fstnet_num_arcs(self._h)
+        self.initial, self.max_pdf = L.aasr_fstnet_initial(self._h), L.aasr_fstnet_max_pdf(self._h)
+        self.symbols = [L.aasr_fstnet_symbol(self._h, i) for i in range(L.aasr_fstnet_num_symbols(self._h))]
+
+    @property
+    def handle(self):
+        return self._h
+
+    def arrays(self) -> dict:
+        a = {"arc_begin": np.zeros(self.num_nodes + 1, np.int32), "arc_tgt": np.zeros(self.num_arcs, np.int32),
+             "arc_lp": np.zeros(self.num_arcs, np.float32), "arc_word": np.zeros(self.num_arcs, np.int32),
+             "node_pdf": np.zeros(self.num_nodes, np.int32), "node_end": np.zeros(self.num_nodes, np.int32)}
+        check(lib().aasr_fstnet_arrays(self._h, *[_ptr(a[k]) for k in ("arc_begin", "arc_tgt", "arc_lp", "arc_word", "node_pdf", "node_end")]))
+        return a
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_fstnet_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FstDurations:
+    """aasr_fst_durations: the .dur file of FstAcoustics::duration_read.  Host only."""
+
+    def __init__(self, path: str):
+        self._h = C.c_void_p()
+        check(lib().aasr_fst_durations_read(os.fsencode(path), C.byref(self._h)))
+        self.num_states = lib().aasr_fst_durations_num_states(self._h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def logprob(self, pdf: int, d: int, by_state: bool = False) -> np.float32:
+        return np.float32(lib().aasr_fst_durations_logprob(self._h, 1 if by_state else 0, pdf, d))
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_fst_durations_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fst_batch_once(net: FstNet, dur, opts: FstOptions, n_frames, d_lna, lnabytes: int, n_models: int, row0, stream: int,
+                    want_tokens: bool) -> list:
+    L = lib()
+    n = len(n_frames)
+    T = np.ascontiguousarray(n_frames, np.int32)
+    r0 = np.ascontiguousarray(row0, np.int64)
+    n_rows = (d_lna.numel() * d_lna.element_size()) // (n_models * lnabytes)
+    b = C.c_void_p()
+    check(L.aasr_fst_batch_create(net.handle, dur.handle if dur is not None else None, C.byref(opts), n, _ptr(T), C.byref(b)))
+    try:
+        over = C.c_int32(0)
+        check(L.aasr_fst_batch_dev(b, _ptr(d_lna), lnabytes, n_models, n_rows, _ptr(r0), stream))
+        check(L.aasr_fst_batch_sync(b, stream, C.byref(over)))
+        resolved = FstOptions()
+        L.aasr_fst_batch_options(b, C.byref(resolved))
+        out = []
+        for u in range(n):
+            st, nw, nt = C.c_int32(), C.c_int32(), C.c_int32()
+            lp, blp, bflp = C.c_float(), C.c_float(), C.c_float()
+            words = np.zeros(int(T[u]) + 1, np.int32)
+            check(L.aasr_fst_batch_result(b, u, C.byref(st), C.byref(lp), C.byref(blp), C.byref(bflp), C.byref(nw), _ptr(words),
+                                          len(words), C.byref(nt)))
+            r = {"status": st.value, "logprob": np.float32(lp.value), "best_logprob": np.float32(blp.value),
+                 "best_final_logprob": np.float32(bflp.value), "words": tuple(int(w) for w in words[:nw.value]),
+                 "text": b" ".join(net.symbols[w] for w in words[:nw.value]), "n_tokens": nt.value,
+                 "options": resolved, "device_bytes": L.aasr_fst_batch_device_bytes(b), "reran": False}
+            if want_tokens:
+                k = nt.value
+                node, tl, td = np.zeros(k, np.int32), np.zeros(k, np.float32), np.zeros(k, np.int32)
+                wb, tw = np.zeros(k + 1, np.int32), np.zeros(max(1, k * (int(T[u]) + 1)), np.int32)
+                check(L.aasr_fst_batch_tokens(b, u, k, _ptr(node), _ptr(tl), _ptr(td), _ptr(wb), len(tw), _ptr(tw)))
+                r["tokens"] = [(int(node[j]), np.float32(tl[j]), int(td[j]), tuple(int(w) for w in tw[wb[j]:wb[j + 1]]))
+                               for j in range(k)]
+            out.append(r)
+        return out
+    finally:
+        L.aasr_fst_batch_destroy(b)
+
+
+def fst_batch(net: FstNet, n_frames: list, d_lna, lnabytes: int, n_models: int, row0: list, opts: Optional[FstOptions] = None,
+              dur: Optional[FstDurations] = None, stream: int = 0, want_tokens: bool = True, rerun: bool = True) -> list:
+    """The FST token pass of a batch of utterances on the device.  d_lna: a device tensor (uint8, or float32 for
+    lnabytes 4) of LNA rows, row0[u] the row of utterance u's first frame.  Per utterance a dict: status, logprob, words
+    (ids), text (bytes), best_logprob, best_final_logprob, n_tokens and, with want_tokens, tokens: (node, logprob, dur,
+    words) by descending log-probability.  With rerun the utterances that overflowed a capacity run once more in a batch of
+    their own with every capacity doubled (`reran`); those that overflow again keep their overflow status."""
+    opts = opts or FstOptions.defaults()
+    out = _fst_batch_once(net, dur, opts, n_frames, d_lna, lnabytes, n_models, row0, stream, want_tokens)
+    again = [u for u, r in enumerate(out) if r["status"] >= AASR_FST_OVERFLOW_CANDIDATES]
+    if rerun and again:
+        o2 = FstOptions()
+        C.memmove(C.byref(o2), C.byref(out[again[0]]["options"]), C.sizeof(o2))
+        o2.cap_candidates, o2.cap_recomb, o2.cap_history = 2 * o2.cap_candidates, 2 * o2.cap_recomb, 2 * o2.cap_history
+        second = _fst_batch_once(net, dur, o2, [n_frames[u] for u in again], d_lna, lnabytes, n_models,
+                                 [row0[u] for u in again], stream, want_tokens)
+        for u, r in zip(again, second):
+            r["reran"] = True
+            out[u] = r
+    return out
+
+
+class FstDecodeOptions(C.Structure):
+    """aasr_fst_decode_options"""
+    _fields_ = [("fst", FstOptions), ("lna_files", C.c_int32), ("lnabytes", C.c_int32), ("group", C.c_int32),
+                ("num_batches", C.c_int32), ("batch_index", C.c_int32), ("info", C.c_int32), ("speakers", C.c_void_p),
+                ("out", C.c_char_p)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "FstDecodeOptions":
+        o = cls()
+        lib().aasr_fst_decode_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_fst_decode_recipe(feat: Optional["Feat"], gmm: Optional["Gmm"], net: FstNet, recipe_path: str, out: str,
+                          opts: Optional[FstDecodeOptions] = None, dur: Optional[FstDurations] = None,
+                          speakers: Optional["SpeakerConfig"] = None) -> dict:
+    """The fst_decode tool's run (aasr_run_fst_decode_recipe): engine mode from the recipe's audio= with feat and gmm, or
+    opts.lna_files on its lna= files.  One line per utterance into `out`.  -> utterances, frames, seconds."""
+    opts = opts or FstDecodeOptions.defaults()
+    opts.out = os.fsencode(out)
+    opts.speakers = speakers._h if speakers is not None else None
+    st = RunStats()
+    check(lib().aasr_run_fst_decode_recipe(feat._h if feat is not None else None, gmm._h if gmm is not None else None, net.handle,
+                                           dur.handle if dur is not None else None, os.fsencode(recipe_path), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total, "seconds_device": st.seconds_device}

@@ -1702,6 +1702,113 @@ aasr_status aasr_run_dur_est(const char *ph_path, const char *recipe_path, const
  * than two points.  Host only. */
 int32_t aasr_dur_est_fit_gamma(const int32_t *hist, int32_t n, double *a, double *b);
 
+/* ---- FST decoder: token passing over a compiled search network (the reference's FstSearch) ---------------------------
+ * The reference's small decoder (decoder/src/FstSearch_tmpl.hh, Fst.cc, FstAcoustics.cc) restated: a frame-synchronous
+ * token pass over a "#FSTBasic MaxPlus" network with state indices on the arcs, a beam, a token limit and recombination
+ * on (node, word history).  One workgroup per utterance, a batch per launch (csrc/fst_search.h).  The arithmetic is
+ * the reference's float operations in its order; tools/fst_restate.py is the same in NumPy and the yardstick of the tests.
+ * Out of scope: FstConfidence, FstWithPhoneLoop, TokenPassSearch and n-grams, lattices and n-best lists, epsilon closure
+ * (the reference has none: a token crosses one arc per frame), one utterance over several workgroups. */
+typedef struct aasr_fstnet aasr_fstnet;
+/* Fst::read (Fst.cc:10-103) with its messages in aasr_last_error() (AASR_ERR_INVALID; AASR_ERR_IO: cannot open): "Unknown
+ * header", "Too few fields", "Too many fields for I:" / "F:", "Weird number of fields for T:", "Weird type indicator:",
+ * "Conflicting emission_pdf_indices".  Also refused: a negative node index, no initial node.  csrc/fst_net.h. */
+aasr_status aasr_fstnet_create_from_file(const char *path, aasr_fstnet **out);
+void aasr_fstnet_destroy(aasr_fstnet *net);
+int32_t aasr_fstnet_num_nodes(const aasr_fstnet *net);
+int32_t aasr_fstnet_num_arcs(const aasr_fstnet *net);
+int32_t aasr_fstnet_num_symbols(const aasr_fstnet *net);
+int32_t aasr_fstnet_initial(const aasr_fstnet *net);
+int32_t aasr_fstnet_max_pdf(const aasr_fstnet *net);
+/* symbol `id` (ids in order of first appearance), the file's bytes; NULL outside 0 ... num_symbols - 1 */
+const char *aasr_fstnet_symbol(const aasr_fstnet *net, int32_t id);
+/* the CSR arrays (any may be NULL): arc_begin [nodes + 1]; arc_tgt, arc_logprob, arc_word (-1: no symbol) [arcs], file
+ * order within a node; node_pdf (-1: non-emitting), node_end [nodes] */
+aasr_status aasr_fstnet_arrays(const aasr_fstnet *net, int32_t *arc_begin, int32_t *arc_tgt, float *arc_logprob,
+                               int32_t *arc_word, int32_t *node_pdf, int32_t *node_end);
+
+typedef struct aasr_fst_options {
+  float beam;              /* 2600; finite, >= 0                                                                      */
+  int32_t token_limit;     /* 5000; the search keeps token_limit + 1 tokens, as the reference does                    */
+  float duration_scale;    /* 3                                                                                        */
+  float transition_scale;  /* 1                                                                                        */
+  int32_t dur_by_state;    /* 0: the duration tables as the reference builds them (the file's values at [n, 2n), zeros
+                              below: no duration term for pdf indices < n); 1: the file's values at [0, n)           */
+  int32_t cap_candidates;  /* capacities per utterance, 0 = derived from the network and the limit: candidates per     */
+  int32_t cap_recomb;      /* frame; recombination table and history table (powers of two).  Exceeding one gives the  */
+  int32_t cap_history;     /* utterance an AASR_FST_OVERFLOW_* status, never a silent truncation                      */
+} aasr_fst_options;
+void aasr_fst_default_options(aasr_fst_options *opt);
+
+enum {
+  AASR_FST_OK = 0,
+  AASR_FST_NO_TOKENS = 1,            /* no candidate at some frame (where the reference indexes an empty vector)      */
+  AASR_FST_OVERFLOW_CANDIDATES = 2,
+  AASR_FST_OVERFLOW_RECOMB = 3,
+  AASR_FST_OVERFLOW_HISTORY = 4
+};
+
+typedef struct aasr_fst_durations aasr_fst_durations;
+/* FstAcoustics::duration_read (FstAcoustics.cc:60-89): "4", the number of states, `id a b` per state.  Host only. */
+aasr_status aasr_fst_durations_read(const char *path, aasr_fst_durations **out);
+void aasr_fst_durations_destroy(aasr_fst_durations *dur);
+int32_t aasr_fst_durations_num_states(const aasr_fst_durations *dur);
+/* duration_logprob (FstAcoustics.cc:91-101) under either indexing; 0 where a <= 0 or the index is past the tables */
+float aasr_fst_durations_logprob(const aasr_fst_durations *dur, int32_t dur_by_state, int32_t pdf, int32_t d);
+
+typedef struct aasr_fst_batch aasr_fst_batch;
+/* A batch of n_utt utterances of n_frames[u] >= 0 frames over one network; dur may be NULL (no duration term: + scale *
+ * 0.0f).  net and dur must outlive the batch.  Needs a device. */
+aasr_status aasr_fst_batch_create(const aasr_fstnet *net, const aasr_fst_durations *dur, const aasr_fst_options *opt,
+                                  int32_t n_utt, const int32_t *n_frames, aasr_fst_batch **out);
+void aasr_fst_batch_destroy(aasr_fst_batch *b);
+int64_t aasr_fst_batch_device_bytes(const aasr_fst_batch *b);
+/* the options with the derived capacities filled in (what a rerun doubles) */
+void aasr_fst_batch_options(const aasr_fst_batch *b, aasr_fst_options *out);
+/* The search of every utterance.  d_lna: n_rows rows of n_models values of lnabytes bytes on the device -- 2 (big-endian
+ * codes) or 4 (floats) as aasr_gmm_score_lna_dev leaves them, or 1 from a file --, decoded as LnaReaderCircular does;
+ * utterance u reads rows row0[u] ... row0[u] + n_frames[u] - 1.  A network whose largest pdf index is not below n_models is
+ * AASR_ERR_INVALID (the reference would read out of bounds), as is a row range outside 0 ... n_rows. */
+aasr_status aasr_fst_batch_dev(aasr_fst_batch *b, const void *d_lna, int32_t lnabytes, int32_t n_models, int64_t n_rows,
+                               const int64_t *row0, void *stream);
+/* (aasr_fst_batch_dev only queues: copies and the launch on `stream`; nothing of the caller's is read after it returns.)
+ * Waits and fetches the results; n_overflow: the utterances with an AASR_FST_OVERFLOW_* status */
+aasr_status aasr_fst_batch_sync(aasr_fst_batch *b, void *stream, int32_t *n_overflow);
+/* Utterance u after a sync (any pointer may be NULL): status; logprob and words [n_words] of the best token at an end node
+ * (none: -1.0f and no words, get_result_and_logprob); best_logprob (get_best_token_logprob, -9999999.0f without tokens);
+ * best_final_logprob (-9999999.9f without an end-node token); n_tokens surviving the last frame. */
+aasr_status aasr_fst_batch_result(const aasr_fst_batch *b, int32_t u, int32_t *status, float *logprob, float *best_logprob,
+                                  float *best_final_logprob, int32_t *n_words, int32_t *words, int32_t cap_words,
+                                  int32_t *n_tokens);
+/* Every token surviving the last frame, by descending log-probability: node, logprob, dur [n_tokens], word_begin
+ * [n_tokens + 1] into words (NULL: counted only).  Copies the utterance's history table from the device. */
+aasr_status aasr_fst_batch_tokens(aasr_fst_batch *b, int32_t u, int32_t cap_tokens, int32_t *node, float *logprob, int32_t *dur,
+                                  int32_t *word_begin, int32_t cap_words, int32_t *words);
+
+/* fst_decode's run over a recipe (csrc/fst_decode.cc), groups of `group` utterances.  Engine mode (lna_files 0; feat and
+ * gmm given): per group the recipe's audio= through the feature chain (one launch set per stretch of equal speaker
+ * settings), ONE score + LNA step over the group's frames (aasr_gmm_score_lna_dev, normalised, lnabytes 2 or 4: the
+ * values phone_probs would write) and one search launch that reads the step's device buffer in place -- no LNA value
+ * leaves the device and no LNA file is written.  lna_files 1: the recipe's lna= files (1-, 2- or 4-byte; one width and
+ * model count per group) are uploaded and searched; feat, gmm and speakers NULL.  Utterances that overflow a capacity
+ * run once more with every capacity doubled (a line on stderr); those that overflow again keep their status.  Output
+ * to `out` ("-": stdout), one line per utterance: the line's audio (engine mode) or lna path, the log-probability as
+ * %.9g, the words, and a trailing status word (NO_TOKENS, OVERFLOW_*) when the status is not OK.  stats->seconds_device:
+ * from a group's first upload to its last result, summed. */
+typedef struct aasr_fst_decode_options {
+  aasr_fst_options fst;
+  int32_t lna_files;
+  int32_t lnabytes;     /* engine mode: 2 or 4 */
+  int32_t group;        /* utterances per launch, >= 1 */
+  int32_t num_batches, batch_index;
+  int32_t info;
+  aasr_spkc *speakers;  /* engine mode: -S, or NULL */
+  const char *out;
+} aasr_fst_decode_options;
+void aasr_fst_decode_default_options(aasr_fst_decode_options *opt);
+aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur,
+                                       const char *recipe_path, const aasr_fst_decode_options *opt, aasr_run_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
