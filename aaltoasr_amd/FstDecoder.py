@@ -7,14 +7,17 @@ The reference builds a SWIG module `FstDecoder` over decoder/src/FstSearch.hh; s
     s.set_beam(300); s.lna_open("a.lna", 1024); s.init_search(); s.run()
     print(s.get_result())
 
-This module keeps the class FstSearch -- same method names, argument order and meaning -- and runs the search on the
-device through the C ABI (include/aasr.h, aasr_fst_batch_*) as a batch of one utterance.  Strings are bytes, as the
+This module keeps the classes FstSearch, FstSearchC, FstConfidence and FstConfidenceWithPhoneLoop -- same method names,
+argument order and meaning -- and runs the search on the device through the C ABI (include/aasr.h, aasr_fst_batch_*,
+aasr_fst_conf_batch_*) as a batch of one utterance.  Strings are bytes, as the
 reference's `bytestype`.  The .ph path is opened as the reference opens it (an unreadable file is the reference's
 "FstAcoustics: open error") and otherwise unused: the search never consults the HMM file, the network carries the state
 indices.  hmm_path and dur_path may be None.  The duration tables are indexed as the reference builds them unless
 `dur_by_state` is set (csrc/fst_net.h).  Differences, on purpose: every lna_open starts at the file's first frame (the
 reference never rewinds its frame counter), and a frame without any candidate ends the search with status NO_TOKENS and
-the empty result where the reference indexes an empty vector.  FstConfidence is not built.
+the empty result where the reference indexes an empty vector.  The confidence classes: include/aasr.h, "FST decoder:
+confidence", states the formulas and what is chosen where the reference is undefined (no end-node token, zero frames); the
+reference's unconditional debug lines are not printed, its verbose block is when `verbose` is not 0.
 `sys.path.insert(0, ".../aaltoasr_amd"); import FstDecoder` is the drop-in spelling.
 """
 import os
@@ -36,6 +39,7 @@ def _guard(fn):
             raise RuntimeError("Exception: %s" % e.msg) from None
     wrapped.__name__ = fn.__name__
     wrapped.__doc__ = fn.__doc__
+    wrapped.__wrapped__ = fn
     return wrapped
 
 
@@ -149,3 +153,102 @@ class FstSearch:
     def best_tokens(self, n=10):
         """the reference's loop prints n + 2 tokens at the most (`if (c++ > n) break` after the print)"""
         return b"Best tokens:\n" + b"".join(b"  " + self._token(t) + b"\n" for t in self._need()["tokens"][:n + 2])
+
+
+class FstSearchC(FstSearch):
+    """the reference's second instantiation of its search template (FstSearch_base<FstConfidenceToken>): FstSearch's surface"""
+
+
+class FstConfidence(FstSearchC):
+    """FstConfidence(grammar_fst, hmm, dur): the grammar search and a confidence, 0.5 * (token_conf + best_acu_conf).
+    The reference's run() computes every frame's best acoustic value here and discards it: the sum is unused in this
+    class, best_acu_score stays 0, and the frame-best pass is not run."""
+    _phone_loop = 0
+
+    @_guard
+    def __init__(self, grammar_fst_name, hmm_fname=None, dur_fname=None):
+        FstSearch.__init__.__wrapped__(self, grammar_fst_name, hmm_fname, dur_fname)
+        self._phone_net = None
+        self._phone_opt = _A.FstOptions.defaults()
+        self._conf = None
+        self._logprob_conf_weight = 2.0            # set and never read, as in the reference
+        self._logprob_conf_hysteresis = 100.0
+
+    def set_logprob_conf_weight(self, lpw):
+        self._logprob_conf_weight = lpw
+
+    def set_logprob_conf_hysteresis(self, h):
+        self._logprob_conf_hysteresis = h
+
+    def init_search(self):
+        """both searches back to one token at their initial nodes"""
+        FstSearch.init_search(self)
+        self._conf = None
+
+    @_guard
+    def run(self):
+        if self._lna is None:
+            raise RuntimeError("Exception: LnaReaderCircular::go_to(): file not opened yet")
+        import torch
+        raw, n_models, lnabytes, frames = self._lna
+        d_lna = torch.frombuffer(bytearray(raw + bytes(16)), dtype=torch.uint8).cuda()
+        self._opt.dur_by_state = self._phone_opt.dur_by_state = 1 if self.dur_by_state else 0
+        o = _A.FstConfOptions.defaults(phone_loop=self._phone_loop, verbose=0)
+        o.grammar, o.phone = self._opt, self._phone_opt
+        self._conf = _A.fst_conf_batch(self._net, self._phone_net, [frames], d_lna, lnabytes, n_models, [0], o, dur=self._dur,
+                                       want_tokens=True)[0]
+        self._result = self._conf["grammar"]
+        self.status = self._result["status"]
+
+    def _need_conf(self):
+        if self._conf is None:
+            raise RuntimeError("Exception: run() first")
+        if not self._conf["valid"]:
+            raise RuntimeError("Exception: the search overflowed a capacity (%s, %s)" % (
+                _A.FST_STATUS_NAMES[self._conf["grammar_status"]], _A.FST_STATUS_NAMES[self._conf["phone_status"]]))
+        return self._conf
+
+    def result_and_confidence(self):
+        """(result string, confidence)"""
+        c = self._need_conf()
+        if self.verbose and self._phone_loop:
+            import sys
+            sys.stderr.write("%s:\n\tToken: %.4f\n\tPloop: %.4f\n\tEdit: %.4f\n\tBacu: %.4f\n\tTotal: %.4f\n\n" % (
+                c["text"].decode("latin-1"), c["token_conf"], c["ploop_conf"], c["edit_conf"], c["best_acu_conf"], c["confidence"]))
+        return c["text"], float(c["confidence"])
+
+
+class FstConfidenceWithPhoneLoop(FstConfidence):
+    """FstConfidenceWithPhoneLoop(grammar_fst, phone_loop_fst, hmm, dur): a second search over the phone-loop network on
+    the same acoustics; the confidence weighs the phone-loop, token, edit-distance and best-acoustics terms (1, 20, 5, 1)."""
+    _phone_loop = 1
+
+    @_guard
+    def __init__(self, grammar_fst_name, phone_loop_fst_name, hmm_fname=None, dur_fname=None):
+        FstConfidence.__init__.__wrapped__(self, grammar_fst_name, hmm_fname, dur_fname)
+        self._phone_net = _A.FstNet(phone_loop_fst_name)
+        self._ploop_logprob_weight = 0.8           # set and never read, as in the reference
+
+    def set_phone_beam(self, pb):
+        self._phone_opt.beam = pb
+
+    def set_phone_token_limit(self, ptl):
+        self._phone_opt.token_limit = int(ptl)
+
+    def set_phone_duration_scale(self, pds):
+        self._phone_opt.duration_scale = pds
+
+    def set_phone_loop_logprob_weight(self, w):
+        self._ploop_logprob_weight = w
+
+    def get_ploop_conf(self):
+        return float(self._need_conf()["ploop_conf"])
+
+    def get_token_conf(self):
+        return float(self._need_conf()["token_conf"])
+
+    def get_edit_conf(self):
+        return float(self._need_conf()["edit_conf"])
+
+    def get_best_acu_conf(self):
+        return float(self._need_conf()["best_acu_conf"])

@@ -473,6 +473,32 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_fst_decode_default_options.argtypes = [vp]
     L.aasr_fst_decode_default_options.restype = None
     L.aasr_run_fst_decode_recipe.argtypes = [vp, vp, vp, vp, cp, vp, vp]
+    L.aasr_fst_conf_default_options.argtypes = [vp]
+    L.aasr_fst_conf_default_options.restype = None
+    L.aasr_fst_conf_batch_create.argtypes = [vp, vp, vp, vp, i32, vp, pvp]
+    L.aasr_fst_conf_batch_destroy.argtypes = [vp]
+    L.aasr_fst_conf_batch_destroy.restype = None
+    L.aasr_fst_conf_batch_options.argtypes = [vp, vp]
+    L.aasr_fst_conf_batch_options.restype = None
+    L.aasr_fst_conf_batch_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp]
+    L.aasr_fst_conf_batch_frame_best_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp]
+    L.aasr_fst_conf_batch_sync.argtypes = [vp, vp, C.POINTER(i32)]
+    L.aasr_fst_conf_batch_result.argtypes = [vp, i32, vp]
+    L.aasr_fst_conf_batch_grammar.argtypes = [vp]
+    L.aasr_fst_conf_batch_grammar.restype = vp
+    L.aasr_fst_conf_batch_phone.argtypes = [vp]
+    L.aasr_fst_conf_batch_phone.restype = vp
+    L.aasr_fst_conf_batch_record.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(f), C.POINTER(f)]
+    L.aasr_fst_conf_batch_frame_best.argtypes = [vp, i32, vp, vp, i32, C.POINTER(f)]
+    L.aasr_fst_conf_remove_junk.argtypes = [cp, i32, cp, i32]
+    L.aasr_fst_conf_remove_junk.restype = i32
+    L.aasr_fst_conf_edit_distance.argtypes = [cp, i32, cp, i32]
+    L.aasr_fst_conf_edit_distance.restype = i32
+    L.aasr_fst_conf_formulas.argtypes = [vp, i32, cp, i32, cp, i32]
+    L.aasr_fst_conf_formulas.restype = None
+    L.aasr_fst_confidence_default_options.argtypes = [vp]
+    L.aasr_fst_confidence_default_options.restype = None
+    L.aasr_run_fst_confidence_recipe.argtypes = [vp, vp, vp, vp, vp, cp, vp, vp]
 
 
 def check(status: int) -> None:
@@ -2925,4 +2951,188 @@ def run_fst_decode_recipe(feat: Optional["Feat"], gmm: Optional["Gmm"], net: Fst
     st = RunStats()
     check(lib().aasr_run_fst_decode_recipe(feat._h if feat is not None else None, gmm._h if gmm is not None else None, net.handle,
                                            dur.handle if dur is not None else None, os.fsencode(recipe_path), C.byref(opts), C.byref(st)))
+    return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total, "seconds_device": st.seconds_device}
+
+
+# ---- FST decoder: confidence (FstConfidence, FstConfidenceWithPhoneLoop) --------------------------
+
+class FstConfOptions(C.Structure):
+    """aasr_fst_conf_options"""
+    _fields_ = [("grammar", FstOptions), ("phone", FstOptions), ("phone_loop", C.c_int32), ("verbose", C.c_int32)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "FstConfOptions":
+        o = cls()
+        lib().aasr_fst_conf_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+class FstConfResult(C.Structure):
+    """aasr_fst_conf_result"""
+    _fields_ = [(k, C.c_float) for k in ("confidence", "token_conf", "ploop_conf", "edit_conf", "best_acu_conf", "grammar_logprob",
+                                         "ploop_logprob", "best_final_logprob", "best_different_logprob", "best_acu_score")] + \
+               [(k, C.c_int32) for k in ("frames", "grammar_status", "phone_status", "no_final", "valid")]
+
+
+FST_CONF_FLOATS = tuple(k for k, t in FstConfResult._fields_ if t is C.c_float)
+
+
+def fst_conf_remove_junk(s: bytes) -> bytes:
+    """remove_junk of FstConfidence.cc: spaces and repeated consecutive bytes removed (the host's code)"""
+    out = C.create_string_buffer(max(1, len(s)))
+    n = lib().aasr_fst_conf_remove_junk(s, len(s), out, len(s))
+    if n < 0:
+        raise ValueError("aasr_fst_conf_remove_junk")
+    return out.raw[:n]
+
+
+def fst_conf_edit_distance(a: bytes, b: bytes) -> int:
+    return lib().aasr_fst_conf_edit_distance(a, len(a), b, len(b))
+
+
+def fst_conf_formulas(inputs: dict, n_words: int, grammar: bytes, ploop: Optional[bytes]) -> dict:
+    """The host's formulas on given raw inputs (grammar_logprob, ploop_logprob, best_final_logprob, best_different_logprob,
+    best_acu_score, frames); ploop None: the plain FstConfidence."""
+    r = FstConfResult()
+    for k, v in inputs.items():
+        setattr(r, k, v)
+    lib().aasr_fst_conf_formulas(C.byref(r), n_words, grammar, len(grammar), ploop, len(ploop) if ploop is not None else 0)
+    return {k: np.float32(getattr(r, k)) for k in FST_CONF_FLOATS}
+
+
+def _fst_inner_result(L, b, net: FstNet, u: int, T: int, want_tokens: bool) -> dict:
+    st, nw, nt = C.c_int32(), C.c_int32(), C.c_int32()
+    lp, blp, bflp = C.c_float(), C.c_float(), C.c_float()
+    words = np.zeros(T + 1, np.int32)
+    check(L.aasr_fst_batch_result(b, u, C.byref(st), C.byref(lp), C.byref(blp), C.byref(bflp), C.byref(nw), _ptr(words), len(words), C.byref(nt)))
+    r = {"status": st.value, "logprob": np.float32(lp.value), "best_logprob": np.float32(blp.value),
+         "best_final_logprob": np.float32(bflp.value), "words": tuple(int(w) for w in words[:nw.value]),
+         "text": b" ".join(net.symbols[w] for w in words[:nw.value]), "n_tokens": nt.value}
+    if want_tokens:
+        k = nt.value
+        node, tl, td = np.zeros(k, np.int32), np.zeros(k, np.float32), np.zeros(k, np.int32)
+        wb, tw = np.zeros(k + 1, np.int32), np.zeros(max(1, k * (T + 1)), np.int32)
+        check(L.aasr_fst_batch_tokens(b, u, k, _ptr(node), _ptr(tl), _ptr(td), _ptr(wb), len(tw), _ptr(tw)))
+        r["tokens"] = [(int(node[j]), np.float32(tl[j]), int(td[j]), tuple(int(w) for w in tw[wb[j]:wb[j + 1]])) for j in range(k)]
+    return r
+
+
+def _fst_conf_batch_once(net, phone_net, dur, opts, n_frames, d_lna, lnabytes, n_models, row0, stream, want_tokens) -> list:
+    L = lib()
+    n = len(n_frames)
+    T = np.ascontiguousarray(n_frames, np.int32)
+    r0 = np.ascontiguousarray(row0, np.int64)
+    n_rows = (d_lna.numel() * d_lna.element_size()) // (n_models * lnabytes)
+    b = C.c_void_p()
+    check(L.aasr_fst_conf_batch_create(net.handle, phone_net.handle if phone_net is not None else None,
+                                       dur.handle if dur is not None else None, C.byref(opts), n, _ptr(T), C.byref(b)))
+    try:
+        over = C.c_int32(0)
+        check(L.aasr_fst_conf_batch_dev(b, _ptr(d_lna), lnabytes, n_models, n_rows, _ptr(r0), stream))
+        check(L.aasr_fst_conf_batch_sync(b, stream, C.byref(over)))
+        resolved = FstConfOptions()
+        L.aasr_fst_conf_batch_options(b, C.byref(resolved))
+        inner = [(L.aasr_fst_conf_batch_grammar(b), net, "grammar"), (L.aasr_fst_conf_batch_phone(b), phone_net, "phone")]
+        out = []
+        for u in range(n):
+            cr = FstConfResult()
+            check(L.aasr_fst_conf_batch_result(b, u, C.byref(cr)))
+            r = {k: np.float32(getattr(cr, k)) for k in FST_CONF_FLOATS}
+            r.update(frames=cr.frames, grammar_status=cr.grammar_status, phone_status=cr.phone_status, no_final=cr.no_final,
+                     valid=cr.valid, options=resolved, reran=False)
+            if not cr.valid:
+                r["confidence"] = None
+            for k, (h, nt, name) in enumerate(inner):
+                if not h:
+                    r[name] = None
+                    continue
+                r[name] = _fst_inner_result(L, h, nt, u, int(T[u]), want_tokens)
+                hf, nw, hd = C.c_int32(), C.c_int32(), C.c_int32()
+                bf, bd = C.c_float(), C.c_float()
+                check(L.aasr_fst_conf_batch_record(b, u, k, C.byref(hf), C.byref(nw), C.byref(hd), C.byref(bf), C.byref(bd)))
+                r[name]["record"] = {"has_final": hf.value, "n_words": nw.value, "has_different": hd.value,
+                                     "best_final_logprob": np.float32(bf.value), "best_different_logprob": np.float32(bd.value)}
+            r["text"] = r["grammar"]["text"]
+            out.append(r)
+        return out
+    finally:
+        L.aasr_fst_conf_batch_destroy(b)
+
+
+def fst_conf_batch(net: FstNet, phone_net: Optional[FstNet], n_frames: list, d_lna, lnabytes: int, n_models: int, row0: list,
+                   opts: Optional[FstConfOptions] = None, dur: Optional[FstDurations] = None, stream: int = 0,
+                   want_tokens: bool = False, rerun: bool = True) -> list:
+    """The confidence of a batch of utterances on the device (aasr_fst_conf_batch_*): the grammar search, with
+    opts.phone_loop the search over phone_net on the same acoustics, the frame-best sums and the token records.  Per
+    utterance a dict: the ten floats of aasr_fst_conf_result (confidence None when a search overflowed), frames,
+    grammar_status, phone_status, no_final, valid, text, and `grammar` / `phone` (None without a phone loop): the search's
+    result as fst_batch gives it plus `record`, the device's token record.  With rerun the utterances that overflowed a
+    capacity run once more with every capacity of both searches doubled (`reran`)."""
+    opts = opts or FstConfOptions.defaults()
+    out = _fst_conf_batch_once(net, phone_net, dur, opts, n_frames, d_lna, lnabytes, n_models, row0, stream, want_tokens)
+    again = [u for u, r in enumerate(out) if not r["valid"]]
+    if rerun and again:
+        o2 = FstConfOptions()
+        C.memmove(C.byref(o2), C.byref(out[again[0]]["options"]), C.sizeof(o2))
+        for o in (o2.grammar, o2.phone):
+            o.cap_candidates, o.cap_recomb, o.cap_history = 2 * o.cap_candidates, 2 * o.cap_recomb, 2 * o.cap_history
+        second = _fst_conf_batch_once(net, phone_net, dur, o2, [n_frames[u] for u in again], d_lna, lnabytes, n_models,
+                                      [row0[u] for u in again], stream, want_tokens)
+        for u, r in zip(again, second):
+            r["reran"] = True
+            out[u] = r
+    return out
+
+
+def fst_frame_best(n_frames: list, d_lna, lnabytes: int, n_models: int, row0: list, net: FstNet, stream: int = 0):
+    """The frame-best pass alone (aasr_fst_conf_batch_frame_best_dev): per utterance (float32 [frames] of the frames' best
+    acoustic values, their float32 sum in frame order).  net: any network (the batch is made over it and not searched)."""
+    L = lib()
+    n = len(n_frames)
+    T = np.ascontiguousarray(n_frames, np.int32)
+    r0 = np.ascontiguousarray(row0, np.int64)
+    n_rows = (d_lna.numel() * d_lna.element_size()) // (n_models * lnabytes)
+    b = C.c_void_p()
+    opts = FstConfOptions.defaults()
+    check(L.aasr_fst_conf_batch_create(net.handle, None, None, C.byref(opts), n, _ptr(T), C.byref(b)))
+    try:
+        check(L.aasr_fst_conf_batch_frame_best_dev(b, _ptr(d_lna), lnabytes, n_models, n_rows, _ptr(r0), stream))
+        out = []
+        for u in range(n):
+            best, s = np.zeros(int(T[u]), np.float32), C.c_float()
+            check(L.aasr_fst_conf_batch_frame_best(b, u, stream, _ptr(best), len(best), C.byref(s)))
+            out.append((best, np.float32(s.value)))
+        return out
+    finally:
+        L.aasr_fst_conf_batch_destroy(b)
+
+
+class FstConfidenceOptions(C.Structure):
+    """aasr_fst_confidence_options"""
+    _fields_ = [("decode", FstDecodeOptions), ("phone", FstOptions), ("phone_loop", C.c_int32)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "FstConfidenceOptions":
+        o = cls()
+        lib().aasr_fst_confidence_default_options(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+
+def run_fst_confidence_recipe(feat: Optional["Feat"], gmm: Optional["Gmm"], net: FstNet, phone_net: Optional[FstNet], recipe_path: str,
+                              out: str, opts: Optional[FstConfidenceOptions] = None, dur: Optional[FstDurations] = None,
+                              speakers: Optional["SpeakerConfig"] = None) -> dict:
+    """fst_decode --confidence (aasr_run_fst_confidence_recipe): as run_fst_decode_recipe, a confidence behind every
+    log-probability; opts.phone_loop is set from phone_net."""
+    opts = opts or FstConfidenceOptions.defaults()
+    opts.decode.out = os.fsencode(out)
+    opts.decode.speakers = speakers._h if speakers is not None else None
+    opts.phone_loop = 1 if phone_net is not None else 0
+    st = RunStats()
+    check(lib().aasr_run_fst_confidence_recipe(feat._h if feat is not None else None, gmm._h if gmm is not None else None, net.handle,
+                                               phone_net.handle if phone_net is not None else None,
+                                               dur.handle if dur is not None else None, os.fsencode(recipe_path), C.byref(opts), C.byref(st)))
     return {"utterances": st.utterances, "frames": st.frames, "seconds_total": st.seconds_total, "seconds_device": st.seconds_device}

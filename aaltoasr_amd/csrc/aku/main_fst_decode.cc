@@ -5,8 +5,13 @@
 //              [--duration-scale F] [--transition-scale F] -r RECIPE -o OUT
 //              ( (-b BASE | -g -m -p) -c CFG [-S SPKC] [--lnabytes 2|4]  |  --lna-files )
 //              [--cap-candidates N] [--cap-recomb N] [--cap-history N]
+//              [--confidence [--phone-loop FST [--phone-beam F] [--phone-token-limit N] [--phone-duration-scale F]]]
 //              [-B n -I k] [-G utterances] [-i level] [--device N]
 //
+// --confidence: the reference's FstConfidence (with --phone-loop: FstConfidenceWithPhoneLoop, a second search over the
+// phone-loop network on the same acoustics; aasr_run_fst_confidence_recipe).  A line is then
+// `path logprob confidence words... [status]`, both numbers as %.9g; at -i 1 the reference's verbose block goes to stderr
+// per utterance.  A --phone-* option without --confidence is refused.
 // --lna-files: the recipe's lna= files (1-, 2- or 4-byte) are uploaded and searched -- what the reference's decoder does;
 // no model and no feature configuration.  Engine mode: the recipe's audio= through the feature chain and the score + LNA
 // step into the search, all on the device (--lnabytes 2 by default: precisely the values phone_probs would have
@@ -51,6 +56,11 @@ int main(int argc, char *argv[]) {
     ('\0', "cap-candidates=INT", "arg", "0", "candidates per frame and utterance (0: derived)")
     ('\0', "cap-recomb=INT", "arg", "0", "recombination table entries, a power of two (0: derived)")
     ('\0', "cap-history=INT", "arg", "0", "history table entries, a power of two (0: derived)")
+    ('\0', "confidence", "", "", "write a confidence in [0, 1] behind the log-probability")
+    ('\0', "phone-loop=FILE", "arg", "", "phone-loop network of the confidence (#FSTBasic MaxPlus)")
+    ('\0', "phone-beam=FLOAT", "arg", "2600", "beam of the phone-loop search")
+    ('\0', "phone-token-limit=INT", "arg", "5000", "token limit of the phone-loop search")
+    ('\0', "phone-duration-scale=FLOAT", "arg", "3", "duration scale of the phone-loop search")
     ('i', "info=INT", "arg", "0", "info level")
     ('\0', "device=INT", "arg", "-1", "GPU ordinal (default: the first visible device)");
   config.default_parse(argc, argv);
@@ -62,6 +72,11 @@ int main(int argc, char *argv[]) {
   if (lna_files && model_opts) die("fst_decode: --lna-files takes no model and no feature configuration");
   if (lna_files && config["lnabytes"].specified) die("fst_decode: --lnabytes belongs to engine mode; an LNA file states its own");
   if (lna_files && config["speakers"].specified) die("fst_decode: -S belongs to engine mode");
+  const bool confidence = config["confidence"].specified;
+  for (const char *name : {"phone-loop", "phone-beam", "phone-token-limit", "phone-duration-scale"}) {
+    if (config[name].specified && !confidence) die(std::string("fst_decode: --") + name + " without --confidence");
+    if (config[name].specified && !config["phone-loop"].specified) die(std::string("fst_decode: --") + name + " without --phone-loop");
+  }
   if (config["dur-by-state"].specified && !config["dur"].specified) die("fst_decode: --dur-by-state without --dur");
   if (config["batch"].specified != config["bindex"].specified) die("Must give both --batch and --bindex");
   const int engine_bytes = config["lnabytes"].get_int();
@@ -83,6 +98,14 @@ int main(int argc, char *argv[]) {
   if (opt.cap_candidates < 0 || opt.cap_recomb < 0 || opt.cap_history < 0) die("fst_decode: a capacity must not be negative");
   if ((opt.cap_recomb & (opt.cap_recomb - 1)) || (opt.cap_history & (opt.cap_history - 1)))
     die("fst_decode: --cap-recomb and --cap-history are powers of two");
+  aasr_fst_options phone;
+  aasr_fst_default_options(&phone);
+  phone.beam = config["phone-beam"].get_float();
+  phone.token_limit = config["phone-token-limit"].get_int();
+  phone.duration_scale = config["phone-duration-scale"].get_float();
+  phone.dur_by_state = opt.dur_by_state;
+  if (!(phone.beam >= 0)) die("fst_decode: the phone beam must not be negative");
+  if (phone.token_limit < 0) die("fst_decode: the phone token limit must not be negative");
   std::string gk, mc, ph, cfg_text;
   if (!lna_files) {
     if (!config["config"].specified) die("fst_decode: engine mode needs --config (or give --lna-files)");
@@ -97,6 +120,9 @@ int main(int argc, char *argv[]) {
   }
   aasr_fstnet *net = nullptr;
   if (aasr_fstnet_create_from_file(config["fst"].get_str().c_str(), &net) != AASR_OK) die(std::string("fst_decode: ") + aasr_last_error());
+  aasr_fstnet *phone_net = nullptr;
+  if (config["phone-loop"].specified && aasr_fstnet_create_from_file(config["phone-loop"].get_str().c_str(), &phone_net) != AASR_OK)
+    die(std::string("fst_decode: ") + aasr_last_error());
   aasr_fst_durations *dur = nullptr;
   if (config["dur"].specified && aasr_fst_durations_read(config["dur"].get_str().c_str(), &dur) != AASR_OK)
     die(std::string("fst_decode: ") + aasr_last_error());
@@ -135,13 +161,24 @@ int main(int argc, char *argv[]) {
   run.out = out_path.c_str();
   aasr_run_stats st;
   memset(&st, 0, sizeof st);
-  if (aasr_run_fst_decode_recipe(feat, gmm, net, dur, config["recipe"].get_str().c_str(), &run, &st) != AASR_OK)
-    die(std::string("fst_decode: ") + aasr_last_error());
+  aasr_status status;
+  if (confidence) {
+    aasr_fst_confidence_options crun;
+    aasr_fst_confidence_default_options(&crun);
+    crun.decode = run;
+    crun.phone = phone;
+    crun.phone_loop = phone_net != nullptr;
+    status = aasr_run_fst_confidence_recipe(feat, gmm, net, phone_net, dur, config["recipe"].get_str().c_str(), &crun, &st);
+  } else {
+    status = aasr_run_fst_decode_recipe(feat, gmm, net, dur, config["recipe"].get_str().c_str(), &run, &st);
+  }
+  if (status != AASR_OK) die(std::string("fst_decode: ") + aasr_last_error());
   if (run.info > 0)
     fprintf(stderr, "fst_decode: %lld utterances, %lld frames, %.3f s (%.3f s from upload to result)\n", (long long)st.utterances,
             (long long)st.frames, st.seconds_total, st.seconds_device);
   if (spk) aasr_spkc_destroy(spk);
   if (dur) aasr_fst_durations_destroy(dur);
+  if (phone_net) aasr_fstnet_destroy(phone_net);
   aasr_fstnet_destroy(net);
   if (gmm) aasr_gmm_destroy(gmm);
   if (feat) aasr_feat_destroy(feat);

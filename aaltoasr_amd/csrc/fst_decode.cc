@@ -3,6 +3,8 @@
 // settings, ONE score + LNA step over the group's frames (aasr_gmm_score_lna_dev: what the phone_probs driver runs per
 // block) and one search launch (aasr_fst_batch_*) that reads the step's device buffer in place -- the LNA values of
 // engine mode never leave the device.  With lna_files the recipe's lna= files are uploaded instead.
+// aasr_run_fst_confidence_recipe is the same loop with a confidence batch (aasr_fst_conf_batch_*) per group: the group's
+// LNA device buffer feeds the grammar search, the phone-loop search and the frame-best pass.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,11 +32,16 @@ struct Line {
   int32_t status = 0;
   float logprob = -1;
   std::vector<int32_t> words;
+  aasr_fst_conf_result conf{};  // --confidence
 };
 
 struct BatchGuard {
   aasr_fst_batch *b = nullptr;
   ~BatchGuard() { aasr_fst_batch_destroy(b); }
+};
+struct ConfBatchGuard {
+  aasr_fst_conf_batch *b = nullptr;
+  ~ConfBatchGuard() { aasr_fst_conf_batch_destroy(b); }
 };
 
 void ok(aasr_status s) {
@@ -67,9 +74,67 @@ int32_t run_batch(const aasr_fstnet *net, const aasr_fst_durations *dur, const a
   return over;
 }
 
+// the same over a confidence batch; at info >= 1 the reference's verbose block per utterance on stderr
+int32_t run_conf_batch(const aasr_fstnet *net, const aasr_fstnet *phone_net, const aasr_fst_durations *dur, const aasr_fst_conf_options &opt,
+                       const std::vector<int32_t> &frames, const std::vector<int64_t> &row0_all, const std::vector<size_t> &which,
+                       const uint8_t *d_lna, int64_t n_rows, int lnabytes, int n_models, hipStream_t stream, std::vector<Line> &out,
+                       aasr_fst_conf_options *resolved) {
+  std::vector<int32_t> T;
+  std::vector<int64_t> row0;
+  for (size_t i : which) {
+    T.push_back(frames[i]);
+    row0.push_back(row0_all[i]);
+  }
+  ConfBatchGuard g;
+  int32_t over = 0;
+  ok(aasr_fst_conf_batch_create(net, phone_net, dur, &opt, (int32_t)which.size(), T.data(), &g.b));
+  ok(aasr_fst_conf_batch_dev(g.b, d_lna, lnabytes, n_models, n_rows, row0.data(), stream));
+  ok(aasr_fst_conf_batch_sync(g.b, stream, &over));
+  aasr_fst_conf_batch_options(g.b, resolved);
+  for (size_t k = 0; k < which.size(); k++) {
+    Line &l = out[which[k]];
+    int32_t n = 0;
+    l.words.assign((size_t)T[k] + 1, 0);
+    ok(aasr_fst_batch_result(aasr_fst_conf_batch_grammar(g.b), (int32_t)k, &l.status, &l.logprob, nullptr, nullptr, &n, l.words.data(),
+                             (int32_t)l.words.size(), nullptr));
+    l.words.resize((size_t)n);
+    ok(aasr_fst_conf_batch_result(g.b, (int32_t)k, &l.conf));
+  }
+  return over;
+}
+
+void double_capacities(aasr_fst_options &o) {
+  o.cap_candidates *= 2;
+  o.cap_recomb *= 2;
+  o.cap_history *= 2;
+}
+
+aasr_status run_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur, const char *recipe_path,
+                       const aasr_fst_decode_options *opt, const aasr_fstnet *phone_net, const aasr_fst_confidence_options *conf,
+                       aasr_run_stats *stats);
+
 }  // namespace
 
 extern "C" {
+
+void aasr_fst_confidence_default_options(aasr_fst_confidence_options *o) {
+  if (!o) return;
+  *o = aasr_fst_confidence_options();
+  aasr_fst_decode_default_options(&o->decode);
+  aasr_fst_default_options(&o->phone);
+}
+
+aasr_status aasr_run_fst_confidence_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fstnet *phone_net,
+                                           const aasr_fst_durations *dur, const char *recipe_path,
+                                           const aasr_fst_confidence_options *opt, aasr_run_stats *stats) {
+  if (!opt) return guarded([&] { raise(AASR_ERR_INVALID, "aasr_run_fst_confidence_recipe: null argument"); });
+  return run_recipe(feat, gmm, net, dur, recipe_path, &opt->decode, phone_net, opt, stats);
+}
+
+aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur,
+                                       const char *recipe_path, const aasr_fst_decode_options *opt, aasr_run_stats *stats) {
+  return run_recipe(feat, gmm, net, dur, recipe_path, opt, nullptr, nullptr, stats);
+}
 
 void aasr_fst_decode_default_options(aasr_fst_decode_options *o) {
   if (!o) return;
@@ -79,8 +144,13 @@ void aasr_fst_decode_default_options(aasr_fst_decode_options *o) {
   o->group = 256;
 }
 
-aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur,
-                                       const char *recipe_path, const aasr_fst_decode_options *opt, aasr_run_stats *stats) {
+}  // extern "C"
+
+namespace {
+
+aasr_status run_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur, const char *recipe_path,
+                       const aasr_fst_decode_options *opt, const aasr_fstnet *phone_net, const aasr_fst_confidence_options *conf,
+                       aasr_run_stats *stats) {
   return guarded([&] {
     if (!net || !recipe_path || !opt || !opt->out) raise(AASR_ERR_INVALID, "aasr_run_fst_decode_recipe: null argument");
     const bool engine = !opt->lna_files;
@@ -88,6 +158,16 @@ aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aas
     if (!engine && opt->speakers) raise(AASR_ERR_INVALID, "fst_decode: a speaker configuration belongs to engine mode");
     if (engine && opt->lnabytes != 2 && opt->lnabytes != 4) raise(AASR_ERR_INVALID, "Invalid number of LNA bytes");
     if (opt->group < 1) raise(AASR_ERR_INVALID, "fst_decode: the group must hold at least 1 utterance");
+    if (conf && conf->phone_loop && !phone_net) raise(AASR_ERR_INVALID, "fst_decode: a phone loop without a phone-loop network");
+    const int32_t max_pdf = std::max(aasr_fstnet_max_pdf(net), conf && conf->phone_loop ? aasr_fstnet_max_pdf(phone_net) : -1);
+    aasr_fst_conf_options copt;
+    aasr_fst_conf_default_options(&copt);
+    if (conf) {
+      copt.grammar = opt->fst;
+      copt.phone = conf->phone;
+      copt.phone_loop = conf->phone_loop;
+      copt.verbose = opt->info > 0;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const std::vector<RecipeInfo> infos = read_recipe_file(recipe_path, opt->num_batches, opt->batch_index, false);
     for (const RecipeInfo &u : infos) {
@@ -96,9 +176,8 @@ aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aas
     }
     if (engine) {
       check_feature_dim(gmm, feat);
-      if (aasr_fstnet_max_pdf(net) >= aasr_gmm_num_states(gmm))
-        raise(AASR_ERR_INVALID, "fst_decode: the network names pdf %d, the model has %d states", aasr_fstnet_max_pdf(net),
-              aasr_gmm_num_states(gmm));
+      if (max_pdf >= aasr_gmm_num_states(gmm))
+        raise(AASR_ERR_INVALID, "fst_decode: the network names pdf %d, the model has %d states", max_pdf, aasr_gmm_num_states(gmm));
     }
     require_device();
     const bool to_stdout = strcmp(opt->out, "-") == 0;
@@ -212,33 +291,47 @@ aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aas
           row0[i + 1] = row0[i] + frames[i];
           all.insert(all.end(), image.begin() + 5, image.begin() + 5 + (long)((size_t)frames[i] * row));
         }
-        if (aasr_fstnet_max_pdf(net) >= n_models)
-          raise(AASR_ERR_INVALID, "fst_decode: the network names pdf %d, the acoustics have %d models", aasr_fstnet_max_pdf(net), n_models);
+        if (max_pdf >= n_models)
+          raise(AASR_ERR_INVALID, "fst_decode: the network names pdf %d, the acoustics have %d models", max_pdf, n_models);
         d_lna.ensure(std::max<size_t>(16, all.size()));
         if (!all.empty()) AASR_HIP(hipMemcpy(d_lna.p, all.data(), all.size(), hipMemcpyHostToDevice));
       }
       std::vector<Line> result(n);
       std::vector<size_t> which(n);
       for (size_t i = 0; i < n; i++) which[i] = i;
-      aasr_fst_options resolved;
-      if (run_batch(net, dur, opt->fst, frames, row0, which, d_lna.p, row0[n], lnabytes, n_models, stream, result, &resolved) > 0) {
-        which.clear();
-        for (size_t i = 0; i < n; i++)
-          if (result[i].status >= AASR_FST_OVERFLOW_CANDIDATES) which.push_back(i);
-        resolved.cap_candidates *= 2;
-        resolved.cap_recomb *= 2;
-        resolved.cap_history *= 2;
-        fprintf(stderr, "fst_decode: %zu utterances overflowed a capacity, running them again with twice as much\n", which.size());
-        aasr_fst_options again;
-        run_batch(net, dur, resolved, frames, row0, which, d_lna.p, row0[n], lnabytes, n_models, stream, result, &again);
+      if (conf) {
+        aasr_fst_conf_options resolved;
+        if (run_conf_batch(net, phone_net, dur, copt, frames, row0, which, d_lna.p, row0[n], lnabytes, n_models, stream, result, &resolved) > 0) {
+          which.clear();
+          for (size_t i = 0; i < n; i++)
+            if (!result[i].conf.valid) which.push_back(i);
+          double_capacities(resolved.grammar);
+          double_capacities(resolved.phone);
+          fprintf(stderr, "fst_decode: %zu utterances overflowed a capacity, running them again with twice as much\n", which.size());
+          aasr_fst_conf_options again;
+          run_conf_batch(net, phone_net, dur, resolved, frames, row0, which, d_lna.p, row0[n], lnabytes, n_models, stream, result, &again);
+        }
+      } else {
+        aasr_fst_options resolved;
+        if (run_batch(net, dur, opt->fst, frames, row0, which, d_lna.p, row0[n], lnabytes, n_models, stream, result, &resolved) > 0) {
+          which.clear();
+          for (size_t i = 0; i < n; i++)
+            if (result[i].status >= AASR_FST_OVERFLOW_CANDIDATES) which.push_back(i);
+          double_capacities(resolved);
+          fprintf(stderr, "fst_decode: %zu utterances overflowed a capacity, running them again with twice as much\n", which.size());
+          aasr_fst_options again;
+          run_batch(net, dur, resolved, frames, row0, which, d_lna.p, row0[n], lnabytes, n_models, stream, result, &again);
+        }
       }
       device_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count();
       total_frames += row0[n];
       for (size_t i = 0; i < n; i++) {
         const RecipeInfo &u = infos[g0 + i];
         fprintf(out, "%s %.9g", engine ? u.audio_path.c_str() : u.lna_path.c_str(), (double)result[i].logprob);
+        if (conf) fprintf(out, " %.9g", (double)result[i].conf.confidence);
         for (int32_t w : result[i].words) fprintf(out, " %s", aasr_fstnet_symbol(net, w));
-        if (result[i].status != AASR_FST_OK) fprintf(out, " %s", STATUS[result[i].status]);
+        const int32_t status = result[i].status != AASR_FST_OK || !conf ? result[i].status : result[i].conf.phone_status;
+        if (status != AASR_FST_OK) fprintf(out, " %s", STATUS[status]);
         fprintf(out, "\n");
       }
       fflush(out);
@@ -247,4 +340,4 @@ aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aas
   });
 }
 
-}  // extern "C"
+}  // namespace

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "fst_conf.h"
 #include "fst_net.h"
 #include "fst_search.h"
 
@@ -45,6 +46,17 @@ int32_t pow2_at_least(int64_t v) {
 }
 
 }  // namespace
+
+namespace aasr {
+
+const FstParams &fst_batch_params(const aasr_fst_batch *b) { return b->p; }
+
+void fst_decode_table(int32_t lnabytes, std::vector<float> &dec) {  // LnaReaderCircular.cc:180-198, the division in double
+  dec.resize(lnabytes == 2 ? 65536 : 256);
+  for (size_t i = 0; i < dec.size(); i++) dec[i] = lnabytes == 2 ? (float)((double)(int)i / -1820.0) : (float)((double)(int)i / -24.0);
+}
+
+}  // namespace aasr
 
 extern "C" {
 
@@ -248,9 +260,9 @@ aasr_status aasr_fst_batch_dev(aasr_fst_batch *b, const void *d_lna, int32_t lna
     }
     if (b->n == 0) return;
     if (!d_lna && n_rows > 0) raise(AASR_ERR_INVALID, "aasr_fst_batch_dev: null acoustics");
-    if (lnabytes != 4 && b->decode_bytes != lnabytes) {  // LnaReaderCircular.cc:180-198, the division in double
-      std::vector<float> dec(lnabytes == 2 ? 65536 : 256);
-      for (size_t i = 0; i < dec.size(); i++) dec[i] = lnabytes == 2 ? (float)((double)(int)i / -1820.0) : (float)((double)(int)i / -24.0);
+    if (lnabytes != 4 && b->decode_bytes != lnabytes) {
+      std::vector<float> dec;
+      fst_decode_table(lnabytes, dec);
       b->d_decode.upload(dec.data(), dec.size());
       b->decode_bytes = lnabytes;
     }

@@ -1707,8 +1707,9 @@ int32_t aasr_dur_est_fit_gamma(const int32_t *hist, int32_t n, double *a, double
  * token pass over a "#FSTBasic MaxPlus" network with state indices on the arcs, a beam, a token limit and recombination
  * on (node, word history).  One workgroup per utterance, a batch per launch (csrc/fst_search.h).  The arithmetic is
  * the reference's float operations in its order; tools/fst_restate.py is the same in NumPy and the yardstick of the tests.
- * Out of scope: FstConfidence, FstWithPhoneLoop, TokenPassSearch and n-grams, lattices and n-best lists, epsilon closure
- * (the reference has none: a token crosses one arc per frame), one utterance over several workgroups. */
+ * Confidence scores (FstConfidence, FstConfidenceWithPhoneLoop): the block "FST decoder: confidence" below.
+ * Out of scope: TokenPassSearch and n-grams, lattices and n-best lists, epsilon closure (the reference has none: a token
+ * crosses one arc per frame), one utterance over several workgroups. */
 typedef struct aasr_fstnet aasr_fstnet;
 /* Fst::read (Fst.cc:10-103) with its messages in aasr_last_error() (AASR_ERR_INVALID; AASR_ERR_IO: cannot open): "Unknown
  * header", "Too few fields", "Too many fields for I:" / "F:", "Weird number of fields for T:", "Weird type indicator:",
@@ -1808,6 +1809,101 @@ typedef struct aasr_fst_decode_options {
 void aasr_fst_decode_default_options(aasr_fst_decode_options *opt);
 aasr_status aasr_run_fst_decode_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur,
                                        const char *recipe_path, const aasr_fst_decode_options *opt, aasr_run_stats *stats);
+
+/* ---- FST decoder: confidence (the reference's FstConfidence and FstConfidenceWithPhoneLoop) -----------------------------
+ * A grammar search, optionally a second search over a phone-loop network on the same acoustics, the best acoustic value
+ * of every frame summed per utterance, and the best surviving hypothesis whose words differ from the winner's
+ * (csrc/fst_conf.h).  Neither LNA values nor token or history tables leave the device for a confidence.  All float
+ * operations in the reference's order (decoder/src/FstConfidence.cc), frames an int converted to float:
+ *   ploop_conf    = min(1, 1 - 0.25 * (-grammar_logprob + ploop_logprob) / frames)
+ *   best_acu_conf = 1.5 - 0.25 * (-best_final_logprob + best_acu_score) / frames
+ *   token_conf    = max(0, min(1, 0.2 - 5 * (-best_final_logprob + best_different_logprob) / frames)); -9999999.9f when
+ *                   the best end-node token has no words
+ *   edit_conf     = max(0, 1 - ldist / len): byte Levenshtein distance of the two result strings without spaces and
+ *                   repeated consecutive bytes, len of the cleaned grammar string (0: IEEE division, a NaN gives 0)
+ *   confidence    = (min(1, ploop) + 20 min(1, token) + 5 min(1, edit) + min(1, best_acu)) / 27
+ * best_acu_score: the float sum in frame order of every frame's maximum over ALL n_models values (start -999999999.9f,
+ * replaced on strict >).  best_different_logprob: the best log-probability among the surviving tokens whose word
+ * sequence differs from the best end-node token's, -9999999.9f without one.
+ * phone_loop 0 is the reference's plain FstConfidence: no second search, best_acu_score stays 0 (the reference computes
+ * the frame maximum there and discards it; here the pass is not run), confidence = 0.5 * (token_conf + best_acu_conf)
+ * (the product in double, stored to float); ploop_logprob is -1, ploop_conf and edit_conf are 0.
+ * Where the reference is undefined or only noisy:
+ *   no end-node token    the reference reads an uninitialised float.  Here best_final_logprob is -9999999.9f (what
+ *                        get_best_final_token_logprob returns), token_conf is -9999999.9f, and no_final is set.
+ *   zero frames          the IEEE result of the float division is kept.
+ *   debug lines          the reference's unconditional "Ldist", "pl_lp" and "Emptiness" lines are not printed; its verbose
+ *                        block goes to stderr from aasr_fst_conf_batch_result when options.verbose is not 0.
+ *   unused members       the phone-loop log-probability weight, the log-probability confidence weight and hysteresis are
+ *                        set and never read in the reference: they have no counterpart here (the Python classes keep
+ *                        the setters). */
+typedef struct aasr_fst_conf_options {
+  aasr_fst_options grammar;
+  aasr_fst_options phone;  /* the phone-loop search: its own beam, token limit, scales and capacities */
+  int32_t phone_loop;      /* 0: FstConfidence; 1: FstConfidenceWithPhoneLoop (needs a phone-loop network) */
+  int32_t verbose;
+} aasr_fst_conf_options;
+/* both searches 2600 / 5000 / 3 / 1, phone_loop 0, verbose 0 */
+void aasr_fst_conf_default_options(aasr_fst_conf_options *opt);
+
+typedef struct aasr_fst_conf_result {
+  float confidence, token_conf, ploop_conf, edit_conf, best_acu_conf;
+  float grammar_logprob, ploop_logprob, best_final_logprob, best_different_logprob, best_acu_score;
+  int32_t frames;
+  int32_t grammar_status, phone_status; /* AASR_FST_*; phone_status AASR_FST_OK without a phone loop */
+  int32_t no_final;                     /* the grammar search left no token at an end node */
+  int32_t valid;                        /* 0: a search overflowed a capacity, the floats above are 0 */
+} aasr_fst_conf_result;
+
+typedef struct aasr_fst_conf_batch aasr_fst_conf_batch;
+/* One aasr_fst_batch per network (phone_net NULL without a phone loop), the frame-best and token-record buffers.  Bad
+ * options (either search's), a NULL grammar and phone_loop without a network are AASR_ERR_INVALID before a device is
+ * looked for.  The networks and dur must outlive the batch. */
+aasr_status aasr_fst_conf_batch_create(const aasr_fstnet *grammar_net, const aasr_fstnet *phone_net, const aasr_fst_durations *dur,
+                                       const aasr_fst_conf_options *opt, int32_t n_utt, const int32_t *n_frames,
+                                       aasr_fst_conf_batch **out);
+void aasr_fst_conf_batch_destroy(aasr_fst_conf_batch *b);
+/* the options with both searches' derived capacities filled in (what a rerun doubles) */
+void aasr_fst_conf_batch_options(const aasr_fst_conf_batch *b, aasr_fst_conf_options *out);
+/* Queues on `stream`: the grammar search, the phone-loop search, the frame-best pass with its sums, and the token records
+ * of both searches.  Arguments as aasr_fst_batch_dev; d_lna must be aligned to lnabytes. */
+aasr_status aasr_fst_conf_batch_dev(aasr_fst_conf_batch *b, const void *d_lna, int32_t lnabytes, int32_t n_models, int64_t n_rows,
+                                    const int64_t *row0, void *stream);
+/* the frame-best pass and its sums alone (what aasr_fst_conf_batch_dev queues for them); also without a phone loop */
+aasr_status aasr_fst_conf_batch_frame_best_dev(aasr_fst_conf_batch *b, const void *d_lna, int32_t lnabytes, int32_t n_models,
+                                               int64_t n_rows, const int64_t *row0, void *stream);
+/* Waits, fetches the per-utterance records and both searches' results, and computes the confidences on the host */
+aasr_status aasr_fst_conf_batch_sync(aasr_fst_conf_batch *b, void *stream, int32_t *n_overflow);
+aasr_status aasr_fst_conf_batch_result(const aasr_fst_conf_batch *b, int32_t u, aasr_fst_conf_result *out);
+/* the inner batches, for aasr_fst_batch_result and aasr_fst_batch_tokens; phone: NULL without a phone loop */
+aasr_fst_batch *aasr_fst_conf_batch_grammar(aasr_fst_conf_batch *b);
+aasr_fst_batch *aasr_fst_conf_batch_phone(aasr_fst_conf_batch *b);
+/* The device's record of utterance u for the grammar search (phone 0) or the phone-loop search (phone 1), after a sync:
+ * whether a token stands at an end node, the words of the best such token, whether a token with other words survives,
+ * and the two log-probabilities (-9999999.9f where there is none).  Any pointer may be NULL. */
+aasr_status aasr_fst_conf_batch_record(const aasr_fst_conf_batch *b, int32_t u, int32_t phone, int32_t *has_final, int32_t *n_words,
+                                       int32_t *has_different, float *best_final_logprob, float *best_different_logprob);
+/* the frame-best values of utterance u [n_frames[u]] and their sum, copied from the device after a frame-best pass */
+aasr_status aasr_fst_conf_batch_frame_best(aasr_fst_conf_batch *b, int32_t u, void *stream, float *best, int32_t cap, float *sum);
+/* The host's part alone (no device): the cleaned string of remove_junk into out (cap bytes, -> its length or -1), the
+ * byte edit distance, and the formulas on given inputs (grammar, ploop: the result strings, ploop NULL: plain). */
+int32_t aasr_fst_conf_remove_junk(const char *s, int32_t n, char *out, int32_t cap);
+int32_t aasr_fst_conf_edit_distance(const char *a, int32_t na, const char *b, int32_t nb);
+void aasr_fst_conf_formulas(aasr_fst_conf_result *r, int32_t n_words, const char *grammar, int32_t n_grammar, const char *ploop,
+                            int32_t n_ploop);
+
+/* fst_decode --confidence over a recipe: the group loop of aasr_run_fst_decode_recipe with a confidence batch per group;
+ * the group's LNA device buffer feeds both searches and the frame-best pass.  Output lines: path, log-probability and
+ * confidence as %.9g, the words, and a trailing status word when a search's status is not OK (the grammar's first). */
+typedef struct aasr_fst_confidence_options {
+  aasr_fst_decode_options decode;  /* decode.fst is the grammar search */
+  aasr_fst_options phone;
+  int32_t phone_loop;
+} aasr_fst_confidence_options;
+void aasr_fst_confidence_default_options(aasr_fst_confidence_options *opt);
+aasr_status aasr_run_fst_confidence_recipe(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fstnet *phone_net,
+                                           const aasr_fst_durations *dur, const char *recipe_path,
+                                           const aasr_fst_confidence_options *opt, aasr_run_stats *stats);
 
 #ifdef __cplusplus
 }
