@@ -19,6 +19,12 @@ the empty result where the reference indexes an empty vector.  The confidence cl
 confidence", states the formulas and what is chosen where the reference is undefined (no end-node token, zero frames); the
 reference's unconditional debug lines are not printed, its verbose block is when `verbose` is not 0.
 `sys.path.insert(0, ".../aaltoasr_amd"); import FstDecoder` is the drop-in spelling.
+
+lna_open_fd(fd, size) reads a descriptor -- a pipe that is still being written -- instead of a file: run() reads it in
+blocks as they arrive and feeds each block to a one-session streaming search (capi.FstStream, include/aasr.h "FST
+decoder: streaming sessions"), which is the batch search of the same frames bit for bit.  A descriptor has no size to
+derive the search's tables from: they are sized for STREAM_MAX_FRAMES frames (module level, settable before run(); a longer
+input is refused when it gets there).  STREAM_BLOCK_FRAMES is the most frames one feed takes.
 """
 import os
 import struct
@@ -29,6 +35,10 @@ except ImportError:  # imported as a top-level module named FstDecoder
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from aaltoasr_amd import capi as _A
+
+
+STREAM_MAX_FRAMES = 7500      # lna_open_fd: the longest input a descriptor may deliver (one minute at 125 frames/s)
+STREAM_BLOCK_FRAMES = 64      # lna_open_fd: frames per feed at the most
 
 
 def _guard(fn):
@@ -59,6 +69,7 @@ class FstSearch:
         self._net = _A.FstNet(search_fst_fname)
         self._opt = _A.FstOptions.defaults()
         self._lna = None
+        self._fd = None
         self._result = None
         self.verbose = 0
         self.dur_by_state = False
@@ -104,8 +115,50 @@ class FstSearch:
         frames = (len(data) - 5) // (n_models * lnabytes)
         self._lna = (data[5:5 + frames * n_models * lnabytes], n_models, lnabytes, frames)
 
+    def lna_open_fd(self, fd, size):
+        """LnaReaderCircular::open_fd: the header from the descriptor now, the frames when run() reads them"""
+        head = b""
+        while len(head) < 5:
+            piece = os.read(fd, 5 - len(head))
+            if not piece:
+                raise RuntimeError("Exception: LnaReaderCircular::read_int(): End of file reached.")
+            head += piece
+        n_models, lnabytes = struct.unpack(">iB", head)
+        if n_models <= 0:
+            raise RuntimeError("Exception: LnaReaderCircular::open(): invalid number of states %d" % n_models)
+        if lnabytes not in (1, 2, 4):
+            raise RuntimeError("Exception: LnaReaderCircular::open(): invalid LNA byte number %d" % lnabytes)
+        self._lna = None
+        self._fd = (fd, n_models, lnabytes)
+
     def lna_close(self):
         self._lna = None
+        self._fd = None
+
+    def _run_fd(self):
+        """the descriptor to its end: whole frames are fed as soon as they are there, at most STREAM_BLOCK_FRAMES a feed"""
+        import torch
+        fd, n_models, lnabytes = self._fd
+        row = n_models * lnabytes
+        self._opt.dur_by_state = 1 if self.dur_by_state else 0
+        stream = _A.FstStream(self._net, 1, STREAM_MAX_FRAMES, self._opt, dur=self._dur)
+        try:
+            held = b""
+            while True:
+                piece = os.read(fd, row * STREAM_BLOCK_FRAMES - len(held))
+                held += piece
+                frames = len(held) // row
+                if frames:
+                    d_lna = torch.frombuffer(bytearray(held[:frames * row] + bytes(16)), dtype=torch.uint8).cuda()
+                    stream.feed_dev(d_lna, lnabytes, n_models, [0], [frames])
+                    stream.sync()      # (d_lna is read by the queued launch: it must not be freed before)
+                    held = held[frames * row:]
+                if not piece:
+                    break
+            self._result = stream.result(0)
+        finally:
+            stream.close()
+        self.status = self._result["status"]
 
     def init_search(self):
         """one token at the initial node (FstSearch_tmpl.hh:45-51)"""
@@ -115,6 +168,8 @@ class FstSearch:
 
     @_guard
     def run(self):
+        if self._lna is None and self._fd is not None:      # (lna_open after lna_open_fd: the file, opened last)
+            return self._run_fd()
         if self._lna is None:
             raise RuntimeError("Exception: LnaReaderCircular::go_to(): file not opened yet")
         import torch

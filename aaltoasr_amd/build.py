@@ -104,6 +104,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                       ("logl", "aku/main_logl.cc"),
                       ("dur_est", "aku/main_dur_est.cc"),
                       ("fst_decode", "aku/main_fst_decode.cc"),
+                      ("fst_stream", "aku/main_fst_stream.cc"),
                       ("aku_adapter_check", "aku/main_adapter_check.cc"),
                       ("feacat", "aku/main_feacat.cc"),
                       ("plugin_check", "aku/main_plugin_check.cc"),

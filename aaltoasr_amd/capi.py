@@ -470,6 +470,22 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_fst_batch_result.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(f), C.POINTER(f), C.POINTER(f), C.POINTER(i32),
                                         vp, i32, C.POINTER(i32)]
     L.aasr_fst_batch_tokens.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp]
+    L.aasr_fst_stream_create.argtypes = [vp, vp, vp, i32, i32, pvp]
+    L.aasr_fst_stream_destroy.argtypes = [vp]
+    L.aasr_fst_stream_destroy.restype = None
+    L.aasr_fst_stream_device_bytes.argtypes = [vp]
+    L.aasr_fst_stream_device_bytes.restype = i64
+    L.aasr_fst_stream_options.argtypes = [vp, vp]
+    L.aasr_fst_stream_options.restype = None
+    L.aasr_fst_stream_reset.argtypes = [vp, i32]
+    L.aasr_fst_stream_feed_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp]
+    L.aasr_fst_stream_sync.argtypes = [vp, vp]
+    L.aasr_fst_stream_result.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f), C.POINTER(f), C.POINTER(f),
+                                         C.POINTER(i32), vp, i32, C.POINTER(i32), vp, i32, C.POINTER(i32)]
+    L.aasr_fst_stream_tokens.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp]
+    L.aasr_fst_live_default_options.argtypes = [vp]
+    L.aasr_fst_live_default_options.restype = None
+    L.aasr_run_fst_live.argtypes = [vp, vp, vp, vp, vp, vp]
     L.aasr_fst_decode_default_options.argtypes = [vp]
     L.aasr_fst_decode_default_options.restype = None
     L.aasr_run_fst_decode_recipe.argtypes = [vp, vp, vp, vp, cp, vp, vp]
@@ -2923,6 +2939,83 @@ def fst_batch(net: FstNet, n_frames: list, d_lna, lnabytes: int, n_models: int, 
             r["reran"] = True
             out[u] = r
     return out
+
+
+class FstStream:
+    """aasr_fst_stream: n_sessions live searches over one network, fed frames as they arrive (include/aasr.h, "FST
+    decoder: streaming sessions").  A session after t frames holds what fst_batch gives for an utterance of those t
+    frames, whatever the feeds' sizes.  opts: FstOptions (None: the defaults); max_frames bounds every session's length
+    and sizes its tables.  A status other than OK is sticky until reset(u); nothing is rerun."""
+
+    def __init__(self, net: FstNet, n_sessions: int, max_frames: int, opts: Optional[FstOptions] = None,
+                 dur: Optional[FstDurations] = None):
+        self._h = C.c_void_p()
+        self.net, self.dur = net, dur           # (both must outlive the handle)
+        self.n_sessions, self.max_frames = n_sessions, max_frames
+        opts = opts or FstOptions.defaults()
+        check(lib().aasr_fst_stream_create(net.handle, dur.handle if dur is not None else None, C.byref(opts), n_sessions,
+                                           max_frames, C.byref(self._h)))
+        self.options = FstOptions()
+        lib().aasr_fst_stream_options(self._h, C.byref(self.options))
+        self.device_bytes = lib().aasr_fst_stream_device_bytes(self._h)
+
+    def feed_dev(self, d_lna, lnabytes: int, n_models: int, row0: list, n_new: list, stream: int = 0) -> None:
+        """queues one feed: session u takes n_new[u] frames from rows row0[u]... of the device tensor d_lna"""
+        r0 = np.ascontiguousarray(row0, np.int64)
+        nn = np.ascontiguousarray(n_new, np.int32)
+        if len(r0) != self.n_sessions or len(nn) != self.n_sessions:
+            raise ValueError("FstStream.feed_dev: row0 and n_new need one entry per session")
+        n_rows = (d_lna.numel() * d_lna.element_size()) // (n_models * lnabytes) if n_models > 0 and lnabytes > 0 else 0
+        check(lib().aasr_fst_stream_feed_dev(self._h, _ptr(d_lna), lnabytes, n_models, n_rows, _ptr(r0), _ptr(nn), stream))
+
+    def sync(self, stream: int = 0) -> None:
+        check(lib().aasr_fst_stream_sync(self._h, stream))
+
+    def reset(self, u: int = -1) -> None:
+        check(lib().aasr_fst_stream_reset(self._h, u))
+
+    def result(self, u: int, want_tokens: bool = True) -> dict:
+        """fst_batch's entry for the frames so far, plus partial_words, partial_text (the best token's words) and frames_done"""
+        L = lib()
+        st, fd, nw, npw, nt = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        lp, blp, bflp = C.c_float(), C.c_float(), C.c_float()
+        words, part = np.zeros(self.max_frames + 1, np.int32), np.zeros(self.max_frames + 1, np.int32)
+        check(L.aasr_fst_stream_result(self._h, u, C.byref(st), C.byref(fd), C.byref(lp), C.byref(blp), C.byref(bflp), C.byref(nw),
+                                       _ptr(words), len(words), C.byref(npw), _ptr(part), len(part), C.byref(nt)))
+        sym = self.net.symbols
+        r = {"status": st.value, "logprob": np.float32(lp.value), "best_logprob": np.float32(blp.value),
+             "best_final_logprob": np.float32(bflp.value), "words": tuple(int(w) for w in words[:nw.value]),
+             "text": b" ".join(sym[w] for w in words[:nw.value]), "n_tokens": nt.value, "options": self.options,
+             "device_bytes": self.device_bytes, "reran": False, "frames_done": fd.value,
+             "partial_words": tuple(int(w) for w in part[:npw.value]),
+             "partial_text": b" ".join(sym[w] for w in part[:npw.value])}
+        if want_tokens:
+            r["tokens"] = self.tokens(u, nt.value, fd.value)
+        return r
+
+    def tokens(self, u: int, n_tokens: Optional[int] = None, frames_done: Optional[int] = None) -> list:
+        """(node, logprob, dur, words) of the session's tokens, by descending log-probability"""
+        L = lib()
+        if n_tokens is None or frames_done is None:
+            nt, fd = C.c_int32(), C.c_int32()
+            check(L.aasr_fst_stream_result(self._h, u, None, C.byref(fd), None, None, None, None, None, 0, None, None, 0, C.byref(nt)))
+            n_tokens, frames_done = nt.value, fd.value
+        k = n_tokens
+        node, tl, td = np.zeros(max(1, k), np.int32), np.zeros(max(1, k), np.float32), np.zeros(max(1, k), np.int32)
+        wb, tw = np.zeros(k + 2, np.int32), np.zeros(max(1, k * (frames_done + 1)), np.int32)
+        check(L.aasr_fst_stream_tokens(self._h, u, k, _ptr(node), _ptr(tl), _ptr(td), _ptr(wb), len(tw), _ptr(tw)))
+        return [(int(node[j]), np.float32(tl[j]), int(td[j]), tuple(int(w) for w in tw[wb[j]:wb[j + 1]])) for j in range(k)]
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_fst_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FstDecodeOptions(C.Structure):

@@ -56,6 +56,48 @@ void fst_decode_table(int32_t lnabytes, std::vector<float> &dec) {  // LnaReader
   for (size_t i = 0; i < dec.size(); i++) dec[i] = lnabytes == 2 ? (float)((double)(int)i / -1820.0) : (float)((double)(int)i / -24.0);
 }
 
+// the n tokens of utterance u by descending log-probability, their words read back through the history table
+void fst_tokens_read(const char *who, const FstParams &p, int32_t u, int32_t n, hipStream_t st, int32_t *node, float *logprob,
+                     int32_t *dur, int32_t *word_begin, int32_t cap_words, int32_t *words) {
+  word_begin[0] = 0;
+  if (n == 0) return;
+  const size_t ct = (size_t)p.cap_tok, ch = (size_t)p.cap_hist;
+  std::vector<int32_t> tn((size_t)n), td((size_t)n), th((size_t)n);
+  std::vector<float> tl((size_t)n);
+  std::vector<unsigned long long> hk(ch);
+  AASR_HIP(hipMemcpyAsync(tn.data(), p.t_node + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  AASR_HIP(hipMemcpyAsync(td.data(), p.t_dur + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  AASR_HIP(hipMemcpyAsync(th.data(), p.t_hist + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  AASR_HIP(hipMemcpyAsync(tl.data(), p.t_lp + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  AASR_HIP(hipMemcpyAsync(hk.data(), p.h_key + (size_t)u * ch, ch * 8, hipMemcpyDeviceToHost, st));
+  AASR_HIP(hipStreamSynchronize(st));
+  // descending log-probability, the earlier token first among equals (the order of the reference's list)
+  std::vector<int32_t> order((size_t)n);
+  for (int32_t i = 0; i < n; i++) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return tl[(size_t)x] > tl[(size_t)y]; });
+  int32_t at = 0;
+  std::vector<int32_t> chain;
+  for (int32_t j = 0; j < n; j++) {
+    const int32_t i = order[(size_t)j];
+    node[j] = tn[(size_t)i];
+    logprob[j] = tl[(size_t)i];
+    dur[j] = td[(size_t)i];
+    chain.clear();
+    for (int64_t h = th[(size_t)i]; h != 0;) {
+      if (h < 0 || h > (int64_t)ch || hk[(size_t)h - 1] == ~0ull || chain.size() > (size_t)p.cap_words)
+        raise(AASR_ERR_INVALID, "%s: utterance %d has a broken history chain", who, u);
+      chain.push_back((int32_t)(uint32_t)hk[(size_t)h - 1]);
+      h = (int64_t)(hk[(size_t)h - 1] >> 32);
+    }
+    if (words) {
+      if (at + (int32_t)chain.size() > cap_words) raise(AASR_ERR_INVALID, "%s: room for %d words", who, cap_words);
+      std::copy(chain.rbegin(), chain.rend(), words + at);
+    }
+    at += (int32_t)chain.size();
+    word_begin[j + 1] = at;
+  }
+}
+
 }  // namespace aasr
 
 extern "C" {
@@ -330,44 +372,7 @@ aasr_status aasr_fst_batch_tokens(aasr_fst_batch *b, int32_t u, int32_t cap_toke
     const int32_t n = r.n_tokens;
     if (n < 0 || n > b->cap_tok) raise(AASR_ERR_INVALID, "aasr_fst_batch_tokens: utterance %d reports %d tokens", u, n);
     if (cap_tokens < n) raise(AASR_ERR_INVALID, "aasr_fst_batch_tokens: %d tokens, room for %d", n, cap_tokens);
-    word_begin[0] = 0;
-    if (n == 0) return;
-    const size_t ct = (size_t)b->cap_tok, ch = (size_t)b->opt.cap_history;
-    std::vector<int32_t> tn((size_t)n), td((size_t)n), th((size_t)n);
-    std::vector<float> tl((size_t)n);
-    std::vector<unsigned long long> hk(ch);
-    const hipStream_t st = b->sync_stream;
-    AASR_HIP(hipMemcpyAsync(tn.data(), b->p.t_node + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    AASR_HIP(hipMemcpyAsync(td.data(), b->p.t_dur + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    AASR_HIP(hipMemcpyAsync(th.data(), b->p.t_hist + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    AASR_HIP(hipMemcpyAsync(tl.data(), b->p.t_lp + (size_t)u * ct, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    AASR_HIP(hipMemcpyAsync(hk.data(), b->p.h_key + (size_t)u * ch, ch * 8, hipMemcpyDeviceToHost, st));
-    AASR_HIP(hipStreamSynchronize(st));
-    // descending log-probability, the earlier token first among equals (the order of the reference's list)
-    std::vector<int32_t> order((size_t)n);
-    for (int32_t i = 0; i < n; i++) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return tl[(size_t)x] > tl[(size_t)y]; });
-    int32_t at = 0;
-    std::vector<int32_t> chain;
-    for (int32_t j = 0; j < n; j++) {
-      const int32_t i = order[(size_t)j];
-      node[j] = tn[(size_t)i];
-      logprob[j] = tl[(size_t)i];
-      dur[j] = td[(size_t)i];
-      chain.clear();
-      for (int64_t h = th[(size_t)i]; h != 0;) {
-        if (h < 0 || h > (int64_t)ch || hk[(size_t)h - 1] == ~0ull || chain.size() > (size_t)b->cap_words)
-          raise(AASR_ERR_INVALID, "aasr_fst_batch_tokens: utterance %d has a broken history chain", u);
-        chain.push_back((int32_t)(uint32_t)hk[(size_t)h - 1]);
-        h = (int64_t)(hk[(size_t)h - 1] >> 32);
-      }
-      if (words) {
-        if (at + (int32_t)chain.size() > cap_words) raise(AASR_ERR_INVALID, "aasr_fst_batch_tokens: room for %d words", cap_words);
-        std::copy(chain.rbegin(), chain.rend(), words + at);
-      }
-      at += (int32_t)chain.size();
-      word_begin[j + 1] = at;
-    }
+    fst_tokens_read("aasr_fst_batch_tokens", b->p, u, n, b->sync_stream, node, logprob, dur, word_begin, cap_words, words);
   });
 }
 

@@ -29,6 +29,9 @@
 // candidates is "earlier" in the next frame and nothing else (tools/fst_restate.py reports every such tie).
 //
 // A capacity exceeded ends the utterance with FST_OVERFLOW_*; nothing is truncated silently.
+//
+// The start, the frame's six phases and the result block are device functions in fst_frame.h, shared with the resumable
+// entry k_fst_search_chunk (fst_stream.h), which runs the frames of one feed of a live session from saved state.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,5 +77,10 @@ struct FstParams {
 };
 
 void fst_search_launch(const FstParams &p, int32_t n_launch, hipStream_t st);
+
+// the n tokens utterance u holds, by descending log-probability (the earlier first among equals), with their words read
+// back through the history table; synchronises st.  who: the calling function's name for the messages (fst_search.cc)
+void fst_tokens_read(const char *who, const FstParams &p, int32_t u, int32_t n, hipStream_t st, int32_t *node, float *logprob,
+                     int32_t *dur, int32_t *word_begin, int32_t cap_words, int32_t *words);
 
 }  // namespace aasr

@@ -1786,6 +1786,81 @@ aasr_status aasr_fst_batch_result(const aasr_fst_batch *b, int32_t u, int32_t *s
 aasr_status aasr_fst_batch_tokens(aasr_fst_batch *b, int32_t u, int32_t cap_tokens, int32_t *node, float *logprob, int32_t *dur,
                                   int32_t *word_begin, int32_t cap_words, int32_t *words);
 
+/* ---- FST decoder: streaming sessions ------------------------------------------------------------------------------------
+ * The search of aasr_fst_batch cut at feed boundaries: n_sessions live utterances whose tokens, history table and
+ * counters stay on the device between launches, one launch per feed over all of them (csrc/fst_stream.h).  Whatever the
+ * chunking, a session after t frames holds what aasr_fst_batch holds after an utterance of those t frames, bit for bit:
+ * both kernels run one copy of the frame's arithmetic (csrc/fst_frame.h).
+ * Capacities are derived as aasr_fst_batch_create derives them, with max_frames in the place of the longest utterance
+ * (the same cap_* options; the duration table covers d = 0 ... max_frames; results hold max_frames + 1 words).
+ * A status other than AASR_FST_OK is sticky: the session skips the frames it is fed and keeps its status, frames_done
+ * and result until aasr_fst_stream_reset.  An overflow is reported and never retried behind the caller's back: a live
+ * stream cannot be re-run from frames that are gone, and the tables of a live session do not grow -- choose max_frames
+ * and the capacities for the longest utterance expected.  frames_done counts the frames consumed, the one that ended the
+ * search (NO_TOKENS, OVERFLOW_*) included, so it does not depend on where the feeds were cut.
+ * Out of scope: confidence scores on a stream (they need the whole utterance's sums and the phone loop), growing a table
+ * of a live session, endpointing, one session over several workgroups.
+ * One stream per handle: feeds and syncs of a handle go to the same `stream`. */
+typedef struct aasr_fst_stream aasr_fst_stream;
+/* Sessions start fresh.  n_sessions < 1, max_frames < 1 or a null argument: AASR_ERR_INVALID.  net and dur (may be NULL)
+ * must outlive the handle.  Needs a device. */
+aasr_status aasr_fst_stream_create(const aasr_fstnet *net, const aasr_fst_durations *dur, const aasr_fst_options *opt,
+                                   int32_t n_sessions, int32_t max_frames, aasr_fst_stream **out);
+void aasr_fst_stream_destroy(aasr_fst_stream *s);
+int64_t aasr_fst_stream_device_bytes(const aasr_fst_stream *s);
+/* the options with the derived capacities filled in */
+void aasr_fst_stream_options(const aasr_fst_stream *s, aasr_fst_options *out);
+/* Marks session u (-1: every session) fresh: the next feed starts it anew -- tables cleared, one token at the initial
+ * node --, whatever its n_new.  No launch of its own; until that feed, result and tokens answer with the start state. */
+aasr_status aasr_fst_stream_reset(aasr_fst_stream *s, int32_t u);
+/* One feed: session u takes n_new[u] >= 0 further frames from rows row0[u] ... row0[u] + n_new[u] - 1 of d_lna (rows of
+ * THIS buffer; layout and decoding as aasr_fst_batch_dev).  Only queues: a copy and one launch on `stream`; row0 and n_new
+ * are not read after it returns.  A session with n_new[u] == 0 that is not fresh is left untouched.
+ * Refused with AASR_ERR_INVALID before anything is queued, every session left as it was: a negative n_new[u]; frames_done +
+ * n_new[u] > max_frames; a row range outside 0 ... n_rows; a network whose largest pdf index is not below n_models; an
+ * lnabytes or n_models other than what a session that is not fresh was fed before.
+ * frames_done is counted on the host, for the sessions whose status the last sync saw as AASR_FST_OK.  A session that went
+ * sticky in a feed not yet synced is still counted (and checked against max_frames) as if it had taken its frames; the next
+ * sync sets its count to the device's frames_done, and from then on its feeds are neither counted nor checked against
+ * max_frames. */
+aasr_status aasr_fst_stream_feed_dev(aasr_fst_stream *s, const void *d_lna, int32_t lnabytes, int32_t n_models,
+                                     int64_t n_rows, const int64_t *row0, const int32_t *n_new, void *stream);
+/* waits for the feeds queued on `stream` and fetches every session's record */
+aasr_status aasr_fst_stream_sync(aasr_fst_stream *s, void *stream);
+/* Session u after a sync (any pointer may be NULL): the fields of aasr_fst_batch_result for the frames so far, with the
+ * same sentinels; frames_done; and the partial hypothesis, the words of the best token over all nodes (the token behind
+ * best_logprob: the highest log-probability, the earlier token among equals -- the reference's best_tokens(1)).  A fresh
+ * session that was not fed yet reports the start state (init_search()): one token, best_logprob 0.0f, no words. */
+aasr_status aasr_fst_stream_result(const aasr_fst_stream *s, int32_t u, int32_t *status, int32_t *frames_done,
+                                   float *logprob, float *best_logprob, float *best_final_logprob,
+                                   int32_t *n_words, int32_t *words, int32_t cap_words,
+                                   int32_t *n_partial_words, int32_t *partial_words, int32_t cap_partial, int32_t *n_tokens);
+/* as aasr_fst_batch_tokens: the session's tokens by descending log-probability */
+aasr_status aasr_fst_stream_tokens(aasr_fst_stream *s, int32_t u, int32_t cap_tokens, int32_t *node, float *logprob,
+                                   int32_t *dur, int32_t *word_begin, int32_t cap_words, int32_t *words);
+
+/* The fst_stream tool's run (csrc/fst_live.cc): headerless PCM16 (the audiofile module's byte order) from the descriptor
+ * in_fd while it is still being written.  The samples are read as frames become computable (frame t when the samples
+ * cover frame t + halo_r + 1, aasr_feat_halo; at the end of input the frames up to aasr_feat_eof_frame); per chunk of
+ * chunk_frames frames the feature chain for exactly those frames over the samples so far, one score + LNA step
+ * (aasr_gmm_score_lna_dev, normalised, lnabytes 2 or 4) and one feed of a one-session aasr_fst_stream that reads the
+ * step's device buffer in place.  On stdout: with `partial`, a flushed line `frames best_logprob words...` whenever the
+ * partial hypothesis differs from the one printed last; at the end of input one line `- logprob words... [STATUS]` in
+ * fst_decode's format.  An input of more than max_frames frames is refused when it gets there; nothing is rerun.
+ * Out of scope: speaker files, endpointing. */
+typedef struct aasr_fst_live_options {
+  aasr_fst_options fst;
+  int32_t lnabytes;      /* 2 or 4 */
+  int32_t chunk_frames;  /* 16; >= 1 */
+  int32_t max_frames;    /* 7500 (one minute at 125 frames/s); >= 1 */
+  int32_t partial;
+  int32_t info;
+  int32_t in_fd;         /* 0: standard input */
+} aasr_fst_live_options;
+void aasr_fst_live_default_options(aasr_fst_live_options *opt);
+aasr_status aasr_run_fst_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur,
+                              const aasr_fst_live_options *opt, aasr_run_stats *stats);
+
 /* fst_decode's run over a recipe (csrc/fst_decode.cc), groups of `group` utterances.  Engine mode (lna_files 0; feat and
  * gmm given): per group the recipe's audio= through the feature chain (one launch set per stretch of equal speaker
  * settings), ONE score + LNA step over the group's frames (aasr_gmm_score_lna_dev, normalised, lnabytes 2 or 4: the
