@@ -22,7 +22,8 @@ reference's unconditional debug lines are not printed, its verbose block is when
 
 lna_open_fd(fd, size) reads a descriptor -- a pipe that is still being written -- instead of a file: run() reads it in
 blocks as they arrive and feeds each block to a one-session streaming search (capi.FstStream, include/aasr.h "FST
-decoder: streaming sessions"), which is the batch search of the same frames bit for bit.  A descriptor has no size to
+decoder: streaming sessions"), which is the batch search of the same frames bit for bit.  The confidence classes do the
+same on a one-session streaming confidence (capi.FstConfStream, "FST decoder: confidence on streaming sessions").  A descriptor has no size to
 derive the search's tables from: they are sized for STREAM_MAX_FRAMES frames (module level, settable before run(); a longer
 input is refused when it gets there).  STREAM_BLOCK_FRAMES is the most frames one feed takes.
 """
@@ -135,13 +136,21 @@ class FstSearch:
         self._lna = None
         self._fd = None
 
+    def _open_stream(self):
+        """the one-session stream of _run_fd, and what reads its answer into the object"""
+        self._opt.dur_by_state = 1 if self.dur_by_state else 0
+        stream = _A.FstStream(self._net, 1, STREAM_MAX_FRAMES, self._opt, dur=self._dur)
+
+        def take():
+            self._result = stream.result(0)
+        return stream, take
+
     def _run_fd(self):
         """the descriptor to its end: whole frames are fed as soon as they are there, at most STREAM_BLOCK_FRAMES a feed"""
         import torch
         fd, n_models, lnabytes = self._fd
         row = n_models * lnabytes
-        self._opt.dur_by_state = 1 if self.dur_by_state else 0
-        stream = _A.FstStream(self._net, 1, STREAM_MAX_FRAMES, self._opt, dur=self._dur)
+        stream, take = self._open_stream()
         try:
             held = b""
             while True:
@@ -155,7 +164,7 @@ class FstSearch:
                     held = held[frames * row:]
                 if not piece:
                     break
-            self._result = stream.result(0)
+            take()
         finally:
             stream.close()
         self.status = self._result["status"]
@@ -240,16 +249,31 @@ class FstConfidence(FstSearchC):
         FstSearch.init_search(self)
         self._conf = None
 
+    def _conf_options(self):
+        self._opt.dur_by_state = self._phone_opt.dur_by_state = 1 if self.dur_by_state else 0
+        o = _A.FstConfOptions.defaults(phone_loop=self._phone_loop, verbose=0)
+        o.grammar, o.phone = self._opt, self._phone_opt
+        return o
+
+    def _open_stream(self):
+        """a one-session confidence stream (capi.FstConfStream): the batch confidence of the same frames bit for bit"""
+        stream = _A.FstConfStream(self._net, self._phone_net, 1, STREAM_MAX_FRAMES, self._conf_options(), dur=self._dur)
+
+        def take():
+            self._conf = stream.result(0, want_tokens=True)
+            self._result = self._conf["grammar"]
+        return stream, take
+
     @_guard
     def run(self):
+        if self._lna is None and self._fd is not None:      # (lna_open after lna_open_fd: the file, opened last)
+            return self._run_fd()
         if self._lna is None:
             raise RuntimeError("Exception: LnaReaderCircular::go_to(): file not opened yet")
         import torch
         raw, n_models, lnabytes, frames = self._lna
         d_lna = torch.frombuffer(bytearray(raw + bytes(16)), dtype=torch.uint8).cuda()
-        self._opt.dur_by_state = self._phone_opt.dur_by_state = 1 if self.dur_by_state else 0
-        o = _A.FstConfOptions.defaults(phone_loop=self._phone_loop, verbose=0)
-        o.grammar, o.phone = self._opt, self._phone_opt
+        o = self._conf_options()
         self._conf = _A.fst_conf_batch(self._net, self._phone_net, [frames], d_lna, lnabytes, n_models, [0], o, dur=self._dur,
                                        want_tokens=True)[0]
         self._result = self._conf["grammar"]

@@ -512,6 +512,25 @@ def _declare(L: C.CDLL) -> None:
     L.aasr_fst_conf_edit_distance.restype = i32
     L.aasr_fst_conf_formulas.argtypes = [vp, i32, cp, i32, cp, i32]
     L.aasr_fst_conf_formulas.restype = None
+    L.aasr_fst_conf_stream_create.argtypes = [vp, vp, vp, vp, i32, i32, pvp]
+    L.aasr_fst_conf_stream_destroy.argtypes = [vp]
+    L.aasr_fst_conf_stream_destroy.restype = None
+    L.aasr_fst_conf_stream_device_bytes.argtypes = [vp]
+    L.aasr_fst_conf_stream_device_bytes.restype = i64
+    L.aasr_fst_conf_stream_options.argtypes = [vp, vp]
+    L.aasr_fst_conf_stream_options.restype = None
+    L.aasr_fst_conf_stream_reset.argtypes = [vp, i32]
+    L.aasr_fst_conf_stream_feed_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp]
+    L.aasr_fst_conf_stream_sync.argtypes = [vp, vp]
+    L.aasr_fst_conf_stream_result.argtypes = [vp, i32, vp]
+    L.aasr_fst_conf_stream_search_result.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f), C.POINTER(f), C.POINTER(f),
+                                                     C.POINTER(i32), vp, i32, C.POINTER(i32), vp, i32, C.POINTER(i32)]
+    L.aasr_fst_conf_stream_tokens.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]
+    L.aasr_fst_conf_stream_record.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(f), C.POINTER(f)]
+    L.aasr_fst_conf_stream_best_acu.argtypes = [vp, i32, C.POINTER(f), C.POINTER(i32)]
+    L.aasr_fst_live_confidence_default_options.argtypes = [vp]
+    L.aasr_fst_live_confidence_default_options.restype = None
+    L.aasr_run_fst_live_confidence.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.aasr_fst_confidence_default_options.argtypes = [vp]
     L.aasr_fst_confidence_default_options.restype = None
     L.aasr_run_fst_confidence_recipe.argtypes = [vp, vp, vp, vp, vp, cp, vp, vp]
@@ -3200,6 +3219,111 @@ def fst_frame_best(n_frames: list, d_lna, lnabytes: int, n_models: int, row0: li
         return out
     finally:
         L.aasr_fst_conf_batch_destroy(b)
+
+
+class FstConfStream:
+    """aasr_fst_conf_stream: n_sessions live confidences, fed frames as they arrive (include/aasr.h, "FST decoder:
+    confidence on streaming sessions").  A session after t frames answers what fst_conf_batch gives for an utterance of
+    those t frames, whatever the feeds' sizes.  opts: FstConfOptions (None: the defaults; phone_loop is set from
+    phone_net); max_frames bounds every session's length and sizes both searches' tables.  A search's status other than
+    OK is sticky until reset(u); nothing is rerun."""
+
+    def __init__(self, net: FstNet, phone_net: Optional[FstNet], n_sessions: int, max_frames: int,
+                 opts: Optional[FstConfOptions] = None, dur: Optional[FstDurations] = None):
+        self._h = C.c_void_p()
+        self.net, self.phone_net, self.dur = net, phone_net, dur           # (all must outlive the handle)
+        self.n_sessions, self.max_frames = n_sessions, max_frames
+        opts = opts or FstConfOptions.defaults(phone_loop=1 if phone_net is not None else 0)
+        check(lib().aasr_fst_conf_stream_create(net.handle, phone_net.handle if phone_net is not None else None,
+                                                dur.handle if dur is not None else None, C.byref(opts), n_sessions, max_frames,
+                                                C.byref(self._h)))
+        self.options = FstConfOptions()
+        lib().aasr_fst_conf_stream_options(self._h, C.byref(self.options))
+        self.device_bytes = lib().aasr_fst_conf_stream_device_bytes(self._h)
+        self._nets = (net, phone_net if self.options.phone_loop else None)
+
+    def feed_dev(self, d_lna, lnabytes: int, n_models: int, row0: list, n_new: list, stream: int = 0) -> None:
+        """queues one feed: session u takes n_new[u] frames from rows row0[u]... of the device tensor d_lna"""
+        r0 = np.ascontiguousarray(row0, np.int64)
+        nn = np.ascontiguousarray(n_new, np.int32)
+        if len(r0) != self.n_sessions or len(nn) != self.n_sessions:
+            raise ValueError("FstConfStream.feed_dev: row0 and n_new need one entry per session")
+        n_rows = (d_lna.numel() * d_lna.element_size()) // (n_models * lnabytes) if n_models > 0 and lnabytes > 0 else 0
+        check(lib().aasr_fst_conf_stream_feed_dev(self._h, _ptr(d_lna), lnabytes, n_models, n_rows, _ptr(r0), _ptr(nn), stream))
+
+    def sync(self, stream: int = 0) -> None:
+        check(lib().aasr_fst_conf_stream_sync(self._h, stream))
+
+    def reset(self, u: int = -1) -> None:
+        check(lib().aasr_fst_conf_stream_reset(self._h, u))
+
+    def search_result(self, u: int, phone: int = 0, want_tokens: bool = False) -> dict:
+        """FstStream.result's entry for the grammar search (phone 0) or the phone-loop search (phone 1), plus `record`"""
+        L = lib()
+        st, fd, nw, npw, nt = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        lp, blp, bflp = C.c_float(), C.c_float(), C.c_float()
+        words, part = np.zeros(self.max_frames + 1, np.int32), np.zeros(self.max_frames + 1, np.int32)
+        check(L.aasr_fst_conf_stream_search_result(self._h, u, phone, C.byref(st), C.byref(fd), C.byref(lp), C.byref(blp), C.byref(bflp),
+                                                   C.byref(nw), _ptr(words), len(words), C.byref(npw), _ptr(part), len(part), C.byref(nt)))
+        sym = self._nets[phone].symbols
+        r = {"status": st.value, "logprob": np.float32(lp.value), "best_logprob": np.float32(blp.value),
+             "best_final_logprob": np.float32(bflp.value), "words": tuple(int(w) for w in words[:nw.value]),
+             "text": b" ".join(sym[w] for w in words[:nw.value]), "n_tokens": nt.value, "frames_done": fd.value,
+             "partial_words": tuple(int(w) for w in part[:npw.value]),
+             "partial_text": b" ".join(sym[w] for w in part[:npw.value])}
+        hf, rw, hd = C.c_int32(), C.c_int32(), C.c_int32()
+        bf, bd = C.c_float(), C.c_float()
+        check(L.aasr_fst_conf_stream_record(self._h, u, phone, C.byref(hf), C.byref(rw), C.byref(hd), C.byref(bf), C.byref(bd)))
+        r["record"] = {"has_final": hf.value, "n_words": rw.value, "has_different": hd.value,
+                       "best_final_logprob": np.float32(bf.value), "best_different_logprob": np.float32(bd.value)}
+        if want_tokens:
+            r["tokens"] = self.tokens(u, phone, nt.value, fd.value)
+        return r
+
+    def tokens(self, u: int, phone: int = 0, n_tokens: Optional[int] = None, frames_done: Optional[int] = None) -> list:
+        """(node, logprob, dur, words) of a search's tokens, by descending log-probability"""
+        L = lib()
+        if n_tokens is None or frames_done is None:
+            nt, fd = C.c_int32(), C.c_int32()
+            check(L.aasr_fst_conf_stream_search_result(self._h, u, phone, None, C.byref(fd), None, None, None, None, None, 0, None, None, 0,
+                                                       C.byref(nt)))
+            n_tokens, frames_done = nt.value, fd.value
+        k = n_tokens
+        node, tl, td = np.zeros(max(1, k), np.int32), np.zeros(max(1, k), np.float32), np.zeros(max(1, k), np.int32)
+        wb, tw = np.zeros(k + 2, np.int32), np.zeros(max(1, k * (frames_done + 1)), np.int32)
+        check(L.aasr_fst_conf_stream_tokens(self._h, u, phone, k, _ptr(node), _ptr(tl), _ptr(td), _ptr(wb), len(tw), _ptr(tw)))
+        return [(int(node[j]), np.float32(tl[j]), int(td[j]), tuple(int(w) for w in tw[wb[j]:wb[j + 1]])) for j in range(k)]
+
+    def best_acu(self, u: int):
+        """(the carried float32 sum of the frames' best acoustic values, the frames it covers); with a phone loop only"""
+        s, n = C.c_float(), C.c_int32()
+        check(lib().aasr_fst_conf_stream_best_acu(self._h, u, C.byref(s), C.byref(n)))
+        return np.float32(s.value), n.value
+
+    def result(self, u: int, want_tokens: bool = False) -> dict:
+        """fst_conf_batch's entry for the frames fed so far (without `reran`: nothing is rerun on a stream)"""
+        cr = FstConfResult()
+        check(lib().aasr_fst_conf_stream_result(self._h, u, C.byref(cr)))
+        r = {k: np.float32(getattr(cr, k)) for k in FST_CONF_FLOATS}
+        r.update(frames=cr.frames, grammar_status=cr.grammar_status, phone_status=cr.phone_status, no_final=cr.no_final,
+                 valid=cr.valid, options=self.options, reran=False)
+        if not cr.valid:
+            r["confidence"] = None
+        r["grammar"] = self.search_result(u, 0, want_tokens)
+        r["phone"] = self.search_result(u, 1, want_tokens) if self._nets[1] is not None else None
+        r["text"] = r["grammar"]["text"]
+        return r
+
+    def close(self) -> None:
+        if self._h:
+            lib().aasr_fst_conf_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FstConfidenceOptions(C.Structure):

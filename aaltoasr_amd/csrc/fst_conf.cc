@@ -48,15 +48,6 @@ void ok(aasr_status s) {
   if (s != AASR_OK) raise(s, "%s", last_error().c_str());
 }
 
-void check_options(const aasr_fst_options &o, const char *which) {
-  if (!(o.beam >= 0) || !std::isfinite(o.beam)) raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_create: the %s beam must be finite and not negative", which);
-  if (o.token_limit < 0) raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_create: the %s token limit must not be negative", which);
-  if (!std::isfinite(o.duration_scale) || !std::isfinite(o.transition_scale))
-    raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_create: the %s scales must be finite", which);
-  if (o.cap_candidates < 0 || o.cap_recomb < 0 || o.cap_history < 0)
-    raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_create: negative %s capacity", which);
-}
-
 std::string remove_junk(const char *s, size_t n) {  // spaces and repeats of the last kept byte go; a space does not end a run
   std::string out;
   char prev = ' ';
@@ -141,6 +132,45 @@ void queue_frame_best(aasr_fst_conf_batch *b, const void *d_lna, int32_t lnabyte
 
 }  // namespace
 
+namespace aasr {
+
+void fst_conf_check_options(const aasr_fst_options &o, const char *who, const char *which) {
+  if (!(o.beam >= 0) || !std::isfinite(o.beam)) raise(AASR_ERR_INVALID, "%s: the %s beam must be finite and not negative", who, which);
+  if (o.token_limit < 0) raise(AASR_ERR_INVALID, "%s: the %s token limit must not be negative", who, which);
+  if (!std::isfinite(o.duration_scale) || !std::isfinite(o.transition_scale)) raise(AASR_ERR_INVALID, "%s: the %s scales must be finite", who, which);
+  if (o.cap_candidates < 0 || o.cap_recomb < 0 || o.cap_history < 0) raise(AASR_ERR_INVALID, "%s: negative %s capacity", who, which);
+}
+
+// a phone loop puts a symbol on every phone: far more of its candidates carry a word than a grammar's, so its derived
+// history table holds frames x tokens entries (aasr_fst_batch_create: a quarter of that), between 2^12 and 2^21
+int32_t fst_conf_phone_history(const aasr_fst_options &phone, int64_t longest) {
+  int64_t K = (int64_t)phone.token_limit + 1;
+  if (phone.cap_candidates > 0) K = std::min<int64_t>(K, phone.cap_candidates);
+  int64_t cap = 1 << 12;
+  while (cap < longest * K && cap < (1 << 21)) cap <<= 1;
+  return (int32_t)cap;
+}
+
+bool fst_conf_finish(aasr_fst_conf_result &r, const int32_t status[2], const float logprob[2], const FstConfRecord &g, bool phone_loop,
+                     float sum, const std::string &grammar, const std::string &ploop, const char *who, int32_t u) {
+  r.grammar_status = status[0];
+  r.phone_status = status[1];
+  if (status[0] >= AASR_FST_OVERFLOW_CANDIDATES || status[1] >= AASR_FST_OVERFLOW_CANDIDATES) return true;
+  if (g.has_final && std::memcmp(&g.best_final_lp, &logprob[0], sizeof(float)) != 0)
+    raise(AASR_ERR_INVALID, "%s: utterance %d: the token record's best end-node token is not the search's", who, u);
+  r.valid = 1;
+  r.no_final = !g.has_final;
+  r.grammar_logprob = logprob[0];
+  r.ploop_logprob = logprob[1];
+  r.best_final_logprob = g.best_final_lp;  // (-9999999.9f without an end-node token)
+  r.best_different_logprob = g.best_different_lp;
+  r.best_acu_score = phone_loop ? sum : 0.0f;
+  formulas(r, g.has_final ? g.best_final_n_words : 0, grammar, phone_loop ? &ploop : nullptr);
+  return false;
+}
+
+}  // namespace aasr
+
 extern "C" {
 
 void aasr_fst_conf_default_options(aasr_fst_conf_options *o) {
@@ -158,8 +188,8 @@ aasr_status aasr_fst_conf_batch_create(const aasr_fstnet *grammar_net, const aas
     *out = nullptr;
     if (!grammar_net) raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_create: no grammar network");
     if (opt->phone_loop && !phone_net) raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_create: phone_loop without a phone-loop network");
-    check_options(opt->grammar, "grammar");
-    check_options(opt->phone, "phone");
+    fst_conf_check_options(opt->grammar, "aasr_fst_conf_batch_create", "grammar");
+    fst_conf_check_options(opt->phone, "aasr_fst_conf_batch_create", "phone");
     for (int u = 0; u < n_utt; u++)
       if (n_frames[u] < 0) raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_create: utterance %d has %d frames", u, n_frames[u]);
     require_device();
@@ -172,17 +202,10 @@ aasr_status aasr_fst_conf_batch_create(const aasr_fstnet *grammar_net, const aas
     ok(aasr_fst_batch_create(grammar_net, dur, &opt->grammar, n_utt, n_frames, &b->inner[0]));
     aasr_fst_batch_options(b->inner[0], &b->opt.grammar);
     if (opt->phone_loop) {
-      // a phone loop puts a symbol on every phone: far more of its candidates carry a word than a grammar's, so its derived
-      // history table holds frames x tokens entries (aasr_fst_batch_create: a quarter of that), between 2^12 and 2^21
       aasr_fst_options phone = opt->phone;
-      if (phone.cap_history == 0) {
-        int64_t D = 0, K = (int64_t)phone.token_limit + 1;
-        for (int u = 0; u < n_utt; u++) D = std::max<int64_t>(D, n_frames[u]);
-        if (phone.cap_candidates > 0) K = std::min<int64_t>(K, phone.cap_candidates);
-        int64_t cap = 1 << 12;
-        while (cap < D * K && cap < (1 << 21)) cap <<= 1;
-        phone.cap_history = (int32_t)cap;
-      }
+      int64_t D = 0;
+      for (int u = 0; u < n_utt; u++) D = std::max<int64_t>(D, n_frames[u]);
+      if (phone.cap_history == 0) phone.cap_history = fst_conf_phone_history(phone, D);
       ok(aasr_fst_batch_create(phone_net, dur, &phone, n_utt, n_frames, &b->inner[1]));
       aasr_fst_batch_options(b->inner[1], &b->opt.phone);
     }
@@ -270,24 +293,9 @@ aasr_status aasr_fst_conf_batch_sync(aasr_fst_conf_batch *b, void *stream, int32
           t += b->net[k]->symbols[(size_t)words[(size_t)i]];
         }
       }
-      r.grammar_status = status[0];
-      r.phone_status = status[1];
-      if (status[0] >= AASR_FST_OVERFLOW_CANDIDATES || status[1] >= AASR_FST_OVERFLOW_CANDIDATES) {
+      if (fst_conf_finish(r, status, logprob, b->rec[0][(size_t)u], b->inner[1] != nullptr, b->sum[(size_t)u], b->text[0][(size_t)u],
+                          b->text[1][(size_t)u], "aasr_fst_conf_batch_sync", u))
         n_over++;
-        b->result[(size_t)u] = r;
-        continue;
-      }
-      const FstConfRecord &g = b->rec[0][(size_t)u];
-      if (g.has_final && std::memcmp(&g.best_final_lp, &logprob[0], sizeof(float)) != 0)
-        raise(AASR_ERR_INVALID, "aasr_fst_conf_batch_sync: utterance %d: the token record's best end-node token is not the search's", u);
-      r.valid = 1;
-      r.no_final = !g.has_final;
-      r.grammar_logprob = logprob[0];
-      r.ploop_logprob = logprob[1];
-      r.best_final_logprob = g.best_final_lp;  // (-9999999.9f without an end-node token)
-      r.best_different_logprob = g.best_different_lp;
-      r.best_acu_score = b->inner[1] ? b->sum[(size_t)u] : 0.0f;
-      formulas(r, g.has_final ? g.best_final_n_words : 0, b->text[0][(size_t)u], b->inner[1] ? &b->text[1][(size_t)u] : nullptr);
       b->result[(size_t)u] = r;
     }
     b->synced = true;

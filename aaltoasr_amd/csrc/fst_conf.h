@@ -16,9 +16,13 @@
 //                    candidate order): the best end-node token by that kernel's rule (highest log-probability, the earlier
 //                    token among equals), its history id, and the best log-probability among the tokens of any other history
 //                    id -- equal ids are equal word sequences (fst_search.h).  LDS: 48 bytes of wave results.  No atomics.
+// The row sweep of k_fst_frame_best and the body of k_fst_conf_tokens are device functions in fst_conf_frame.h, shared with
+// the streaming entry k_fst_conf_chunk (fst_conf_stream.h), which carries a confidence across the feeds of a live session.
 #pragma once
+#include <string>
 #include <vector>
 
+#include "../../include/aasr.h"
 #include "fst_search.h"
 
 struct aasr_fst_batch;
@@ -51,5 +55,16 @@ void fst_conf_tokens_launch(const FstParams &p, FstConfRecord *rec, int32_t n_la
 // fst_search.cc: the device pointers of a batch (lna and decode unset) and the LNA decode table of a code width
 const FstParams &fst_batch_params(const aasr_fst_batch *b);
 void fst_decode_table(int32_t lnabytes, std::vector<float> &table);
+
+
+// fst_conf.cc, shared with the streaming handle (fst_conf_stream.cc).  The option checks of one search, with the calling
+// function's name; the phone loop's derived history capacity for a longest utterance; and one utterance's result from
+// what a sync fetched: r holds frames and is otherwise zero, status and logprob are the two searches' (phone: FST_OK and
+// -1.0f without a phone loop), g the grammar's record, sum the frames' best values.  -> true when a search overflowed
+// (r keeps the statuses, valid 0); raises when the record's best end-node token is not the search's.
+void fst_conf_check_options(const aasr_fst_options &o, const char *who, const char *which);
+int32_t fst_conf_phone_history(const aasr_fst_options &phone, int64_t longest);
+bool fst_conf_finish(aasr_fst_conf_result &r, const int32_t status[2], const float logprob[2], const FstConfRecord &g, bool phone_loop,
+                     float sum, const std::string &grammar, const std::string &ploop, const char *who, int32_t u);
 
 }  // namespace aasr

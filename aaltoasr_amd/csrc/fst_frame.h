@@ -1,7 +1,8 @@
-// fst_frame.h -- the device body of the FST token pass, shared by its two entries: k_fst_search (fst_search.hip, an
-// utterance's whole frame loop in one launch) and k_fst_search_chunk (fst_stream.hip, the frames of one feed of a
-// session).  One copy of the arithmetic: the start of a search, the six phases of a frame and the result block are the
-// functions below, forced inline into both kernels.  Layout, phases and the reference's line numbers: fst_search.h.
+// fst_frame.h -- the device body of the FST token pass, shared by its entries: k_fst_search (fst_search.hip, an
+// utterance's whole frame loop in one launch), k_fst_search_chunk (fst_stream.hip, the frames of one feed of a
+// session) and, through fst_chunk.h, k_fst_conf_chunk (fst_conf_stream.hip).  One copy of the arithmetic: the start of a
+// search, the six phases of a frame and the result block are the functions below, forced inline into the kernels.
+// Layout, phases and the reference's line numbers: fst_search.h.
 // Included by device code only.
 #pragma once
 #include "fst_search.h"

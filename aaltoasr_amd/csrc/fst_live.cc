@@ -4,7 +4,8 @@
 // + 1; at the end of input, the frames up to aasr_feat_eof_frame).  Per chunk of chunk_frames frames: the feature
 // chain for exactly those frames over the samples so far, ONE score + LNA step (aasr_gmm_score_lna_dev, normalised, as
 // fst_decode's engine mode runs it per group) and one feed of a one-session aasr_fst_stream that reads the step's
-// device buffer in place -- no LNA value leaves the device.
+// device buffer in place -- no LNA value leaves the device.  aasr_run_fst_live_confidence is the same loop over a
+// one-session aasr_fst_conf_stream (fst_stream --confidence): a confidence behind every log-probability it prints.
 #include <hip/hip_runtime.h>
 #include <unistd.h>
 
@@ -32,9 +33,35 @@ void ok(aasr_status s) {
   if (s != AASR_OK) raise(s, "%s", last_error().c_str());
 }
 
-struct StreamGuard {
+// the one live session: an aasr_fst_stream, or with conf an aasr_fst_conf_stream whose grammar search answers for it
+struct Session {
   aasr_fst_stream *s = nullptr;
-  ~StreamGuard() { aasr_fst_stream_destroy(s); }
+  aasr_fst_conf_stream *c = nullptr;
+  ~Session() {
+    aasr_fst_stream_destroy(s);
+    aasr_fst_conf_stream_destroy(c);
+  }
+  void feed(const void *d_lna, int lnabytes, int n_models, int32_t n, hipStream_t stream) {
+    const int64_t row0 = 0;
+    if (c)
+      ok(aasr_fst_conf_stream_feed_dev(c, d_lna, lnabytes, n_models, n, &row0, &n, stream));
+    else
+      ok(aasr_fst_stream_feed_dev(s, d_lna, lnabytes, n_models, n, &row0, &n, stream));
+  }
+  // after a sync: the search's answers (any pointer may be NULL) and, with conf, the confidence's
+  void fetch(hipStream_t stream, int32_t *status, int32_t *frames, float *logprob, float *best, int32_t *n_words, std::vector<int32_t> *words,
+             int32_t *n_partial, std::vector<int32_t> *partial, aasr_fst_conf_result *conf) {
+    int32_t *w = words ? words->data() : nullptr, *pw = partial ? partial->data() : nullptr;
+    const int32_t cw = words ? (int32_t)words->size() : 0, cp = partial ? (int32_t)partial->size() : 0;
+    if (c) {
+      ok(aasr_fst_conf_stream_sync(c, stream));
+      ok(aasr_fst_conf_stream_search_result(c, 0, 0, status, frames, logprob, best, nullptr, n_words, w, cw, n_partial, pw, cp, nullptr));
+      ok(aasr_fst_conf_stream_result(c, 0, conf));
+    } else {
+      ok(aasr_fst_stream_sync(s, stream));
+      ok(aasr_fst_stream_result(s, 0, status, frames, logprob, best, nullptr, n_words, w, cw, n_partial, pw, cp, nullptr));
+    }
+  }
 };
 
 // the descriptor's samples, appended to pcm as they arrive
@@ -75,6 +102,10 @@ struct SampleReader {
   }
 };
 
+aasr_status run_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fstnet *phone_net, const aasr_fst_durations *dur,
+                     const aasr_fst_live_options *opt, const aasr_fst_live_confidence_options *conf, aasr_run_stats *stats,
+                     const char *who);
+
 }  // namespace
 
 extern "C" {
@@ -90,8 +121,35 @@ void aasr_fst_live_default_options(aasr_fst_live_options *o) {
 
 aasr_status aasr_run_fst_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fst_durations *dur,
                               const aasr_fst_live_options *opt, aasr_run_stats *stats) {
+  if (!opt) return guarded([&] { raise(AASR_ERR_INVALID, "aasr_run_fst_live: null argument"); });
+  return run_live(feat, gmm, net, nullptr, dur, opt, nullptr, stats, "aasr_run_fst_live");
+}
+
+void aasr_fst_live_confidence_default_options(aasr_fst_live_confidence_options *o) {
+  if (!o) return;
+  *o = aasr_fst_live_confidence_options();
+  aasr_fst_live_default_options(&o->live);
+  aasr_fst_default_options(&o->phone);
+}
+
+aasr_status aasr_run_fst_live_confidence(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fstnet *phone_net,
+                                         const aasr_fst_durations *dur, const aasr_fst_live_confidence_options *opt,
+                                         aasr_run_stats *stats) {
+  if (!opt) return guarded([&] { raise(AASR_ERR_INVALID, "aasr_run_fst_live_confidence: null argument"); });
+  return run_live(feat, gmm, net, phone_net, dur, &opt->live, opt, stats, "aasr_run_fst_live_confidence");
+}
+
+}  // extern "C"
+
+namespace {
+
+aasr_status run_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fstnet *phone_net, const aasr_fst_durations *dur,
+                     const aasr_fst_live_options *opt, const aasr_fst_live_confidence_options *conf, aasr_run_stats *stats,
+                     const char *who) {
   return guarded([&] {
-    if (!feat || !gmm || !net || !opt) raise(AASR_ERR_INVALID, "aasr_run_fst_live: null argument");
+    if (!feat || !gmm || !net || !opt) raise(AASR_ERR_INVALID, "%s: null argument", who);
+    if (conf && conf->phone_loop && !phone_net) raise(AASR_ERR_INVALID, "%s: phone_loop without a phone-loop network", who);
+    if (conf && !conf->phone_loop) phone_net = nullptr;
     if (opt->lnabytes != 2 && opt->lnabytes != 4) raise(AASR_ERR_INVALID, "Invalid number of LNA bytes");
     if (opt->chunk_frames < 1) raise(AASR_ERR_INVALID, "fst_stream: a chunk must hold at least 1 frame");
     if (opt->max_frames < 1) raise(AASR_ERR_INVALID, "fst_stream: max_frames must be at least 1");
@@ -100,6 +158,8 @@ aasr_status aasr_run_fst_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet 
     const int n_models = aasr_gmm_num_states(gmm);
     if (aasr_fstnet_max_pdf(net) >= n_models)
       raise(AASR_ERR_INVALID, "fst_stream: the network names pdf %d, the model has %d states", aasr_fstnet_max_pdf(net), n_models);
+    if (phone_net && aasr_fstnet_max_pdf(phone_net) >= n_models)
+      raise(AASR_ERR_INVALID, "fst_stream: the phone-loop network names pdf %d, the model has %d states", aasr_fstnet_max_pdf(phone_net), n_models);
     require_device();
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t stream = nullptr;
@@ -112,8 +172,18 @@ aasr_status aasr_run_fst_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet 
     // the samples of max_frames frames and their look-ahead, with room for what one read can bring beyond them
     const double adv = (double)aasr_feat_sample_rate(feat) / (double)aasr_feat_frame_rate(feat);
     const size_t cap_pcm = (size_t)(((double)opt->max_frames + halo_r + 16) * adv) + (size_t)(8 * adv) + (1 << 16);
-    StreamGuard g;
-    ok(aasr_fst_stream_create(net, dur, &opt->fst, 1, opt->max_frames, &g.s));
+    Session g;
+    if (conf) {
+      aasr_fst_conf_options co;
+      aasr_fst_conf_default_options(&co);
+      co.grammar = opt->fst;
+      co.phone = conf->phone;
+      co.phone_loop = phone_net != nullptr;
+      co.verbose = 0;
+      ok(aasr_fst_conf_stream_create(net, phone_net, dur, &co, 1, opt->max_frames, &g.c));
+    } else {
+      ok(aasr_fst_stream_create(net, dur, &opt->fst, 1, opt->max_frames, &g.s));
+    }
     DevBuf<int16_t> d_pcm;
     DevBuf<float> d_fea, d_scratch;
     DevBuf<uint8_t> d_lna;
@@ -151,19 +221,17 @@ aasr_status aasr_run_fst_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet 
         ub.first = {done};
         feat_run_batch(feat, d_pcm.p, ub, (int)feat->mods.size() - 1, d_fea.p, nullptr, stream);
         ok(aasr_gmm_score_lna_dev(gmm, d_fea.p, n, 1, lnabytes, d_scratch.p, d_lna.p, stream));
-        const int64_t row0 = 0;
-        const int32_t n_new = n;
-        ok(aasr_fst_stream_feed_dev(g.s, d_lna.p, lnabytes, n_models, n, &row0, &n_new, stream));
+        g.feed(d_lna.p, lnabytes, n_models, n, stream);
         done += n;
         if (opt->partial) {  // a line whenever the best token's words are not the ones printed last
           int32_t status = 0, frames = 0, np = 0;
           float best = 0;
-          ok(aasr_fst_stream_sync(g.s, stream));
-          ok(aasr_fst_stream_result(g.s, 0, &status, &frames, nullptr, &best, nullptr, nullptr, nullptr, 0, &np, partial.data(),
-                                    (int32_t)partial.size(), nullptr));
+          aasr_fst_conf_result cr{};
+          g.fetch(stream, &status, &frames, nullptr, &best, nullptr, nullptr, &np, &partial, &cr);
           const std::vector<int32_t> now(partial.begin(), partial.begin() + np);
           if (status == AASR_FST_OK && (!printed_any ? !now.empty() : now != printed)) {
             printf("%d %.9g", frames, (double)best);
+            if (conf) printf(" %.9g", (double)cr.confidence);
             for (int32_t w : now) printf(" %s", aasr_fstnet_symbol(net, w));
             printf("\n");
             fflush(stdout);
@@ -176,11 +244,12 @@ aasr_status aasr_run_fst_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet 
     }
     int32_t status = 0, n_words = 0;
     float logprob = -1;
-    ok(aasr_fst_stream_sync(g.s, stream));
-    ok(aasr_fst_stream_result(g.s, 0, &status, nullptr, &logprob, nullptr, nullptr, &n_words, words.data(), (int32_t)words.size(), nullptr,
-                              nullptr, 0, nullptr));
+    aasr_fst_conf_result cr{};
+    g.fetch(stream, &status, nullptr, &logprob, nullptr, &n_words, &words, nullptr, nullptr, &cr);
     printf("- %.9g", (double)logprob);
+    if (conf) printf(" %.9g", (double)cr.confidence);
     for (int32_t i = 0; i < n_words; i++) printf(" %s", aasr_fstnet_symbol(net, words[(size_t)i]));
+    if (conf && status == AASR_FST_OK) status = cr.phone_status;  // (the grammar's status first, as fst_decode --confidence)
     if (status != AASR_FST_OK) printf(" %s", STATUS[status]);
     printf("\n");
     fflush(stdout);
@@ -189,4 +258,4 @@ aasr_status aasr_run_fst_live(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet 
   });
 }
 
-}  // extern "C"
+}  // namespace

@@ -4,7 +4,8 @@
 // utterance lives in global memory already (fst_search.h: the tokens t_*, the history table h_key, the recombination
 // table, which every frame leaves empty); what a launch of k_fst_search keeps in registers and LDS is the record below.
 // k_fst_search_chunk, one workgroup of FST_THREADS per session, restores it, runs the frames of one feed with the batch
-// kernel's own frame body (fst_frame.h) and saves it again.
+// kernel's own frame body (fst_frame.h) and saves it again.  That body of a feed is fst_chunk.h's fst_chunk, which
+// k_fst_conf_chunk (fst_conf_stream.h) runs too, once per network of a confidence.
 //
 //   fresh (the feed's flag, or the record's after creation)   the start of k_fst_search: both tables cleared, one
 //                 token at the initial node with 0.0f, dur 0 and no words, frames_done = 0

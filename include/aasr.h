@@ -1798,8 +1798,8 @@ aasr_status aasr_fst_batch_tokens(aasr_fst_batch *b, int32_t u, int32_t cap_toke
  * stream cannot be re-run from frames that are gone, and the tables of a live session do not grow -- choose max_frames
  * and the capacities for the longest utterance expected.  frames_done counts the frames consumed, the one that ended the
  * search (NO_TOKENS, OVERFLOW_*) included, so it does not depend on where the feeds were cut.
- * Out of scope: confidence scores on a stream (they need the whole utterance's sums and the phone loop), growing a table
- * of a live session, endpointing, one session over several workgroups.
+ * Confidence scores on a stream: aasr_fst_conf_stream_*, the block "FST decoder: confidence on streaming sessions" below.
+ * Out of scope: growing a table of a live session, endpointing, one session over several workgroups.
  * One stream per handle: feeds and syncs of a handle go to the same `stream`. */
 typedef struct aasr_fst_stream aasr_fst_stream;
 /* Sessions start fresh.  n_sessions < 1, max_frames < 1 or a null argument: AASR_ERR_INVALID.  net and dur (may be NULL)
@@ -1966,6 +1966,76 @@ int32_t aasr_fst_conf_remove_junk(const char *s, int32_t n, char *out, int32_t c
 int32_t aasr_fst_conf_edit_distance(const char *a, int32_t na, const char *b, int32_t nb);
 void aasr_fst_conf_formulas(aasr_fst_conf_result *r, int32_t n_words, const char *grammar, int32_t n_grammar, const char *ploop,
                             int32_t n_ploop);
+
+/* ---- FST decoder: confidence on streaming sessions ---------------------------------------------------------------------
+ * aasr_fst_conf_batch cut at feed boundaries: n_sessions live utterances whose two searches (aasr_fst_stream's state, once
+ * per network), token records and best-acoustics sums stay on the device between launches.  One launch per feed runs a
+ * session's grammar search, its phone-loop search and its sum as sibling workgroups (csrc/fst_conf_stream.h), so a feed
+ * waits for the slower of the two searches, not for one after the other.
+ * The contract: after any sequence of feeds that gave a session t frames since its reset, aasr_fst_conf_stream_result is
+ * field for field and bit for bit what aasr_fst_conf_batch returns for an utterance of those t rows under the same options
+ * -- t = 0 with its IEEE division; AASR_FST_NO_TOKENS in either search (valid, the sentinels as in the batch);
+ * AASR_FST_OVERFLOW_* in either search (valid 0, floats 0, the statuses reported).  A confidence is there at every feed
+ * boundary, not only at the end.
+ * Capacities: as aasr_fst_stream_create derives them, for both searches, with max_frames in the place of the longest
+ * utterance; the phone loop's derived history table is the confidence batch's larger one.
+ * Each search's status is sticky as in aasr_fst_stream and an overflow is never rerun.  The sum is carried for every fed
+ * frame whatever the searches' statuses, and so is `frames`: this handle counts the frames fed per session for every
+ * accepted feed; each search's own frames_done is reported by aasr_fst_conf_stream_search_result.
+ * One stream per handle: feeds and syncs of a handle go to the same `stream`. */
+typedef struct aasr_fst_conf_stream aasr_fst_conf_stream;
+/* Sessions start fresh.  phone_net NULL without a phone loop.  A null argument, n_sessions < 1, max_frames < 1, bad options
+ * of either search and phone_loop without a network are AASR_ERR_INVALID before a device is looked for.  The networks and
+ * dur (may be NULL) must outlive the handle. */
+aasr_status aasr_fst_conf_stream_create(const aasr_fstnet *grammar_net, const aasr_fstnet *phone_net, const aasr_fst_durations *dur,
+                                        const aasr_fst_conf_options *opt, int32_t n_sessions, int32_t max_frames,
+                                        aasr_fst_conf_stream **out);
+void aasr_fst_conf_stream_destroy(aasr_fst_conf_stream *s);
+int64_t aasr_fst_conf_stream_device_bytes(const aasr_fst_conf_stream *s);
+/* the options with both searches' derived capacities filled in */
+void aasr_fst_conf_stream_options(const aasr_fst_conf_stream *s, aasr_fst_conf_options *out);
+/* Marks session u (-1: every session) fresh, as aasr_fst_stream_reset: both searches and the sum start anew at the next
+ * feed; until then the session answers with the zero-frame result of the batch. */
+aasr_status aasr_fst_conf_stream_reset(aasr_fst_conf_stream *s, int32_t u);
+/* One feed, arguments as aasr_fst_stream_feed_dev.  Only queues: one small copy and the one launch on `stream`.  Refused
+ * with AASR_ERR_INVALID before anything is queued, every session left as it was: a negative n_new[u]; frames fed + n_new[u]
+ * > max_frames; a row range outside 0 ... n_rows; a pdf of either network that is not below n_models; an lnabytes or
+ * n_models other than what a session that is not fresh was fed before; d_lna not aligned to lnabytes. */
+aasr_status aasr_fst_conf_stream_feed_dev(aasr_fst_conf_stream *s, const void *d_lna, int32_t lnabytes, int32_t n_models, int64_t n_rows,
+                                          const int64_t *row0, const int32_t *n_new, void *stream);
+/* Waits for the feeds queued on `stream`, fetches the records, the sums and both searches' results, and computes the
+ * confidences on the host with aasr_fst_conf_batch_sync's own code. */
+aasr_status aasr_fst_conf_stream_sync(aasr_fst_conf_stream *s, void *stream);
+/* session u after a sync: the fields of aasr_fst_conf_batch_result for the frames fed so far */
+aasr_status aasr_fst_conf_stream_result(const aasr_fst_conf_stream *s, int32_t u, aasr_fst_conf_result *out);
+/* The grammar search (phone 0) or the phone-loop search (phone 1) of session u: as aasr_fst_stream_result and
+ * aasr_fst_stream_tokens.  phone 1 without a phone loop is AASR_ERR_INVALID. */
+aasr_status aasr_fst_conf_stream_search_result(const aasr_fst_conf_stream *s, int32_t u, int32_t phone, int32_t *status,
+                                               int32_t *frames_done, float *logprob, float *best_logprob, float *best_final_logprob,
+                                               int32_t *n_words, int32_t *words, int32_t cap_words, int32_t *n_partial_words,
+                                               int32_t *partial_words, int32_t cap_partial, int32_t *n_tokens);
+aasr_status aasr_fst_conf_stream_tokens(aasr_fst_conf_stream *s, int32_t u, int32_t phone, int32_t cap_tokens, int32_t *node,
+                                        float *logprob, int32_t *dur, int32_t *word_begin, int32_t cap_words, int32_t *words);
+/* the device's token record of session u, as aasr_fst_conf_batch_record */
+aasr_status aasr_fst_conf_stream_record(const aasr_fst_conf_stream *s, int32_t u, int32_t phone, int32_t *has_final, int32_t *n_words,
+                                        int32_t *has_different, float *best_final_logprob, float *best_different_logprob);
+/* the carried sum of the frames' best acoustic values and the frames it covers (with a phone loop only: the plain
+ * FstConfidence never uses the sum, and it is not carried) */
+aasr_status aasr_fst_conf_stream_best_acu(const aasr_fst_conf_stream *s, int32_t u, float *sum, int32_t *frames);
+
+/* fst_stream --confidence (csrc/fst_live.cc): aasr_run_fst_live's chunk loop with a one-session aasr_fst_conf_stream in
+ * the place of the aasr_fst_stream.  With live.partial the lines are `frames best_logprob confidence words...`; the final
+ * line is fst_decode --confidence's with `-` as the path: `- logprob confidence words... [STATUS]` (the grammar's status
+ * first, else the phone loop's). */
+typedef struct aasr_fst_live_confidence_options {
+  aasr_fst_live_options live;  /* live.fst is the grammar search */
+  aasr_fst_options phone;
+  int32_t phone_loop;
+} aasr_fst_live_confidence_options;
+void aasr_fst_live_confidence_default_options(aasr_fst_live_confidence_options *opt);
+aasr_status aasr_run_fst_live_confidence(aasr_feat *feat, aasr_gmm *gmm, const aasr_fstnet *net, const aasr_fstnet *phone_net,
+                                         const aasr_fst_durations *dur, const aasr_fst_live_confidence_options *opt,
+                                         aasr_run_stats *stats);
 
 /* fst_decode --confidence over a recipe: the group loop of aasr_run_fst_decode_recipe with a confidence batch per group;
  * the group's LNA device buffer feeds both searches and the frame-best pass.  Output lines: path, log-probability and
